@@ -34,6 +34,7 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as graft  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together, .npy headers included
 
 WORKLOADS = {
     # BASELINE.json configs[1]: SIFT-1M-shaped, 16 tables x 32 bits (m=16, lambda=2, divisions=1), B=256, batch=1024
@@ -129,6 +130,24 @@ def make_data(kind, n, d, nb, q, seed, rank):
     return X, np.ascontiguousarray(Qs), f"{os.path.basename(kind)} ({len(X)} x {d}), queries tiled to {nb} x {q}"
 
 
+def dump_outputs(out_dir, arrays):
+    """Write {name: [rows, ...] array} as out_dir/<name>.npy in float64 (int32 ids and counts are exact in it).  Beyond
+    DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of rows (queries), whose indices go to rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k_: np.asarray(v_, dtype=np.float64) for k_, v_ in arrays.items()}
+    nrows = len(next(iter(arrays.values())))
+    row_bytes = sum(a_[0].nbytes for a_ in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 1024 * (len(arrays) + 1)          # (a .npy header is at most a few hundred bytes)
+    if nrows * row_bytes > budget:
+        keep = budget // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(nrows, keep, replace=False))
+        arrays = {k_: a_[rows] for k_, a_ in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for k_, a_ in arrays.items():
+        np.save(os.path.join(out_dir, k_ + ".npy"), a_)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -177,7 +196,12 @@ def main():
                          "costs the region about two steps per reading).  Default: the solo readings come from the untimed tail (--solo-tail), the "
                          "timed region holds exactly --steps pipeline steps and only the overlapped readings")
     ap.add_argument("--launch-check", action="store_true", help="(tests) only prove the N-rank launch: every rank joins a gloo group, rank 0 prints one JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's top-k ids, fp64 distances, result "
+                         "counts, scored candidates) as DIR/<name>.npy in float64, to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` with N > 1 and no rank environment: start the N ranks ourselves — a CHILD torch.distributed.run,
     # spawned before this process touches the GPU (no exec: replacing a process that initialised the GPU takes the box down), its
@@ -361,11 +385,14 @@ def main():
                        f"one collective per {MG} batches of a context"
                        if lib_ok else "torch.distributed all_gather_into_tensor")
 
+    last_out = [None]     # (buffers, parity, slot) of the batch the latest step wrote its top-k to (--dump-outputs)
+
     def out_slot(b):
         """packed top-k destination of the context's next batch: (parity, ids pointer, distances pointer, last batch of its group)"""
         n = b["nsteps"]
         b["nsteps"] += 1
         par, slot = (n // MG) & 1, n % MG
+        last_out[0] = (b, par, slot)
         tk = b["topk"][par]
         return par, tk.ids.data_ptr() + slot * Q * k * 4, tk.dist.data_ptr() + slot * Q * k * 8, slot == MG - 1
 
@@ -637,6 +664,14 @@ def main():
         tick_fused = False
     overlapped_main = overlapped[0]
     host_issue_main = host_issue_s[0]
+    if args.dump_outputs and rank == 0:
+        # the timed region ends synchronised: what its last step returned is final in that context's buffers
+        lb, lpar, lslot = last_out[0]
+        ltk = lb["topk"][lpar]
+        names = dump_outputs(args.dump_outputs, dict(
+            topk_ids=ltk.ids[lslot * Q:(lslot + 1) * Q].cpu().numpy(), topk_dist=ltk.dist[lslot * Q:(lslot + 1) * Q].cpu().numpy(),
+            topk_count=lb["out_cnt"].cpu().numpy(), scored=lb["scored"].cpu().numpy()))
+        log("[bench] last timed step's outputs written to %s: %s" % (args.dump_outputs, ", ".join(n_ + ".npy" for n_ in names)))
     # ---------------- what was timed is what is checked: the LAST step each context ran inside the timed region (front_kernel +
     # the scan that finishes PENDING queries, on the clones' own streams) against the plain three-launch path on context 0 for the
     # same batch here, and against the CPU oracle in the cpu_baseline leg ------------------------------------------------------

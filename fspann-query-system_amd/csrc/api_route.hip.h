@@ -106,9 +106,9 @@ int plan_route(fspann_ctx* c, int probe_override, int64_t nq, int32_t limit, Rou
     const bool legal = c->d_inv && c->d_ids_bk && c->bk_epoch == c->meta_epoch && !pl.need_cap && cap_fixed && !want_counters && limit <= (for_tick ? 512 : 1024) && pl.lds_mode && check_ok;
     if (legal && c->route_mode != 1 && (c->route_mode == 2 || static_cast<int64_t>(limit) * 4 <= mt)) {
         const int cap_env = c->knob_lazy_cap;   // tests: distinct ids one query may hold before it is handed back
-        // size class: 512 entries (19.6 KB, 6 workgroups per CU) when limit <= 256 and the probe's scratch fits the smaller key
+        // size class: 512 entries (19.7 KB, 8 workgroups per CU at 16 x 5) when limit <= 256 and the probe's scratch fits the smaller key
         // array; the tick kernel keeps the large class (its redo runs the full select over the same LDS)
-        // (the 512-entry kernel is built WITHOUT the exact treeify check: its loads live across the ordering step and would spill at 80
+        // (the 512-entry kernel is built WITHOUT the exact treeify check: its loads live across the ordering step and would spill at 64
         // registers — and any scratch use costs every dispatch of the stream; a checked Route takes the 1024-entry class, 4 per CU)
         const bool small_cls = c->knob_lazy_small && !for_tick && !pl.bincheck && limit <= 256 && (kLzThreads / 16) * (2 * pl.P - 1) * 12 <= 512 * 4;
         const int kent = small_cls ? 512 : (limit <= 512 ? kLzEntriesMax : 2048);

@@ -34,23 +34,46 @@ namespace fspann {
 constexpr uint64_t kLzEmpty = ~0ull;
 constexpr int kLzThreads = 256;
 // Three size classes (template parameter kEnt = distinct ids one query may hold before it is handed over): 512 for limit <= 256
-// (19.6 KB of LDS, 6 workgroups per CU: the kernel's throughput follows its workgroups per CU), 1024 for
-// limit <= 512 (33 KB, 4 per CU) and 2048 for limit <= 1024 (BASELINE config #4's B; 63 KB, 2 per CU).
+// (19.7 KB of LDS at 16 x 5, 64 vector and 78 scalar registers: 8 workgroups per CU — the kernel's throughput follows its workgroups
+// per CU), 1024 for limit <= 512 (35 KB, 4 per CU) and 2048 for limit <= 1024 (BASELINE config #4's B; 65 KB, 2 per CU).
 constexpr int kLzEntriesMax = 1024;
 constexpr int kLzCollMax = 256;     // entries sharing (score, bucket) with another one
 constexpr int lz_ht_size(int kEnt) { return 2 * kEnt; }          // hash slots (64-bit entries): load <= 0.5
 constexpr int lz_sort_max(int kEnt) { return kEnt - 128; }       // entries the rank pass takes (16 slices padded to multiples of 8 stay < kEnt)
-constexpr size_t lz_lds_bytes(int kEnt, int TD, int P) {         // dynamic LDS of route_lazy_run (host and device agree through this)
-    return static_cast<size_t>(lz_ht_size(kEnt)) * 8 + static_cast<size_t>(TD) * P * 16 + static_cast<size_t>(kEnt) * 4 + 4096 +
-           (static_cast<size_t>(TD) * P + 2) * 8 + (static_cast<size_t>(TD) * P + 1) * 4 + 8 + static_cast<size_t>(TD) * 8 +
-           ((static_cast<size_t>(TD) * P * 2 + 3) & ~size_t(3)) + static_cast<size_t>(kEnt) * 2 * 3 + static_cast<size_t>(kEnt) * 4 +
-           static_cast<size_t>(TD) * P * 8 + static_cast<size_t>(TD) * 4 + 16 + static_cast<size_t>(TD) * 4 + static_cast<size_t>(TD) * P * 4;
+// the probe ordering's arrays (pkv, pcs, pbase, ord: dead once the levels are walked) share their bytes with the rank pass's
+// grouped keys (gk: live only in the rank pass)
+constexpr size_t lz_order_bytes(int TP) {
+    return static_cast<size_t>(TP + 2) * 8 + ((static_cast<size_t>(TP + 1) * 4 + 7) & ~size_t(7)) + static_cast<size_t>(TP) * 8 +
+           ((static_cast<size_t>(TP) * 2 + 3) & ~size_t(3));
 }
+constexpr size_t lz_lds_bytes(int kEnt, int TD, int P) {         // dynamic LDS of route_lazy_run (host and device agree through this)
+    const size_t tp = static_cast<size_t>(TD) * P, ord_gk = lz_order_bytes(TD * P), gk = static_cast<size_t>(lz_sort_max(kEnt)) * 4;
+    return static_cast<size_t>(lz_ht_size(kEnt)) * 8 + tp * 16 + static_cast<size_t>(kEnt) * 4 + 4096 +
+           (((ord_gk > gk ? ord_gk : gk) + 7) & ~size_t(7)) + static_cast<size_t>(TD) * 8 + static_cast<size_t>(kEnt) * 2 +
+           static_cast<size_t>(lz_sort_max(kEnt)) * 2 * 2 + static_cast<size_t>(TD) * 4 +
+           (kEnt != 512 ? static_cast<size_t>(TD) * 4 + tp * 4 : 0);   // part0 / pglob: the treeify check only (not in the 512-entry class)
+}
+// BASELINE config #2 / #3's shape (16 tables x 5 probes) in the 512-entry class: eight workgroups per CU by LDS, the eight ints of
+// static LDS and the host's 256-byte margin included (tests/test_route_residency.py checks the registers)
+static_assert(lz_lds_bytes(512, 16, 5) == 20152 && lz_lds_bytes(512, 16, 5) + 256 <= 160 * 1024 / 8, "eight per CU at 16 x 5");
 // probed partitions in flight per wave (lz_stage_u) and partitions of the crossing level one wave keeps in registers (lz_keep).
-// (Halving both fits the small class into 64 registers = 8 workgroups per CU, but a lone launch then takes 52 us instead of 42
-// and three overlapped ones gain nothing: measured, not used.)
+// Both stay as they are at eight workgroups per CU: halving them (an earlier way to 64 registers) made a lone launch take 52 us
+// instead of 42, and at that time the workgroups per CU were held at 6 by LDS (23.1 KB) and scalar registers (106) anyway.
+// At 16 x 5 the compiler now fits __launch_bounds__(256, 8) without scratch: the one value it spilled was the constant of the
+// odd-list sentinel, which an even probe list never reads.
 constexpr int lz_stage_u(int) { return 4; }
 constexpr int lz_keep(int) { return 8; }
+
+#ifdef FSPANN_DEBUG_STAMPS
+// Residency census (debug builds, tools/route_residency.py): where the calling wave runs, XCC_ID << 32 | HW_ID.  HW_ID[15:8]
+// holds the shader engine, shader array and CU; with the XCC they name one CU of the chip.
+__device__ __forceinline__ long long dbg_hw_where() {
+    uint32_t hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    return (static_cast<long long>(xcc) << 32) | hw;
+}
+#endif
 
 // wave_find_cut for exactly 1024 bins starting at a 16-byte aligned address: each lane takes 16 bins with four
 // 16-byte reads and walks ITS bins out of registers (no second LDS pass).  One wave; result in every lane.
@@ -91,7 +114,7 @@ __device__ __forceinline__ int wave_cut1024(const int32_t* bins, int need, int l
 // (`smem` = its dynamic LDS, `block_id` = its slice of the global fallback arena).  Called by route_select_lazy_kernel
 // and by the route role of tick_kernel (tick.hip.h).
 // kChk: built with the exact treeify check (step 0; it runs when prm.bin16 is set).  A template parameter because the check's
-// loads live across the ordering step: in the 512-entry class (80 registers at six workgroups per CU) they would spill, and any
+// loads live across the ordering step: in the 512-entry class (64 registers at eight workgroups per CU) they would spill, and any
 // scratch use costs every dispatch of the stream — that class is built without it, and a checked Route takes the 1024-entry class.
 // kTD / kP (0 = run-time values): the tables x probes shape as compile-time constants.  With them every LDS array base, trip count
 // and division by T*D*P below is an immediate; left to run time the kernel computes ~60 scalars in its prologue, keeps them for the
@@ -118,18 +141,21 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
     int4* plist = reinterpret_cast<int4*>(smem + o);             o += static_cast<size_t>(TP) * 16;
     uint32_t* pre = reinterpret_cast<uint32_t*>(smem + o);       o += static_cast<size_t>(kEnt) * 4;   // (score << 20 | bucket) per entry
     int32_t* bins = reinterpret_cast<int32_t*>(smem + o);        o += 1024 * 4;
+    const size_t o_ord = o;                                      // [pkv pcs pbase ord] until the rank pass, then [gk]
     uint2* pkv = reinterpret_cast<uint2*>(smem + o);             o += (static_cast<size_t>(TP) + 2) * 8;   // {distance << 16 | probe index, size}, padded to even
     int32_t* pcs = reinterpret_cast<int32_t*>(smem + o);         o += (static_cast<size_t>(TP) + 1) * 4;
     o = (o + 7) & ~size_t(7);
-    int64_t* ids_base = reinterpret_cast<int64_t*>(smem + o);    o += static_cast<size_t>(TD) * 8;
     int64_t* pbase = reinterpret_cast<int64_t*>(smem + o);       o += static_cast<size_t>(TP) * 8;   // per probed partition: position of its first id in ids_bk
-    uint16_t* ord = reinterpret_cast<uint16_t*>(smem + o);       o += (static_cast<size_t>(TP) * 2 + 3) & ~size_t(3);
+    uint16_t* ord = reinterpret_cast<uint16_t*>(smem + o);
+    uint32_t* gk = reinterpret_cast<uint32_t*>(smem + o_ord);    // the keys grouped by their top bits (rank pass): < kLzSortMax
+    o = o_ord + ((max(lz_order_bytes(TP), static_cast<size_t>(kLzSortMax) * 4) + 7) & ~size_t(7));
+    int64_t* ids_base = reinterpret_cast<int64_t*>(smem + o);    o += static_cast<size_t>(TD) * 8;
     uint16_t* ulist = reinterpret_cast<uint16_t*>(smem + o);     o += static_cast<size_t>(kLzEntries) * 2;   // hash slots of the entries
-    uint16_t* rk = reinterpret_cast<uint16_t*>(smem + o);        o += static_cast<size_t>(kEnt) * 2;   // entries per (score, bucket) rank: > 1 = collision
-    uint16_t* lrank = reinterpret_cast<uint16_t*>(smem + o);     o += static_cast<size_t>(kEnt) * 2;   // (score, bucket) rank of each entry
-    uint32_t* gk = reinterpret_cast<uint32_t*>(smem + o);        o += static_cast<size_t>(kEnt) * 4;   // the keys grouped by their top bits (rank pass)
+    uint16_t* rk = reinterpret_cast<uint16_t*>(smem + o);        o += static_cast<size_t>(kLzSortMax) * 2;   // entries per (score, bucket) rank: > 1 = collision
+    uint16_t* lrank = reinterpret_cast<uint16_t*>(smem + o);     o += static_cast<size_t>(kLzSortMax) * 2;   // (score, bucket) rank of each entry
     int32_t* nprobe_l = reinterpret_cast<int32_t*>(smem + o);    o += static_cast<size_t>(TD) * 4;   // [TD] fused probe: partitions probed per table
-    int32_t* part0 = reinterpret_cast<int32_t*>(smem + o);       o += static_cast<size_t>(TD) * 4;   // first partition of each table (global numbering)
+    // the check's arrays exist in the classes that may be built with it (the host's lz_lds_bytes counts them there only)
+    int32_t* part0 = reinterpret_cast<int32_t*>(smem + o);       if (kEnt != 512) o += static_cast<size_t>(TD) * 4;   // first partition of each table (global numbering)
     int32_t* pglob = reinterpret_cast<int32_t*>(smem + o);       // [TP] global number of each probed partition: its row of bin16
     // collision records alias the histogram (free once the levels are in): element, prefix rank, id, sequence
     int32_t* c_elem = bins;
@@ -142,7 +168,7 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
     constexpr int ht_shift = (kEnt == 2048) ? 32 - 12 : (kEnt == 1024) ? 32 - 11 : 32 - 10;   // 32 - log2(hash slots)
     unsigned long long lt_mask = 0;
 
-    for (int i = tid; i < TD; i += nthreads) { ids_base[i] = prm.tables[i].ids_base; part0[i] = static_cast<int32_t>(prm.tables[i].part_base); }
+    for (int i = tid; i < TD; i += nthreads) { ids_base[i] = prm.tables[i].ids_base; if (kChk) part0[i] = static_cast<int32_t>(prm.tables[i].part_base); }
     for (int i = tid; i < kLzHtSize; i += nthreads) ht[i] = kLzEmpty;
     if (kChk && prm.bin16) for (int i = tid; i < 1024; i += nthreads) bins[i] = 0;   // the check's counters (step 0) start clear
     if (block_id == 0 && tid == 0) *prm.ovf_next = 0;   // the other counter, for the next call (stream-ordered after this one)
@@ -270,7 +296,7 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
                 if (step < nprobe_l[td]) e = plist[i];
                 plist[i] = e;
                 pbase[i] = ids_base[td] + e.z;      // (a division by P per tuple trip otherwise: the table of a probe is i / P)
-                pglob[i] = part0[td] + e.x;
+                if (kChk) pglob[i] = part0[td] + e.x;
                 pkv[i] = make_uint2((static_cast<uint32_t>(e.y) << 16) | static_cast<uint32_t>(i), static_cast<uint32_t>(e.w));
             }
         } else {
@@ -280,11 +306,16 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
                 if (step < nprobe_in[qi * TD + td]) e = probe_in[qi * TP + i];
                 plist[i] = e;
                 pbase[i] = ids_base[td] + e.z;
-                pglob[i] = part0[td] + e.x;
+                if (kChk) pglob[i] = part0[td] + e.x;
                 pkv[i] = make_uint2((static_cast<uint32_t>(e.y) << 16) | static_cast<uint32_t>(i), static_cast<uint32_t>(e.w));
             }
         }
-        if (tid == 0) { s_u = 0; s_R = TP; s_ncoll = 0; s_bad = 0; s_short = 0; s_susp = 0; pkv[TP] = make_uint2(0xFFFFFFFFu, 0u); }
+        if (tid == 0) {
+            s_u = 0; s_R = TP; s_ncoll = 0; s_bad = 0; s_short = 0; s_susp = 0;
+            // the ordering reads probes in pairs: an odd list ends in a sentinel (rewritten per query: gk overwrites it).  For an
+            // even list (16 x 5) nothing reads it, and leaving the store out spares a register pair held through the whole query
+            if (TP & 1) pkv[TP] = make_uint2(0xFFFFFFFFu, 0u);
+        }
         __syncthreads();
         LZ_STAMP(1);
         LZ_STOP(1)
@@ -645,7 +676,7 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
             const uint32_t smin = pkv[ord[0]].x >> 16;                       // the lowest distance level: no entry scores below it
             auto coarse = [&](const uint32_t key) -> uint32_t { return min((key - (smin << kBucketBits)) >> (kBucketBits - 6), 1023u); };
             for (int i = tid; i < kEnt; i += nthreads) pre[i] = (i < nsel) ? static_cast<uint32_t>(ht[ulist[i]]) : 0xFFFFFFFFu;
-            for (int i = tid; i < kEnt / 2; i += nthreads) reinterpret_cast<uint32_t*>(rk)[i] = 0u;
+            for (int i = tid; i < kLzSortMax / 2; i += nthreads) reinterpret_cast<uint32_t*>(rk)[i] = 0u;
             for (int i = tid; i < 1024; i += nthreads) bins[i] = 0;
             __syncthreads();
             LZ_STAMP(4);
@@ -792,8 +823,11 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
 }
 
 template <int kThreads, int kEnt, bool kChk, int kTD = 0, int kP = 0>
-__global__ __launch_bounds__(kThreads, (kEnt <= 512 ? 6 : (kEnt <= 1024 ? 4 : 2))) void route_select_lazy_kernel(RouteParams prm) {
+__global__ __launch_bounds__(kThreads, (kEnt <= 512 ? (kTD > 0 ? 8 : 6) : (kEnt <= 1024 ? 4 : 2))) void route_select_lazy_kernel(RouteParams prm) {
     extern __shared__ __align__(16) unsigned char smem[];
+#ifdef FSPANN_DEBUG_STAMPS
+    if (prm.dbg && threadIdx.x == 0) prm.dbg[blockIdx.x * 16 + 9] = dbg_hw_where();   // (slot 9: free among the phase stamps)
+#endif
     route_lazy_run<kThreads, kEnt, kChk, kTD, kP>(prm, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), static_cast<int>(blockIdx.x));
 }
 

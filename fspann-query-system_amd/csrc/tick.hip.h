@@ -107,15 +107,23 @@ __global__ __launch_bounds__(kTickThreads, 4) void tick_kernel(const TickHead h,
 }
 
 // encode(batch t+1) + Route(batch t) as one launch, nothing else: the two stages in front of the host's decrypt loop.  Without a
-// Refine role the launch needs only the bounded select's LDS and registers — in its 512-entry class 19.6 KB and 80 registers, six
-// workgroups per CU — and the encode workgroups (one wave per SIMD, bound by the issue rate of a lone wave) fill slots beside
+// Refine role the launch needs only the bounded select's LDS and registers — in its 512-entry class at 16 x 5 19.7 KB and 64 registers,
+// eight workgroups per CU — and the encode workgroups (one wave per SIMD, bound by the issue rate of a lone wave) fill slots beside
 // the Route workgroups instead of holding the chip for a launch of their own.
 template <int kEnt, bool kChk, int kTD = 0, int kP = 0>
-__global__ __launch_bounds__(kTickThreads, (kEnt <= 512 ? 6 : 4)) void front_kernel(const TickHead h, const EncodeArgs<float> enc, const RouteParams route) {
+__global__ __launch_bounds__(kTickThreads, (kEnt <= 512 ? (kTD > 0 ? 8 : 6) : 4)) void front_kernel(const TickHead h, const EncodeArgs<float> enc, const RouteParams route) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int b = static_cast<int>(blockIdx.x);
+#ifdef FSPANN_DEBUG_STAMPS
+    // residency census (tools/route_residency.py): [grid][4] = {role, where (dbg_hw_where), start, end}
+    if (h.dbg && threadIdx.x == 0) { h.dbg[b * 4 + 0] = (b < h.n_enc) ? kTickEncode : kTickRoute; h.dbg[b * 4 + 1] = dbg_hw_where(); h.dbg[b * 4 + 2] = wall_clock64(); }
+#endif
     if (b < h.n_enc) encode_exact_block<float, kTickEncQB>(enc, b % h.enc_gx, b / h.enc_gx, reinterpret_cast<int32_t*>(smem));
     else route_lazy_run<kLzThreads, kEnt, kChk, kTD, kP>(route, smem, b - h.n_enc, h.n_route, b - h.n_enc);
+#ifdef FSPANN_DEBUG_STAMPS
+    __syncthreads();
+    if (h.dbg && threadIdx.x == 0) h.dbg[b * 4 + 3] = wall_clock64();
+#endif
 }
 
 // The stand-alone streaming scan (refine_stream_kernel) for a batch whose Route ran with a hand-over buffer: every workgroup

@@ -308,6 +308,10 @@ int fspann_ctx_create(int device, const fspann_cfg* cfg, fspann_ctx** out) {
         c->knob_tick_fuse = env_int("FSPANN_TICK_FUSE", 1) != 0;
         c->knob_wave_sort = env_int("FSPANN_ROUTE_WAVE_SORT", 1);      // 1: per-wave group sorts, 0: whole-workgroup group sorts, -1: general sort only
         c->knob_tick_front = std::min(100, std::max(0, env_int("FSPANN_TICK_FRONT", 100)));
+        {
+            const char* fe = getenv("FSPANN_FRONT_ENCODE");
+            c->knob_front_encode = (fe && std::strcmp(fe, "exact") == 0) ? 0 : 1;   // unset / "mfma": the MFMA role
+        }
     }
     c->h_min.resize(c->TD); c->h_max.resize(c->TD); c->h_off.resize(c->TD); c->h_rep.resize(c->TD); c->h_ids.resize(c->TD);
     c->h_table_set.assign(c->TD, 0);

@@ -11,6 +11,7 @@ size_t fspann_route_handover_bytes(fspann_ctx* c, int64_t nq, int probe_override
     return ((static_cast<size_t>(nq) * TP * 16 + 255) & ~size_t(255)) + static_cast<size_t>(nq) * c->TD * 4 + 256;
 }
 int fspann_last_tick_fused(fspann_ctx* c) { return c ? c->last_tick_fused : 0; }
+int fspann_last_front_encode_mfma(fspann_ctx* c) { return c ? c->last_front_encode_mfma : 0; }
 
 }  // extern "C"
 namespace {
@@ -43,6 +44,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         return fail(FSPANN_E_ARG, "ref_handover_dev and ref_codes_dev go together (the batch's codes and the buffer its Route wrote)");
     const bool gather = F && !t->ref_cand_dev;
     const int d = c->cfg.dim;
+    c->last_front_encode_mfma = 0;
     int rc;
 
     // ---- Route of the batch being routed; Route parameters of the batch being refined (to finish its PENDING queries)
@@ -187,6 +189,8 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         return FSPANN_OK;
     }
 
+    // which front_kernel build runs (below), if any: the encode role of that launch may be the MFMA one
+    const bool front_launch = front && (plR.lz_entries == 512 || plR.lz_entries == kLzEntriesMax);
     TickHead p{};
     EncodeArgs<float> eaT{};
     RouteParams routeT{}, fixT{};
@@ -198,9 +202,20 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         p.enc_gx = static_cast<int>((t->nq_encode + kTickEncQB - 1) / kTickEncQB);
         p.n_enc = p.enc_gx * gy;
         eaT = EncodeArgs<float>{static_cast<const float*>(t->enc_q_dev), t->nq_encode, d, c->d_alphaT, c->d_r, c->d_omega, c->P_total, m, c->cfg.lambda,
-                                  c->W, c->TD, tdPerBlock, t->enc_codes_dev, nullptr, t->enc_bad_dev, nullptr, nullptr, 0};
+                                  c->W, c->TD, tdPerBlock, t->enc_codes_dev, nullptr, t->enc_bad_dev, nullptr, nullptr, 0, nullptr,
+                                  c->d_alphaT32, c->d_alpha_rows, c->alpha_norm_max};
+        // front launch: the MFMA role (encode_mfma_block) where the stand-alone MFMA path could run (fp32 alpha present, <= 3 code
+        // words, encode mode not forced to exact fp64 by fspann_set_encode_mode(1)), for P <= 256 (one pass of its four waves), lambda <= 16 (its h table keeps 16 bits) and when its h table fits the
+        // Route workgroups' LDS (the launch's LDS stays theirs)
+        p.enc_mfma = (front_launch && c->knob_front_encode == 1 && c->encode_mode != 1 && c->d_alphaT32 && c->d_alpha_rows && c->W <= 3 && c->P_total <= 4 * 64 && c->cfg.lambda <= 16 &&
+                      encode_mfma_block_lds(c->P_total) <= plR.lz_lds_bytes) ? 1 : 0;
+        if (p.enc_mfma) {
+            p.enc_gx = static_cast<int>((t->nq_encode + kFrontEncQ - 1) / kFrontEncQ);
+            p.n_enc = p.enc_gx;
+        }
         c->mfma_last = false;
     } else p.enc_gx = 1;
+    c->last_front_encode_mfma = p.enc_mfma;
     if (R) {
         p.n_route = static_cast<int>(std::min<int64_t>(t->nq_route, 1 << 24));   // one query per workgroup
         routeT = pR;
@@ -233,7 +248,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         FSP_HIP(hipGetLastError());
         return FSPANN_OK;
     };
-    if (front && (plR.lz_entries == 512 || plR.lz_entries == kLzEntriesMax)) {
+    if (front_launch) {
         if (plR.lz_entries == 512) {
             if (c->knob_shape_spec && c->TD == 16 && plR.P == 5 && plR.S == 64 && c->W == 1 && c->rec_words == 4 && (routeT.probe_G == 16 || routeT.probe_G == 0))
                 hipLaunchKernelGGL((front_kernel<512, false, 16, 5>), dim3(static_cast<unsigned>(total)), dim3(kTickThreads), lds, c->stream, p, eaT, routeT);

@@ -45,7 +45,26 @@ struct EncodeArgs {
     const unsigned long long* only_if_over;   // fallback launch behind the MFMA path: runs only when its re-check list overflowed
     unsigned long long over_cap;
     long long* dbg;                            // FSPANN_DEBUG_STAMPS builds: [grid][16] wall_clock64 stamps per workgroup (else unused)
+    const float* alphaT32;                     // encode_mfma_block only: fp32 alphaT [d][P], alpha [P][d] for the re-check, max ||alpha_j||_2
+    const double* alpha_rows;
+    double alpha_norm_max;
 };
+
+// Coding.C, one code word: bit pos = (lambda-1-i)*m + j  <-  bit i of (h_j ^ 0x80000000), h_at(j) = h_j of the word's table
+template <typename HAt>
+__device__ __forceinline__ uint64_t code_word(const int w, const int m, const int lambda, HAt h_at) {
+    uint64_t word = 0;
+    const int pos0 = w * 64;
+    const int pos1 = min(m * lambda, pos0 + 64);
+    for (int pos = pos0; pos < pos1; pos++) {
+        const int plane = pos / m;            // 0 .. lambda-1, MSB plane first
+        const int j = pos - plane * m;
+        const int i = lambda - 1 - plane;
+        const uint32_t hj = static_cast<uint32_t>(h_at(j)) ^ 0x80000000u;
+        word |= static_cast<uint64_t>((hj >> (i & 31)) & 1u) << (pos - pos0);
+    }
+    return word;
+}
 
 // One workgroup (kEncThreads threads): QB query vectors x tdPerBlock tables; block (bx, by) of ceil(nq / QB) x ceil(TD / tdPerBlock).
 // lds = (QB * kEncThreads + QB) int32 of LDS scratch (static in encode_exact_kernel, part of the dynamic LDS in tick_kernel).
@@ -176,7 +195,6 @@ __device__ __forceinline__ void encode_exact_block(const EncodeArgs<TIn>& a, con
     ENC_STAMP(4, 0);                                  // hashes in LDS
 
     // Coding.C: bit pos = (lambda-1-i)*m + j  <-  bit i of (h_j ^ 0x80000000)
-    const int bitsTotal = m * lambda;
     if ((64 % m) == 0) {
         // m divides the wave: the m lanes of one table are adjacent, so plane i of a table's code is an m-bit field of
         // one ballot.  Lane j < W of the group assembles word j from the lambda fields (a field never straddles words).
@@ -204,17 +222,7 @@ __device__ __forceinline__ void encode_exact_block(const EncodeArgs<TIn>& a, con
             const int tdl = rem / W, w = rem - tdl * W;
             const int64_t qi = q0 + qq;
             if (qi >= nq) continue;
-            uint64_t word = 0;
-            const int pos0 = w * 64;
-            const int pos1 = min(bitsTotal, pos0 + 64);
-            for (int pos = pos0; pos < pos1; pos++) {
-                const int plane = pos / m;            // 0 .. lambda-1, MSB plane first
-                const int j = pos - plane * m;
-                const int i = lambda - 1 - plane;
-                const uint32_t hj = static_cast<uint32_t>(Hs[qq * kEncThreads + tdl * m + j]) ^ 0x80000000u;
-                word |= static_cast<uint64_t>((hj >> (i & 31)) & 1u) << (pos - pos0);
-            }
-            codes[(qi * TD + td0 + tdl) * W + w] = word;
+            codes[(qi * TD + td0 + tdl) * W + w] = code_word(w, m, lambda, [&](const int j) { return Hs[qq * kEncThreads + tdl * m + j]; });
         }
     }
     if (bad && by == 0 && tid < QB && q0 + tid < nq) bad[q0 + tid] = badq[tid];
@@ -257,6 +265,24 @@ constexpr int kMfmaKT = 32;        // K tile
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 constexpr int mfma_tile_q(int RT) { return 32 * RT; }
 constexpr int mfma_tile_p(int CT) { return 128 * CT; }
+
+// Guard band of one query row in y units: gamma * ||v||_2 + f32-underflow floor (error bound above; norm2 = ||v||_2^2 in fp64)
+__device__ __forceinline__ double mfma_row_band(const int d, const double alpha_norm_max, const double norm2) {
+    const double gamma = 1.01 * static_cast<double>(d + 4) * 5.9604644775390625e-08 * alpha_norm_max;  // 2^-24
+    return gamma * sqrt(norm2) * 1.0000001 + static_cast<double>(d) * 1.2e-38;
+}
+
+// The interval test of one (query, projection) pair: fl = a bucket guess through the reciprocal iw = 1 / ww (a fp64 divide per pair
+// was as long as a block's whole MFMA phase): ANY guess is fine, because the pair is accepted only when [y - band, y + band] lies
+// strictly inside the guessed bucket's own edges (in y units), with a margin for the fp64 roundings of the edges and of the
+// reference's own (y + r) / omega.  Not accepted: the pair is recomputed with the exact fp64 chain.
+__device__ __forceinline__ bool mfma_pair_safe(const double y, const double band, const double rr, const double ww, const double iw, double* fl_out) {
+    const double fl = floor((y + rr) * iw);
+    *fl_out = fl;
+    const double e_lo = fl * ww - rr, e_hi = (fl + 1.0) * ww - rr;
+    const double mg = 8.9e-16 * (fabs(fl * ww) + fabs(ww) + fabs(rr) + fabs(y));
+    return (y - band > e_lo + mg) && (y + band < e_hi - mg) && (fabs(fl) < 2147483000.0);
+}
 
 // One block = 64 vectors x 256 projections (the V tile is read once per 256 projections: with the old 64 x 64 tile every vector
 // row was fetched P / 64 times).  Epilogue: quantise (floor((y + r) / omega), Coding.java:254-255) AND bit-pack (Coding.C,
@@ -422,9 +448,8 @@ __global__ __launch_bounds__(256, 2) void encode_mfma_kernel(
     __syncthreads();
     if (bad && blockIdx.y == 0 && tid < kMfmaTileQ && q0 + tid < nq) bad[q0 + tid] = badrow[tid];
 
-    // per-row guard band (y units): gamma * ||v||_2 + f32-underflow floor
-    const double gamma = 1.01 * static_cast<double>(d + 4) * 5.9604644775390625e-08 * alpha_norm_max;  // 2^-24
-    if (tid < kMfmaTileQ) rnorm2[tid] = gamma * sqrt(rnorm2[tid]) * 1.0000001 + static_cast<double>(d) * 1.2e-38;
+    // per-row guard band (y units)
+    if (tid < kMfmaTileQ) rnorm2[tid] = mfma_row_band(d, alpha_norm_max, rnorm2[tid]);
     __syncthreads();
     const int half = lane >> 5, c32 = lane & 31;
 #pragma unroll
@@ -432,8 +457,6 @@ __global__ __launch_bounds__(256, 2) void encode_mfma_kernel(
         const int pb = p0 + wave * (32 * CT) + ct * 32;     // first projection of this 32-column tile (wave-uniform)
         const int p = pb + c32;
         const double rr = (p < P) ? r[p] : 0.0, ww = (p < P) ? omega[p] : 1.0;
-        // bucket guess through the reciprocal (a fp64 divide per pair was as long as the block's whole MFMA phase): ANY guess is
-        // fine, because a pair is accepted only when its error interval lies strictly inside the guessed bucket's own edges
         const double iw = 1.0 / ww;
         // the (t,d) tables whose projections fall into this tile: lane (half, seg) packs the bits of table td_first + seg for row-half `half`
         const int td_first = pb / m;
@@ -454,13 +477,9 @@ __global__ __launch_bounds__(256, 2) void encode_mfma_kernel(
                 const int64_t qi = q0 + row;
                 const bool live = (qi < nq) && (p < P);
                 const double y = static_cast<double>(acc[rt][ct][reg]);
-                const double band = rnorm2[row];
-                const double fl = floor((y + rr) * iw);
-                // bucket edges in y units; safe iff [y - band, y + band] lies strictly inside (edge_lo, edge_hi)
-                // with a margin for the fp64 roundings of the edges and of the reference's own (y + r)/omega
-                const double e_lo = fl * ww - rr, e_hi = (fl + 1.0) * ww - rr;
-                const double mg = 8.9e-16 * (fabs(fl * ww) + fabs(ww) + fabs(rr) + fabs(y));
-                const bool safe = live && (y - band > e_lo + mg) && (y + band < e_hi - mg) && (fabs(fl) < 2147483000.0) && !badrow[row];
+                double fl;
+                const bool inside = mfma_pair_safe(y, rnorm2[row], rr, ww, iw, &fl);
+                const bool safe = live && inside && !badrow[row];
                 const int32_t h = java_d2i(fl);
                 if (live && hashes) hashes[qi * P + p] = h;
                 if (live && !safe) {
@@ -572,6 +591,181 @@ __global__ __launch_bounds__(256) void encode_fix_kernel(const TIn* __restrict__
                     atomicOr(cw + (pos >> 6), 1ull << (pos & 63));
                 }
         }
+    }
+}
+
+// =====================================================================================
+// The MFMA encode as ONE workgroup role (front_kernel's encode role, tick.hip.h): kFrontEncQ query rows x ALL P projections.
+// Owning whole tables it writes whole code words — no clearing launch, no atomicOr, no fix list, no fix launch — and it
+// re-checks its own undecided pairs.  Inside the front launch the role's latency hides behind the Route workgroups beside it;
+// what it costs there is CU slot-time, L2 bytes and issue: the exact role reads all of the fp64 alpha (256 KB at config #2's
+// shape) per four rows and runs P x d dependent fp64 adds per row, this one reads the fp32 alpha (128 KB) per sixteen rows
+// and runs MFMAs plus a short epilogue per pair.
+//
+// Tile: sixteen rows = the M side of v_mfma_f32_16x16x4_f32 (A[l & 15][k = l >> 4], B[k = l >> 4][l & 15], D[4 (l >> 4) + r][l & 15]).
+// Four waves, P <= 256 projections: wave w owns [64 w, 64 w + 64), as four 16 x 16 accumulator tiles = 16 VGPRs (the front kernel's
+// Route role sits at 64 VGPRs: a 32-row tile, 32 accumulators per 64 columns, would not fit beside the loads).  Lane column n of
+// tile t is projection wb + 4 n + t, so one 16-byte load of an alphaT32 row feeds a lane's four tiles.  The k order inside the
+// MFMA chain is free (the error bound holds for any order): lane group g takes k = k0 + 4 g + j at step j of a 16-k trip, so
+// the A operand is four consecutive elements of its query row.
+// Re-check: a wave takes its undecided pairs kFrontEncG at a time; the 64 lanes form each pair's products 64 dimensions at a
+// time (coalesced rows of the query and of alpha [P][d], as encode_fix_kernel), and the sums run over the products IN ORDER
+// (acc = acc + v[k] * alpha[k], Coding.java:351) through v_readlane: bit-identical to the exact chain whoever adds.  No list,
+// no capacity: every pair of the tile may be re-checked (degenerate omega: slow, exact).
+// LDS: the h of the tile's pairs, low 16 bits (lambda <= 16: only bits below lambda reach a code word), kFrontEncQ * P * 2 bytes.
+// =====================================================================================
+constexpr int kFrontEncQ = 16;   // query rows per workgroup
+constexpr int kFrontEncG = 4;    // pairs re-checked together per wave
+
+__host__ __device__ constexpr size_t encode_mfma_block_lds(int P) { return static_cast<size_t>(kFrontEncQ) * P * sizeof(uint16_t); }
+
+__device__ __forceinline__ double readlane_f64(const double v, const int l) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<unsigned>(u)), l));
+    const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<unsigned>(u >> 32)), l));
+    return __builtin_bit_cast(double, (static_cast<unsigned long long>(hi) << 32) | lo);
+}
+
+// Workgroup bx (kEncThreads threads) codes rows [16 bx, 16 bx + 16) of the batch.  Needs a.alphaT32, a.alpha_rows, P <= 256, lambda <= 16.
+template <typename TIn>
+__device__ __forceinline__ void encode_mfma_block(const EncodeArgs<TIn>& a, const int bx, uint16_t* Hs /*[kFrontEncQ][P]*/) {
+    const TIn* __restrict__ q = a.q;
+    const int64_t nq = a.nq;
+    const int d = a.d, P = a.P;
+    const float* __restrict__ aT = a.alphaT32;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i16 = lane & 15, g = lane >> 4;
+    const int64_t q0 = static_cast<int64_t>(bx) * kFrontEncQ;
+    const TIn* qrow = q + min(q0 + i16, nq - 1) * d;            // A operand: row i16 (rows past nq: computed, never stored)
+
+    const int wb = wave * 64;                                   // this wave's 64 projections (P <= 256: one pass)
+    const int pc = wb + 4 * i16;                                // this lane's four columns: pc + t for tile t
+    fsp_f4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = fsp_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    double nrm = 0.0;                                           // this lane's share of ||v_i16||^2
+    bool nonfinite = false;
+    // One trip = 16 k.  A trip's loads (four query elements, four 16-byte pieces of alphaT32 per lane) are all requested together,
+    // from clamped addresses with no condition, before any of them is used: one round trip to memory per trip, d / 16 per workgroup.
+    // (A load behind a branch, or one whose value is masked right away, costs a round trip of its own: d / 4.  A trip prefetched one
+    // ahead does not fit beside the accumulators in the front kernel's 64 registers.)  Nothing of alpha is masked: past d the query
+    // element is zero, past P the columns are never read.
+    auto k_loop = [&](auto vec_c) {
+        constexpr bool kVec = decltype(vec_c)::value;           // P % 4 == 0: a 16-byte piece of an alphaT32 row lies wholly inside P
+        for (int k0 = 0; k0 < d; k0 += 16) {
+            const int kb = k0 + 4 * g;
+            TIn xa[4];
+            fsp_f4 bv[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) xa[j] = qrow[min(kb + j, d - 1)];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float* src = aT + static_cast<int64_t>(min(kb + j, d - 1)) * P;
+                if constexpr (kVec) {
+                    bv[j] = *reinterpret_cast<const fsp_f4*>(src + min(pc, P - 4));
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; t++) bv[j][t] = src[min(pc + t, P - 1)];
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);                  // (keeps the loads ahead of their uses)
+            float av[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const double v = (kb + j < d) ? static_cast<double>(xa[j]) : 0.0;
+                av[j] = static_cast<float>(v);
+                nrm += v * v;
+                nonfinite |= !(fabs(v) <= 1.79769313486231570815e+308);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j], bv[j][t], acc[t], 0, 0, 0);
+        }
+    };
+    if ((P & 3) == 0) k_loop(std::true_type{});
+    else k_loop(std::false_type{});
+    // row i16's norm: the four lane groups hold disjoint k; NaN / Inf rows (Coding.java:356-361) are never accepted, and flagged
+    nrm += __shfl_xor(nrm, 16);
+    nrm += __shfl_xor(nrm, 32);
+    const unsigned long long nb = __ballot(nonfinite);
+    const unsigned rowbad = static_cast<unsigned>((nb | (nb >> 16) | (nb >> 32) | (nb >> 48)) & 0xFFFFull);
+    if (a.bad && wave == 0 && lane < kFrontEncQ && q0 + lane < nq) a.bad[q0 + lane] = (rowbad >> lane) & 1u;
+
+    // epilogue: h of every pair into LDS; the pairs the interval test cannot accept are marked (bit 4 t + r)
+    const double my_band = mfma_row_band(d, a.alpha_norm_max, nrm);
+    double band[4];                                         // guard bands of rows 4 g + r
+#pragma unroll
+    for (int r = 0; r < 4; r++) band[r] = __shfl(my_band, 4 * g + r);
+    unsigned undecided = 0;
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        const int p = pc + t;
+        const bool pin = p < P;
+        const double rr = pin ? a.r[p] : 0.0, ww = pin ? a.omega[p] : 1.0;
+        const double iw = 1.0 / ww;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int row = 4 * g + r;
+            double fl;
+            const bool inside = mfma_pair_safe(static_cast<double>(acc[t][r]), band[r], rr, ww, iw, &fl);
+            if (pin) Hs[row * P + p] = static_cast<uint16_t>(java_d2i(fl));
+            if (pin && q0 + row < nq && !(inside && !((rowbad >> row) & 1u))) undecided |= 1u << (4 * t + r);
+        }
+    }
+
+    // re-check: the exact fp64 chain for the undecided pairs of this wave, kFrontEncG at a time (wave-uniform loops)
+    for (int s = 0; s < 16; s++) {
+        unsigned long long msk = __ballot((undecided >> s) & 1u);
+        const int t = s >> 2, r = s & 3;
+        while (msk) {
+            int rows[kFrontEncG], ps[kFrontEncG];
+            int cnt = 0;
+#pragma unroll
+            for (int e = 0; e < kFrontEncG; e++) {
+                const int src = msk ? __builtin_ctzll(msk) : 0;   // (a slot past the last pair repeats pair 0's rows: computed, never used)
+                if (msk) { msk &= msk - 1; cnt++; }
+                rows[e] = (e < cnt) ? 4 * (src >> 4) + r : rows[0];
+                ps[e] = (e < cnt) ? wb + 4 * (src & 15) + t : ps[0];
+            }
+            double sum[kFrontEncG];
+#pragma unroll
+            for (int e = 0; e < kFrontEncG; e++) sum[e] = 0.0;
+            for (int k0 = 0; k0 < d; k0 += 64) {
+                const int k = min(k0 + lane, d - 1);               // (clamped: a product past d is never added)
+                double pr[kFrontEncG];
+#pragma unroll
+                for (int e = 0; e < kFrontEncG; e++)
+                    pr[e] = static_cast<double>(q[(q0 + rows[e]) * d + k]) * a.alpha_rows[static_cast<int64_t>(ps[e]) * d + k];
+                const int kn = min(64, d - k0);
+#pragma unroll 1
+                for (int j = 0; j < kn; j++)                            // (not unrolled: every pending readlane holds two SGPRs)
+#pragma unroll
+                    for (int e = 0; e < kFrontEncG; e++) sum[e] = sum[e] + readlane_f64(pr[e], j);   // Coding.java:351, in order
+            }
+#pragma unroll
+            for (int e = 0; e < kFrontEncG; e++) {
+                if (e < cnt) {
+                    const double y = sum[e] + a.r[ps[e]];                              // Coding.java:254
+                    const int32_t h = java_d2i(floor(y / a.omega[ps[e]]));             // Coding.java:255
+                    if (lane == 0) Hs[rows[e] * P + ps[e]] = static_cast<uint16_t>(h);
+                }
+            }
+        }
+    }
+    __syncthreads();                                            // every h of the tile is in LDS
+
+    // Coding.C: whole code words of the tile's rows
+    const int m = a.m, lambda = a.lambda, W = a.W, TD = a.TD;
+    const int nwords = kFrontEncQ * TD * W;
+    for (int wi = tid; wi < nwords; wi += kEncThreads) {
+        const int qq = wi / (TD * W);
+        const int rem = wi - qq * (TD * W);
+        const int td = rem / W, w = rem - td * W;
+        const int64_t qi = q0 + qq;
+        if (qi >= nq) continue;
+        const uint16_t* hrow = Hs + qq * P + td * m;
+        a.codes[(qi * TD + td) * W + w] = code_word(w, m, lambda, [&](const int j) { return static_cast<int32_t>(hrow[j]); });
     }
 }
 

@@ -100,6 +100,7 @@ struct fspann_ctx {
     int knob_gpu_cut = 1;            // FSPANN_GPU_CUT=0: fspann_build_index cuts the partitions on host threads (std::sort) instead of the GPU radix sort
     int knob_wave_sort = 1;          // FSPANN_ROUTE_WAVE_SORT=0: long lists' groups are sorted by the whole workgroup one by one (dev A/B)
     int knob_tick_fuse = 1;          // FSPANN_TICK_FUSE=0: fspann_tick_dev always uses the stand-alone kernels
+    int knob_front_encode = 1;       // FSPANN_FRONT_ENCODE: encode role of the front launch, mfma (1, default) or exact (0: encode_exact_block; dev A/B)
     int knob_tick_front = 100;       // FSPANN_TICK_FRONT: percent of a tick's Route workgroups that head the grid
     int knob_bincheck = -1;          // FSPANN_ROUTE_BINCHECK: the bounded select's exact treeify check (-1: on for opaque ids, off for decimal ordinals; 0 / 1 force)
     bool knob_shape_spec = true;     // FSPANN_ROUTE_SHAPE_SPEC=0: the bounded select's build with run-time tables x probes also for 16 x 5 (dev A/B)
@@ -112,6 +113,7 @@ struct fspann_ctx {
     bool knob_refine_run = true;     // FSPANN_REFINE_RUN=0: long lists keep one partial top-k list per 256-row chunk (dev A/B)
     bool knob_slice = true;          // FSPANN_ROUTE_SLICE=0: the full select's global-arena mode builds its hash in the arena (dev A/B)
     int last_tick_fused = 0;
+    int last_front_encode_mfma = 0;  // the last fspann_tick_dev coded its batch with front_kernel's MFMA role (encode_mfma_block)
 
     // GFunctions: alphaT[dim][P_total] fp64 (transposed for coalescing), r/omega[P_total]
     double* d_alphaT = nullptr;

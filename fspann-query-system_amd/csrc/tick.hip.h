@@ -34,6 +34,7 @@ struct TickHead {
     int enc_gx;
     int route_front;                // the first route_front workgroups of the launch are route: the long jobs start first
     int has_fix;                    // `fix` is valid: PENDING queries of the batch being refined are redone before their scan
+    int enc_mfma;                   // front_kernel: the encode role is encode_mfma_block (kFrontEncQ rows per workgroup), else encode_exact_block
     int64_t nq_refine;              // queries of the batch being refined (n_refine workgroups share them)
     long long* dbg;                 // FSPANN_DEBUG_STAMPS builds: [grid][4] = {role, index, start, end} (wall_clock64), else unused
 };
@@ -108,8 +109,10 @@ __global__ __launch_bounds__(kTickThreads, 4) void tick_kernel(const TickHead h,
 
 // encode(batch t+1) + Route(batch t) as one launch, nothing else: the two stages in front of the host's decrypt loop.  Without a
 // Refine role the launch needs only the bounded select's LDS and registers — in its 512-entry class at 16 x 5 19.7 KB and 64 registers,
-// eight workgroups per CU — and the encode workgroups (one wave per SIMD, bound by the issue rate of a lone wave) fill slots beside
-// the Route workgroups instead of holding the chip for a launch of their own.
+// eight workgroups per CU — and the encode workgroups fill slots beside the Route workgroups instead of holding the chip for a launch
+// of their own.  Every encode workgroup holds a Route slot while it runs, so the encode role is the MFMA one where it applies
+// (encode_mfma_block: a quarter of the workgroups, each as long as an exact one or longer but with 16 rows instead of 4, so the
+// role's slot-time is less than half; api_tick.hip.h picks it).
 template <int kEnt, bool kChk, int kTD = 0, int kP = 0>
 __global__ __launch_bounds__(kTickThreads, (kEnt <= 512 ? (kTD > 0 ? 8 : 6) : 4)) void front_kernel(const TickHead h, const EncodeArgs<float> enc, const RouteParams route) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -118,8 +121,10 @@ __global__ __launch_bounds__(kTickThreads, (kEnt <= 512 ? (kTD > 0 ? 8 : 6) : 4)
     // residency census (tools/route_residency.py): [grid][4] = {role, where (dbg_hw_where), start, end}
     if (h.dbg && threadIdx.x == 0) { h.dbg[b * 4 + 0] = (b < h.n_enc) ? kTickEncode : kTickRoute; h.dbg[b * 4 + 1] = dbg_hw_where(); h.dbg[b * 4 + 2] = wall_clock64(); }
 #endif
-    if (b < h.n_enc) encode_exact_block<float, kTickEncQB>(enc, b % h.enc_gx, b / h.enc_gx, reinterpret_cast<int32_t*>(smem));
-    else route_lazy_run<kLzThreads, kEnt, kChk, kTD, kP>(route, smem, b - h.n_enc, h.n_route, b - h.n_enc);
+    if (b < h.n_enc) {
+        if (h.enc_mfma) encode_mfma_block<float>(enc, b, reinterpret_cast<uint16_t*>(smem));
+        else encode_exact_block<float, kTickEncQB>(enc, b % h.enc_gx, b / h.enc_gx, reinterpret_cast<int32_t*>(smem));
+    } else route_lazy_run<kLzThreads, kEnt, kChk, kTD, kP>(route, smem, b - h.n_enc, h.n_route, b - h.n_enc);
 #ifdef FSPANN_DEBUG_STAMPS
     __syncthreads();
     if (h.dbg && threadIdx.x == 0) h.dbg[b * 4 + 3] = wall_clock64();

@@ -449,6 +449,10 @@ class FspannContext:
     def last_tick_fused(self) -> bool:
         return bool(self.L.fspann_last_tick_fused(self._h))
 
+    def last_front_encode_mfma(self) -> bool:
+        """True if the last tick_dev coded its encode batch with the front launch's MFMA role (encode_mfma_block)."""
+        return bool(self.L.fspann_last_front_encode_mfma(self._h))
+
     def refine_timing_begin(self, max_launches, every=1):
         N.check(self.L.fspann_refine_timing_begin(self._h, int(max_launches), int(every)))
 

@@ -325,6 +325,8 @@ size_t fspann_route_handover_bytes(fspann_ctx* ctx, int64_t nq, int probe_overri
 int fspann_tick_dev(fspann_ctx* ctx, const fspann_tick* t);
 /* 1 if the last fspann_tick_dev ran as one shared kernel, 0 if it fell back to the stand-alone kernels. */
 int fspann_last_tick_fused(fspann_ctx* ctx);
+/* 1 if the last fspann_tick_dev coded its encode batch with the front launch's MFMA role, 0 otherwise (exact role, no front launch). */
+int fspann_last_front_encode_mfma(fspann_ctx* ctx);
 
 /* ---- exact ground truth + evaluation metrics --------------------------------------------------------
  * GroundtruthPrecompute.run (api/.../GroundtruthPrecompute.java:218-272): per query the k base vectors with the smallest

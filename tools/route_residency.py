@@ -129,6 +129,22 @@ else:
     res = census(where_key(route[:, 1]), route[:, 2].astype(np.float64), route[:, 3].astype(np.float64))
     res.update(mode="front", launches=args.record * len(ctxs), contexts=len(ctxs),
                all_roles=census(where_key(rows[:, 1]), rows[:, 2].astype(np.float64), rows[:, 3].astype(np.float64)))
+    # slot-time of the two roles per front launch (sum of workgroup durations) and how long the encode workgroups run beside Route
+    us = 0.01                                               # wall_clock64: 100 MHz
+    per = []
+    for st in (s_ for per_ctx in stamps for s_ in per_ctx):
+        r_ = st.cpu().numpy()
+        r_ = r_[r_[:, 2] > 0]
+        enc, rt = r_[r_[:, 0] == 0], r_[r_[:, 0] == 1]
+        if len(enc) == 0 or len(rt) == 0:
+            continue
+        e0, e1, r0, r1 = enc[:, 2].min(), enc[:, 3].max(), rt[:, 2].min(), rt[:, 3].max()
+        per.append(dict(encode_wgs=len(enc), encode_slot_us=float((enc[:, 3] - enc[:, 2]).sum()) * us,
+                        encode_wg_mean_us=float((enc[:, 3] - enc[:, 2]).mean()) * us, route_slot_us=float((rt[:, 3] - rt[:, 2]).sum()) * us,
+                        encode_span_us=float(e1 - e0) * us, launch_span_us=float(max(e1, r1) - min(e0, r0)) * us,
+                        encode_route_overlap_us=float(max(0, min(e1, r1) - max(e0, r0))) * us))
+    if per:
+        res["per_launch_mean"] = {k: round(float(np.mean([x[k] for x in per])), 2) for k in per[0]}
 print(json.dumps(res))
 if args.json:
     with open(args.json, "w") as f:

@@ -14,10 +14,13 @@ GPU (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env).  One "step" = one pass o
 loadPointIfActive + AES-GCM decrypt loop hands over in production — are already resident in HBM when the timed region
 starts (`--candidates dense`; packed once, before the timed region, for each of the `--query-batches` distinct batches,
 so consecutive steps read DIFFERENT blocks: 32 x 134 MB = 4.3 GB cycled, far beyond the 256 MiB Infinity Cache).
-Beside it (extra objects, never `value`): the trusted-HBM variant where Refine reads plaintext rows of a resident store
-by id (`variants.store`), the gather-inclusive variant, the single-stream and single-kernel pipelines, the refine scan on an
-8 M-row store and at config #4's shape (`roofline.hbm_proof`, `roofline.cfg4_shape`), recall@10 / distance ratio vs
-exact kNN, and the CPU oracle on this box's host cores (`cpu_baseline`).  Rank 0 prints ONE JSON line.
+A plain run does only what `value` needs: set up, warm up, time the steps, write `--dump-outputs`, print the line.
+With `--full`, beside it (extra objects, never `value`): the stage breakdown and roofline readings, the trusted-HBM variant
+where Refine reads plaintext rows of a resident store by id (`variants.store`), the gather-inclusive variant, the
+single-stream and single-kernel pipelines, the refine scan on an 8 M-row store and at config #4's shape
+(`roofline.hbm_proof`, `roofline.cfg4_shape`), recall@10 / distance ratio vs exact kNN, the timed steps checked against
+the plain path and the CPU oracle, the CPU oracle on this box's host cores (`cpu_baseline`) and the shipped profiles as
+child runs (`extra`).  Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -153,6 +156,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside `value` (stage breakdown, encode and roofline readings, other pipelines "
+                         "and candidate variants, operator surface, end to end, recall, checks against the plain path and the CPU "
+                         "oracle, CPU baseline, shipped profiles; --no-extras / --no-cpu-baseline / --no-shipped trim it).  Off: set up, "
+                         "warm up, time the steps, write --dump-outputs, print the line")
     ap.add_argument("--workload", default="sift1m_T16_b32_B256_Q1024", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="queries per GPU per step (default: workload's)")
     ap.add_argument("--data", default="gaussian", help="gaussian | clustered | path to a .fvecs base file")
@@ -288,7 +296,8 @@ def main():
         Q = Qw
         q_lo, q_hi = 0, Q
     q_live = q_hi - q_lo
-    extras = (world == 1) and not args.no_extras and not shipped     # the extra passes are sized for the headline workload
+    full = args.full
+    extras = full and (world == 1) and not args.no_extras and not shipped     # the extra passes are sized for the headline workload
     dense = args.candidates == "dense"
 
     # ---------------- data + frozen index ----------------------------------------------------------------------------
@@ -672,11 +681,11 @@ def main():
             topk_ids=ltk.ids[lslot * Q:(lslot + 1) * Q].cpu().numpy(), topk_dist=ltk.dist[lslot * Q:(lslot + 1) * Q].cpu().numpy(),
             topk_count=lb["out_cnt"].cpu().numpy(), scored=lb["scored"].cpu().numpy()))
         log("[bench] last timed step's outputs written to %s: %s" % (args.dump_outputs, ", ".join(n_ + ".npy" for n_ in names)))
-    # ---------------- what was timed is what is checked: the LAST step each context ran inside the timed region (front_kernel +
-    # the scan that finishes PENDING queries, on the clones' own streams) against the plain three-launch path on context 0 for the
+    # ---------------- (--full) what was timed is what is checked: the LAST step each context ran inside the timed region (front_kernel
+    # + the scan that finishes PENDING queries, on the clones' own streams) against the plain three-launch path on context 0 for the
     # same batch here, and against the CPU oracle in the cpu_baseline leg ------------------------------------------------------
     timed_check = None
-    if args.pipeline == "front" and not use_tick and bufs[0]["last_front"] is not None:
+    if full and args.pipeline == "front" and not use_tick and bufs[0]["last_front"] is not None:
         snaps = []
         for si_, b_ in enumerate(bufs[:nctx]):
             if b_["last_front"] is None:
@@ -712,7 +721,7 @@ def main():
     region_n = sum(x for x, _ in rt)
     region_ms = sum(t for _, t in rt)
     tail_ms = []
-    if not use_tick and args.solo_tail > 0 and not shipped:
+    if full and not use_tick and args.solo_tail > 0 and not shipped:
         tail_ms = solo_readings(mode, args.solo_tail, nact=nctx, front=args.pipeline == "front")
     ref_launches = region_n + len(tail_ms)
     ref_ms = (region_ms + sum(tail_ms)) / max(1, ref_launches)     # kernel-attached HIP events, on the context's stream
@@ -726,22 +735,24 @@ def main():
     q_job = Qw if args.scaling == "strong" else world * Q
     qps = q_job * args.steps / elapsed
 
-    # ---------------- stage breakdown: a separate, untimed pass with an event after every stage ---------------------------
-    nprof = min(args.steps, 20)
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(nprof)]
-    barrier()
-    for i in range(nprof):
-        step(mode, evs[i])
-    barrier()
-    stage_ms = np.array([[evs[i][j].elapsed_time(evs[i][j + 1]) for j in range(4)] for i in range(nprof)])
-    st_mean = stage_ms.mean(axis=0)
+    # ---------------- (--full) stage breakdown: a separate, untimed pass with an event after every stage ---------------------
+    st_mean = None
+    if full:
+        nprof = min(args.steps, 20)
+        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(5)] for _ in range(nprof)]
+        barrier()
+        for i in range(nprof):
+            step(mode, evs[i])
+        barrier()
+        stage_ms = np.array([[evs[i][j].elapsed_time(evs[i][j + 1]) for j in range(4)] for i in range(nprof)])
+        st_mean = stage_ms.mean(axis=0)
 
-    # ---------------- encode (north_star: "MFMA utilisation" beside the HBM figure) -------------------------------------------
+    # ---------------- (--full) encode (north_star: "MFMA utilisation" beside the HBM figure) ----------------------------------
     # query side: the exact fp64 VALU kernel (sequential chain per lane = Java's dot, bit-exact by construction); index side
     # (Setup, n >= 4096 rows per call): MFMA fp32 GEMM pre-filter with the quantise + bit-pack fused into its epilogue + exact
     # re-check of the pairs it cannot decide.  flops = 2 * rows * d * (T*D*m).
     encode_stage = None
-    if rank == 0:
+    if rank == 0 and full:
         FP64_VALU_PEAK, F32_MFMA_PEAK = 78.6, 157.3      # TFLOP/s: MI355X fp64 vector (half the fp32 vector rate), fp32 matrix (MI355X_MICROARCH.md)
         fl_q = 2.0 * Q * d * TD * m
         enc_ms = float(st_mean[0])
@@ -853,7 +864,7 @@ def main():
     # copied out of the base array where the JVM would decrypt: that copy is reported, not counted), next to the batched mirror
     # searchBatch (one fspann_route + one fspann_refine for all queries of a batch).
     operator_surface = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and full and not args.no_extras:
         nsamp = 256 if B <= 1024 else 64
         qs_ = Qall[0][:nsamp].astype(np.float64)
         lat = {k_: [] for k_ in ("encode", "route", "host_rows", "refine", "refine_pageable")}
@@ -986,204 +997,208 @@ def main():
         except Exception as e:
             end_to_end["per_open"] = dict(error=str(e)[:200])
 
-    # one more (untimed) step of batch 0 on context 0: its results are what recall and the CPU baseline are checked on
     flagged_in_timed_runs = sum(int(c_.unmodelled_queries()) for c_ in ctxs)     # (read + reset: the timed steps leave such queries empty)
-    for b_ in bufs:
-        b_["nsteps"] = 0
-    step_no[0] = 0
-    barrier()
-    if use_tick:       # batch 0 is refined by tick 0 (its encode and Route were done by tick_prime)
-        tick_prime()
-        tick(mode)
-    else:
-        step(mode, batch=0)   # (active[0] == 1: context 0)
-    flush(1)
-    barrier()
-    # Queries whose bestScore map treeifies a bin (count -1 after Route; ~0.3 % at the shipped profiles, ~2e-9 at the headline
-    # workload) are finished by the library's host model — outside the timed region, which leaves them empty: reported below.
     treeified_batch0 = 0
-    if not use_tick and ctx.unmodelled_queries(reset=False) != 0:
-        b0_ = bufs[0]
-        treeified_batch0 = ctx.route_resolve_dev(Q, b0_["codes"].data_ptr(), probe_passes[-1], B, B, b0_["sel_ids"].data_ptr(), 0, b0_["sel_cnt"].data_ptr())
-        tk0 = b0_["topk"][0]
-        if mode == "store":
-            ctx.refine_store_dev(Q, q_all[0].data_ptr(), F32, B, b0_["sel_ids"].data_ptr(), b0_["sel_cnt"].data_ptr(), k, tk0.ids.data_ptr(), tk0.dist.data_ptr(),
-                                 b0_["out_cnt"].data_ptr(), b0_["scored"].data_ptr())
+    out_ids = out_dist = None
+    if full:
+        # one more (untimed) step of batch 0 on context 0: its results are what recall and the CPU baseline are checked on
+        for b_ in bufs:
+            b_["nsteps"] = 0
+        step_no[0] = 0
+        barrier()
+        if use_tick:       # batch 0 is refined by tick 0 (its encode and Route were done by tick_prime)
+            tick_prime()
+            tick(mode)
         else:
-            cp0 = b0_["cand"].data_ptr() if mode == "gather" else cand_all[0].data_ptr()
-            if mode == "gather":
-                ctx.store_gather_dev(Q, b0_["sel_ids"].data_ptr(), b0_["sel_cnt"].data_ptr(), B, cp0)
-            ctx.refine_dev(Q, q_all[0].data_ptr(), F32, cp0, F32, B, b0_["sel_ids"].data_ptr(), b0_["sel_cnt"].data_ptr(), k, tk0.ids.data_ptr(),
-                           tk0.dist.data_ptr(), b0_["out_cnt"].data_ptr(), b0_["scored"].data_ptr())
-        ctx.sync()
-    out_ids, out_dist = bufs[0]["topk"][0].ids[:Q], bufs[0]["topk"][0].dist[:Q]      # first batch of the first group
-    got_ids, got_dist = out_ids.cpu().numpy(), out_dist.cpu().numpy()
-    if ctx.unmodelled_queries() != 0:
-        raise SystemExit("bench: a query stayed unmodelled (equal hashCodes of non-decimal ids inside a treeified bin)")
-    if end_to_end is not None:      # same batch through the decrypting pipeline: same answer
-        end_to_end["matches_kernel_path"] = bool(np.array_equal(e2e_first["ids"], got_ids) and np.array_equal(e2e_first["dist"], got_dist))
-        if not end_to_end["matches_kernel_path"]:
-            raise SystemExit("bench: the end-to-end pipeline and the kernel path disagree on batch 0")
+            step(mode, batch=0)   # (active[0] == 1: context 0)
+        flush(1)
+        barrier()
+        # Queries whose bestScore map treeifies a bin (count -1 after Route; ~0.3 % at the shipped profiles, ~2e-9 at the headline
+        # workload) are finished by the library's host model — outside the timed region, which leaves them empty: reported below.
+        if not use_tick and ctx.unmodelled_queries(reset=False) != 0:
+            b0_ = bufs[0]
+            treeified_batch0 = ctx.route_resolve_dev(Q, b0_["codes"].data_ptr(), probe_passes[-1], B, B, b0_["sel_ids"].data_ptr(), 0, b0_["sel_cnt"].data_ptr())
+            tk0 = b0_["topk"][0]
+            if mode == "store":
+                ctx.refine_store_dev(Q, q_all[0].data_ptr(), F32, B, b0_["sel_ids"].data_ptr(), b0_["sel_cnt"].data_ptr(), k, tk0.ids.data_ptr(), tk0.dist.data_ptr(),
+                                     b0_["out_cnt"].data_ptr(), b0_["scored"].data_ptr())
+            else:
+                cp0 = b0_["cand"].data_ptr() if mode == "gather" else cand_all[0].data_ptr()
+                if mode == "gather":
+                    ctx.store_gather_dev(Q, b0_["sel_ids"].data_ptr(), b0_["sel_cnt"].data_ptr(), B, cp0)
+                ctx.refine_dev(Q, q_all[0].data_ptr(), F32, cp0, F32, B, b0_["sel_ids"].data_ptr(), b0_["sel_cnt"].data_ptr(), k, tk0.ids.data_ptr(),
+                               tk0.dist.data_ptr(), b0_["out_cnt"].data_ptr(), b0_["scored"].data_ptr())
+            ctx.sync()
+        out_ids, out_dist = bufs[0]["topk"][0].ids[:Q], bufs[0]["topk"][0].dist[:Q]      # first batch of the first group
+        got_ids, got_dist = out_ids.cpu().numpy(), out_dist.cpu().numpy()
+        if ctx.unmodelled_queries() != 0:
+            raise SystemExit("bench: a query stayed unmodelled (equal hashCodes of non-decimal ids inside a treeified bin)")
+        if end_to_end is not None:      # same batch through the decrypting pipeline: same answer
+            end_to_end["matches_kernel_path"] = bool(np.array_equal(e2e_first["ids"], got_ids) and np.array_equal(e2e_first["dist"], got_dist))
+            if not end_to_end["matches_kernel_path"]:
+                raise SystemExit("bench: the end-to-end pipeline and the kernel path disagree on batch 0")
 
-    # ---------------- roofline of the refinement scan (north_star's HBM-bound kernel) ---------------------------------------
-    # algorithmic bytes per launch: Q * (B*d*4 + d*4 + k*8)
-    ref_bytes = Q * (B * d * 4 + d * 4 + k * 8)
-    achieved = ref_bytes / (ref_ms * 1e-3) / 1e9 if ref_ms > 0 else 0.0      # (0: no dispatch carried events — experiments only)
-    traffic, traffic_src = None, None
-    tpath = os.path.join(ROOT, "profiles", "refine_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath)).get(mode, {})
-            if tj.get("workload") == args.workload and tj.get("Q") == Q:
-                traffic, traffic_src = tj.get("hbm_bytes_per_launch"), tj.get("source")
-        except Exception:
-            traffic = None
-    if extras:
-        peak_measured = round(ctx.hbm_read_peak(1 << 32, 5), 1)      # pure 16-byte-load kernel over 4 GiB, best of 5
-        # the same pure-load kernel when one launch reads only as many bytes as one refinement scan does (cold windows of 4 GiB)
-        peak_launch_sized = round(ctx.hbm_read_window(1 << 32, (Q * (B * d * 4 + d * 4 + k * 8) + 15) // 16 * 16, 24), 1)
-        # (a) the same scan reading 1024 x 256 random rows of an 8 M x 128 (4.1 GB) store: 134 MB per launch out of 4.1 GB
-        NS = 8_000_000
-        big = torch.randn((NS, d), dtype=torch.float32, device=dev)
-        rid = torch.randint(0, NS, (8, Q, B), dtype=torch.int32, device=dev)
-        cnt = torch.full((Q,), B, dtype=torch.int32, device=dev)
-        b0 = bufs[0]
-        torch.cuda.synchronize()
-        with pkg.FspannContext(cfg, local_rank) as cp:         # Refine needs no index: a bare context over the big store
-            cp.store_attach_dev(NS, big.data_ptr(), F32)
-
-            def rs(i):
-                cp.refine_store_dev(Q, q_all[0].data_ptr(), F32, B, rid[i % 8].data_ptr(), cnt.data_ptr(), k, b0["topk"][1].ids.data_ptr(),
-                                    b0["topk"][1].dist.data_ptr(), b0["out_cnt"].data_ptr(), b0["scored"].data_ptr())
-            for i in range(4):
-                rs(i)
-            cp.sync()
-            cp.refine_timing_begin(40, 1)
-            for i in range(40):
-                rs(i)
-            nl, tms = cp.refine_timing_end()
-        del big, rid
-        hp_ms = tms / max(1, nl)
-        hbm_proof = dict(kernel="refine_stream_kernel<float,float,32,true>", store_rows=NS, store_bytes=NS * d * 4, launches=nl,
-                         avg_launch_ms=round(hp_ms, 5), achieved=round(ref_bytes / (hp_ms * 1e-3) / 1e9, 1),
-                         frac=round(ref_bytes / (hp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         note="1024 x 256 uniformly random rows of a 4.1 GB store per launch, 8 id sets cycled: at most 6 % of a launch's rows "
-                              "can sit in the 256 MiB Infinity Cache")
-        # (b) BASELINE config #4's refine shape: d = 768, B = 1024 -> four 256-row chunks per query + refine_merge_kernel
-        d4, B4 = 768, 1024
-        cfg4 = pkg.PaperRuntimeConfig(tables=1, divisions=1, m=8, lambda_=2, dim=d4, refinement_limit=B4)
-        with pkg.FspannContext(cfg4, local_rank) as c4:
-            cand4 = torch.randn((2, Q, B4, d4), dtype=torch.float32, device=dev)          # 2 x 3.2 GB
-            q4 = torch.randn((Q, d4), dtype=torch.float32, device=dev)
-            ids4 = torch.arange(Q * B4, dtype=torch.int32, device=dev).view(Q, B4)
-            cnt4 = torch.full((Q,), B4, dtype=torch.int32, device=dev)
-            oi4 = torch.zeros((Q, k), dtype=torch.int32, device=dev)
-            od4 = torch.zeros((Q, k), dtype=torch.float64, device=dev)
-            oc4 = torch.zeros(Q, dtype=torch.int32, device=dev)
+    # ---------------- (--full) roofline of the refinement scan (north_star's HBM-bound kernel) --------------------------------
+    roofline = route_info = None
+    if full:
+        # algorithmic bytes per launch: Q * (B*d*4 + d*4 + k*8)
+        ref_bytes = Q * (B * d * 4 + d * 4 + k * 8)
+        achieved = ref_bytes / (ref_ms * 1e-3) / 1e9 if ref_ms > 0 else 0.0      # (0: no dispatch carried events — experiments only)
+        traffic, traffic_src = None, None
+        tpath = os.path.join(ROOT, "profiles", "refine_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath)).get(mode, {})
+                if tj.get("workload") == args.workload and tj.get("Q") == Q:
+                    traffic, traffic_src = tj.get("hbm_bytes_per_launch"), tj.get("source")
+            except Exception:
+                traffic = None
+        if extras:
+            peak_measured = round(ctx.hbm_read_peak(1 << 32, 5), 1)      # pure 16-byte-load kernel over 4 GiB, best of 5
+            # the same pure-load kernel when one launch reads only as many bytes as one refinement scan does (cold windows of 4 GiB)
+            peak_launch_sized = round(ctx.hbm_read_window(1 << 32, (Q * (B * d * 4 + d * 4 + k * 8) + 15) // 16 * 16, 24), 1)
+            # (a) the same scan reading 1024 x 256 random rows of an 8 M x 128 (4.1 GB) store: 134 MB per launch out of 4.1 GB
+            NS = 8_000_000
+            big = torch.randn((NS, d), dtype=torch.float32, device=dev)
+            rid = torch.randint(0, NS, (8, Q, B), dtype=torch.int32, device=dev)
+            cnt = torch.full((Q,), B, dtype=torch.int32, device=dev)
+            b0 = bufs[0]
             torch.cuda.synchronize()
-            s4 = torch.cuda.ExternalStream(c4.stream, device=dev)
+            with pkg.FspannContext(cfg, local_rank) as cp:         # Refine needs no index: a bare context over the big store
+                cp.store_attach_dev(NS, big.data_ptr(), F32)
 
-            def r4(i):
-                c4.refine_dev(Q, q4.data_ptr(), F32, cand4[i & 1].data_ptr(), F32, B4, ids4.data_ptr(), cnt4.data_ptr(), k, oi4.data_ptr(),
-                              od4.data_ptr(), oc4.data_ptr(), 0)
-            for i in range(2):
-                r4(i)
-            c4.sync()
-            c4.refine_timing_begin(12, 1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s4)
-            for i in range(12):
-                r4(i)
-            e1.record(s4)
-            nl4, tms4 = c4.refine_timing_end()
-            bytes4 = Q * (B4 * d4 * 4 + d4 * 4 + k * 8)
-            scan_ms, call_ms = tms4 / max(1, nl4), e0.elapsed_time(e1) / 12
-            cfg4_shape = dict(kernel="refine_stream_kernel<float,float,32,false> over 4 chunks per query + refine_merge_kernel", Q=Q, B=B4, dim=d4,
-                              algorithmic_bytes_per_launch=bytes4, scan_launch_ms=round(scan_ms, 4), scan_plus_merge_ms=round(call_ms, 4),
-                              achieved=round(bytes4 / (scan_ms * 1e-3) / 1e9, 1), frac=round(bytes4 / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                              note="two 3.2 GB blocks alternate; events attached to the scan kernel; scan_plus_merge_ms = whole fspann_refine_dev call")
-            del cand4
-        # (c) fp64 rows, fp64 query — what the JVM hands over (double[] from decryptFromPoint): refine_stream_kernel<double,double,16,false>,
-        # algorithmic bytes = Q * (B*d*8 + d*8 + k*8); 8 distinct blocks are cycled (2.1 GB at config #2)
-        NB64 = 8
-        cand64 = torch.randn((NB64, Q, B, d), dtype=torch.float64, device=dev)
-        q64 = q_all[0].double()
-        ids64 = torch.arange(Q * B, dtype=torch.int32, device=dev).view(Q, B)
-        cnt64 = torch.full((Q,), B, dtype=torch.int32, device=dev)
-        b0 = bufs[0]
-        torch.cuda.synchronize()
+                def rs(i):
+                    cp.refine_store_dev(Q, q_all[0].data_ptr(), F32, B, rid[i % 8].data_ptr(), cnt.data_ptr(), k, b0["topk"][1].ids.data_ptr(),
+                                        b0["topk"][1].dist.data_ptr(), b0["out_cnt"].data_ptr(), b0["scored"].data_ptr())
+                for i in range(4):
+                    rs(i)
+                cp.sync()
+                cp.refine_timing_begin(40, 1)
+                for i in range(40):
+                    rs(i)
+                nl, tms = cp.refine_timing_end()
+            del big, rid
+            hp_ms = tms / max(1, nl)
+            hbm_proof = dict(kernel="refine_stream_kernel<float,float,32,true>", store_rows=NS, store_bytes=NS * d * 4, launches=nl,
+                             avg_launch_ms=round(hp_ms, 5), achieved=round(ref_bytes / (hp_ms * 1e-3) / 1e9, 1),
+                             frac=round(ref_bytes / (hp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                             note="1024 x 256 uniformly random rows of a 4.1 GB store per launch, 8 id sets cycled: at most 6 % of a launch's rows "
+                                  "can sit in the 256 MiB Infinity Cache")
+            # (b) BASELINE config #4's refine shape: d = 768, B = 1024 -> four 256-row chunks per query + refine_merge_kernel
+            d4, B4 = 768, 1024
+            cfg4 = pkg.PaperRuntimeConfig(tables=1, divisions=1, m=8, lambda_=2, dim=d4, refinement_limit=B4)
+            with pkg.FspannContext(cfg4, local_rank) as c4:
+                cand4 = torch.randn((2, Q, B4, d4), dtype=torch.float32, device=dev)          # 2 x 3.2 GB
+                q4 = torch.randn((Q, d4), dtype=torch.float32, device=dev)
+                ids4 = torch.arange(Q * B4, dtype=torch.int32, device=dev).view(Q, B4)
+                cnt4 = torch.full((Q,), B4, dtype=torch.int32, device=dev)
+                oi4 = torch.zeros((Q, k), dtype=torch.int32, device=dev)
+                od4 = torch.zeros((Q, k), dtype=torch.float64, device=dev)
+                oc4 = torch.zeros(Q, dtype=torch.int32, device=dev)
+                torch.cuda.synchronize()
+                s4 = torch.cuda.ExternalStream(c4.stream, device=dev)
 
-        def r64(i):
-            ctx.refine_dev(Q, q64.data_ptr(), pkg._native.F64, cand64[i % NB64].data_ptr(), pkg._native.F64, B, ids64.data_ptr(), cnt64.data_ptr(), k,
-                           b0["topk"][1].ids.data_ptr(), b0["topk"][1].dist.data_ptr(), b0["out_cnt"].data_ptr(), b0["scored"].data_ptr())
-        for i in range(4):
-            r64(i)
-        ctx.sync()
-        ctx.refine_timing_begin(32, 1)
-        for i in range(32):
-            r64(i)
-            ctx.sync()                        # solo dispatches
-        nl64, tms64 = ctx.refine_timing_end()
-        bytes64 = Q * (B * d * 8 + d * 8 + k * 8)
-        ms64 = tms64 / max(1, nl64)
-        f64_rows = dict(kernel="refine_stream_kernel<double,double,16,false>", algorithmic_bytes_per_launch=bytes64, launches=nl64,
-                        avg_launch_ms=round(ms64, 5), achieved=round(bytes64 / (ms64 * 1e-3) / 1e9, 1),
-                        frac=round(bytes64 / (ms64 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                        note="the scan over fp64 candidate rows and an fp64 query (the dtype GpuQueryServiceImpl hands over), device-resident "
-                             "blocks, solo dispatches with kernel-attached events")
-        del cand64, q64
-    else:
-        f64_rows = None
-    kname = "refine_stream_kernel<float,float,32,%s>" % ("true" if mode == "store" else "false")
-    if mode != "store" and B > 256 and 32 < k <= 128:
-        kname = ("refine_stream_kernel<float,float,32,false,true> (a workgroup walks a run of consecutive chunks of one query and keeps its best k "
-                 "in LDS: one list per run, no merge kernel when a run is the whole query)")
-    if args.pipeline == "front" and not use_tick and mode == "dense" and B <= 256:
-        kname = "refine_stream_fix_kernel<false> (the streaming scan whose workgroups first finish queries the bounded select handed over)"
-    roofline = dict(bound="hbm", kernel=kname, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, peak_spec=HBM_PEAK_GBS,
-                    peak_measured=peak_measured, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4),
-                    frac_of_measured=round(achieved / peak_measured, 4) if peak_measured else None,
-                    peak_launch_sized=peak_launch_sized,
-                    frac_of_launch_sized=round(achieved / peak_launch_sized, 4) if peak_launch_sized else None,
-                    traffic=traffic, traffic_source=traffic_src,
-                    algorithmic_bytes_per_launch=ref_bytes, avg_launch_ms=round(ref_ms, 5), launches=ref_launches, solo=solo_stats,
-                    working_set_bytes=(NB * Q * B * d * 4) if mode == "dense" else n * d * 4,
-                    timing=("every %d-th step of the timed region runs its three stages as stand-alone kernels instead of the shared one; the "
-                            "refinement-scan dispatch of those steps carries HIP start/stop events (hipExtLaunchKernel, on the context's stream)"
-                            if use_tick else (("every %d-th step of the timed region first drains all contexts and then runs alone; its refinement-scan "
-                                               "dispatch carries HIP start/stop events (hipExtLaunchKernel, on its context's stream): a SOLO duration, "
-                                               "measured inside the timed region") if (args.solo_in_region or args.solo_tail <= 0 or shipped) else
-                                              ("SOLO durations from the untimed tail behind the timed region (roofline.solo.tail: drained dispatches of the same "
-                                               "scan in the same pipeline, HIP start/stop events attached to each, hipExtLaunchKernel on the context's stream); "
-                                               "inside the timed region — which holds exactly --steps pipeline steps, no drain — every %d-th scan dispatch of the "
-                                               "other contexts carries events too: roofline.overlapped")) if nctx > 1 else
-                            "HIP start/stop events attached to every %d-th refinement-scan dispatch of the timed region "
-                            "(hipExtLaunchKernel, on the context's stream)") % TIMED_EVERY,
-                    bracket_ms=round(float(st_mean[3]), 5),
-                    overlapped=(dict(launches=overlapped_main[0], avg_launch_ms=round(overlapped_main[1], 5),
-                                     achieved=round(ref_bytes / (overlapped_main[1] * 1e-3) / 1e9, 1),
-                                     note="the same kernel's sampled dispatches while kernels of the other contexts run beside it (what a kernel "
-                                          "trace of this command averages over): it shares HBM then, so this is not a roofline of the kernel")
-                                if overlapped_main and overlapped_main[1] > 0 else None),
-                    hbm_proof=hbm_proof, cfg4_shape=cfg4_shape, f64_rows=f64_rows)
+                def r4(i):
+                    c4.refine_dev(Q, q4.data_ptr(), F32, cand4[i & 1].data_ptr(), F32, B4, ids4.data_ptr(), cnt4.data_ptr(), k, oi4.data_ptr(),
+                                  od4.data_ptr(), oc4.data_ptr(), 0)
+                for i in range(2):
+                    r4(i)
+                c4.sync()
+                c4.refine_timing_begin(12, 1)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(s4)
+                for i in range(12):
+                    r4(i)
+                e1.record(s4)
+                nl4, tms4 = c4.refine_timing_end()
+                bytes4 = Q * (B4 * d4 * 4 + d4 * 4 + k * 8)
+                scan_ms, call_ms = tms4 / max(1, nl4), e0.elapsed_time(e1) / 12
+                cfg4_shape = dict(kernel="refine_stream_kernel<float,float,32,false> over 4 chunks per query + refine_merge_kernel", Q=Q, B=B4, dim=d4,
+                                  algorithmic_bytes_per_launch=bytes4, scan_launch_ms=round(scan_ms, 4), scan_plus_merge_ms=round(call_ms, 4),
+                                  achieved=round(bytes4 / (scan_ms * 1e-3) / 1e9, 1), frac=round(bytes4 / (scan_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                  note="two 3.2 GB blocks alternate; events attached to the scan kernel; scan_plus_merge_ms = whole fspann_refine_dev call")
+                del cand4
+            # (c) fp64 rows, fp64 query — what the JVM hands over (double[] from decryptFromPoint): refine_stream_kernel<double,double,16,false>,
+            # algorithmic bytes = Q * (B*d*8 + d*8 + k*8); 8 distinct blocks are cycled (2.1 GB at config #2)
+            NB64 = 8
+            cand64 = torch.randn((NB64, Q, B, d), dtype=torch.float64, device=dev)
+            q64 = q_all[0].double()
+            ids64 = torch.arange(Q * B, dtype=torch.int32, device=dev).view(Q, B)
+            cnt64 = torch.full((Q,), B, dtype=torch.int32, device=dev)
+            b0 = bufs[0]
+            torch.cuda.synchronize()
 
-    # Route (probe + select) is bound by dependent L2 rounds and LDS atomics, not by HBM or MFMA; its algorithmic bytes
-    # (per (t,d) search + rep/id-range fetch + P*S ids) are reported for scale.
-    P_, S_ = P_eff, 64
-    nparts = (n + S_ - 1) // S_
-    levels = max(1, int(np.ceil(np.log(max(nparts, 2)) / np.log(16))))
-    route_bytes = Q * (TD * (levels * 16 * 16 + (2 * P_ - 1) * (8 * W + 8) + P_ * S_ * 4) + B * 4)
-    route_ms = float(st_mean[1])
-    rinfo = ctx.last_route_info()
-    route_info = dict(kernels=("route_select_lazy_kernel<256> with the probe fused in (bounded select; %d of %d queries handed to the full select)"
-                               % (rinfo["overflowed"], Q)) if rinfo["lazy"] else "route_probe_kernel + route_select_kernel<true,512>",
-                      bound="L2 latency + LDS atomics (integer)", avg_ms=round(route_ms, 5), algorithmic_bytes_per_launch=int(route_bytes),
-                      achieved_GBs=round(route_bytes / (route_ms * 1e-3) / 1e9, 1))
+            def r64(i):
+                ctx.refine_dev(Q, q64.data_ptr(), pkg._native.F64, cand64[i % NB64].data_ptr(), pkg._native.F64, B, ids64.data_ptr(), cnt64.data_ptr(), k,
+                               b0["topk"][1].ids.data_ptr(), b0["topk"][1].dist.data_ptr(), b0["out_cnt"].data_ptr(), b0["scored"].data_ptr())
+            for i in range(4):
+                r64(i)
+            ctx.sync()
+            ctx.refine_timing_begin(32, 1)
+            for i in range(32):
+                r64(i)
+                ctx.sync()                        # solo dispatches
+            nl64, tms64 = ctx.refine_timing_end()
+            bytes64 = Q * (B * d * 8 + d * 8 + k * 8)
+            ms64 = tms64 / max(1, nl64)
+            f64_rows = dict(kernel="refine_stream_kernel<double,double,16,false>", algorithmic_bytes_per_launch=bytes64, launches=nl64,
+                            avg_launch_ms=round(ms64, 5), achieved=round(bytes64 / (ms64 * 1e-3) / 1e9, 1),
+                            frac=round(bytes64 / (ms64 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                            note="the scan over fp64 candidate rows and an fp64 query (the dtype GpuQueryServiceImpl hands over), device-resident "
+                                 "blocks, solo dispatches with kernel-attached events")
+            del cand64, q64
+        else:
+            f64_rows = None
+        kname = "refine_stream_kernel<float,float,32,%s>" % ("true" if mode == "store" else "false")
+        if mode != "store" and B > 256 and 32 < k <= 128:
+            kname = ("refine_stream_kernel<float,float,32,false,true> (a workgroup walks a run of consecutive chunks of one query and keeps its best k "
+                     "in LDS: one list per run, no merge kernel when a run is the whole query)")
+        if args.pipeline == "front" and not use_tick and mode == "dense" and B <= 256:
+            kname = "refine_stream_fix_kernel<false> (the streaming scan whose workgroups first finish queries the bounded select handed over)"
+        roofline = dict(bound="hbm", kernel=kname, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, peak_spec=HBM_PEAK_GBS,
+                        peak_measured=peak_measured, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4),
+                        frac_of_measured=round(achieved / peak_measured, 4) if peak_measured else None,
+                        peak_launch_sized=peak_launch_sized,
+                        frac_of_launch_sized=round(achieved / peak_launch_sized, 4) if peak_launch_sized else None,
+                        traffic=traffic, traffic_source=traffic_src,
+                        algorithmic_bytes_per_launch=ref_bytes, avg_launch_ms=round(ref_ms, 5), launches=ref_launches, solo=solo_stats,
+                        working_set_bytes=(NB * Q * B * d * 4) if mode == "dense" else n * d * 4,
+                        timing=("every %d-th step of the timed region runs its three stages as stand-alone kernels instead of the shared one; the "
+                                "refinement-scan dispatch of those steps carries HIP start/stop events (hipExtLaunchKernel, on the context's stream)"
+                                if use_tick else (("every %d-th step of the timed region first drains all contexts and then runs alone; its refinement-scan "
+                                                   "dispatch carries HIP start/stop events (hipExtLaunchKernel, on its context's stream): a SOLO duration, "
+                                                   "measured inside the timed region") if (args.solo_in_region or args.solo_tail <= 0 or shipped) else
+                                                  ("SOLO durations from the untimed tail behind the timed region (roofline.solo.tail: drained dispatches of the same "
+                                                   "scan in the same pipeline, HIP start/stop events attached to each, hipExtLaunchKernel on the context's stream); "
+                                                   "inside the timed region — which holds exactly --steps pipeline steps, no drain — every %d-th scan dispatch of the "
+                                                   "other contexts carries events too: roofline.overlapped")) if nctx > 1 else
+                                "HIP start/stop events attached to every %d-th refinement-scan dispatch of the timed region "
+                                "(hipExtLaunchKernel, on the context's stream)") % TIMED_EVERY,
+                        bracket_ms=round(float(st_mean[3]), 5),
+                        overlapped=(dict(launches=overlapped_main[0], avg_launch_ms=round(overlapped_main[1], 5),
+                                         achieved=round(ref_bytes / (overlapped_main[1] * 1e-3) / 1e9, 1),
+                                         note="the same kernel's sampled dispatches while kernels of the other contexts run beside it (what a kernel "
+                                              "trace of this command averages over): it shares HBM then, so this is not a roofline of the kernel")
+                                    if overlapped_main and overlapped_main[1] > 0 else None),
+                        hbm_proof=hbm_proof, cfg4_shape=cfg4_shape, f64_rows=f64_rows)
 
-    # ---------------- recall@10 + distance ratio vs exact kNN of the data set (reported, never assumed) ------------------
+        # Route (probe + select) is bound by dependent L2 rounds and LDS atomics, not by HBM or MFMA; its algorithmic bytes
+        # (per (t,d) search + rep/id-range fetch + P*S ids) are reported for scale.
+        P_, S_ = P_eff, 64
+        nparts = (n + S_ - 1) // S_
+        levels = max(1, int(np.ceil(np.log(max(nparts, 2)) / np.log(16))))
+        route_bytes = Q * (TD * (levels * 16 * 16 + (2 * P_ - 1) * (8 * W + 8) + P_ * S_ * 4) + B * 4)
+        route_ms = float(st_mean[1])
+        rinfo = ctx.last_route_info()
+        route_info = dict(kernels=("route_select_lazy_kernel<256> with the probe fused in (bounded select; %d of %d queries handed to the full select)"
+                                   % (rinfo["overflowed"], Q)) if rinfo["lazy"] else "route_probe_kernel + route_select_kernel<true,512>",
+                          bound="L2 latency + LDS atomics (integer)", avg_ms=round(route_ms, 5), algorithmic_bytes_per_launch=int(route_bytes),
+                          achieved_GBs=round(route_bytes / (route_ms * 1e-3) / 1e9, 1))
+
+    # ---------------- (--full) recall@10 + distance ratio vs exact kNN of the data set (reported, never assumed) ---------
     recall = ratio = None
     gt_ms = None
-    if rank == 0:
+    if rank == 0 and full:
         # exact ground truth on the GPU with the reference's own arithmetic and tie rule (fspann_groundtruth_dev =
         # GroundtruthPrecompute.run), recall@k / distance ratio@k as ForwardSecureANNSystem.computeMetricsAtK defines them
         nv = q_live if args.scaling == "strong" else Q
@@ -1249,9 +1264,9 @@ def main():
             except Exception as e:      # the sweep is a report, never a reason to lose the bench line
                 recall_sweep.append(dict(B=Bs, error=str(e)[:200]))
 
-    # ---------------- CPU baseline: the oracle on this box's host cores (rank 0, N = 1 only) --------------------------------
+    # ---------------- (--full) CPU baseline: the oracle on this box's host cores (rank 0, N = 1 only) ---------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:
         O = graft.load_oracle()
         o = O.Oracle(T, D, m, lam, d, refinement_limit=B, max_global_candidates=int(wl.get("hard_cap", 20000)),
                      probe_override=P_cfg if P_cfg > 0 else -1)
@@ -1323,7 +1338,7 @@ def main():
                                     note="the same port with one thread per logical CPU the process may be scheduled on; the box gives this process only "
                                          "a share of them: `cores_worth` = this rate / the single-thread rate = how many cores' worth of work it actually got")
 
-    if use_dist and comms is not None:
+    if full and use_dist and comms is not None:
         # merged result = every rank's top-k in rank order.  EVERY rank checks EVERY slice: the buffer the path's own collective
         # filled against an independent torch.distributed all-gather of the same local buffers, then all ranks agree.
         gat, loc = bufs[0]["gathered"][0], bufs[0]["topk"][0]
@@ -1356,7 +1371,7 @@ def main():
                    "sift1m_P10_HIGH": dict(recall_at_100=0.7714, distance_ratio=1.0097, art_ms=4185.6, source="fsp-anns-parent/logs/New Results:54-57")}
         for wname in ("sift1m_P4_FAST", "sift1m_P10_HIGH"):
             cmd = [sys.executable, os.path.abspath(__file__), "--workload", wname, "--k", "100", "--data", args.shipped_data, "--steps", str(args.shipped_steps),
-                   "--warmup", "3", "--prewarm", "10", "--cpu-sample", "64", "--no-shipped", "--solo-tail", "0"]
+                   "--warmup", "3", "--prewarm", "10", "--cpu-sample", "64", "--full", "--no-shipped", "--solo-tail", "0"]
             t_c = time.perf_counter()
             try:
                 pr = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
@@ -1388,8 +1403,8 @@ def main():
         # LSH has signal: this line says what the same kernels do when the tables agree on some candidates, and what recall B = 256 buys)
         other = {}
         if args.data == "gaussian" and args.workload == "sift1m_T16_b32_B256_Q1024":
-            cmd = [sys.executable, os.path.abspath(__file__), "--data", args.shipped_data, "--steps", "200", "--warmup", "10", "--no-shipped", "--no-extras",
-                   "--no-cpu-baseline"]
+            cmd = [sys.executable, os.path.abspath(__file__), "--data", args.shipped_data, "--steps", "200", "--warmup", "10", "--full",
+                   "--no-shipped", "--no-extras", "--no-cpu-baseline"]
             try:
                 pr = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
                 line = [x for x in pr.stdout.splitlines() if x.startswith("{")]
@@ -1422,7 +1437,7 @@ def main():
             "scaling": args.scaling,
             "vs_baseline": None,
             "dtype": "f64",
-            "data": data_desc + ", exact-kNN ground truth of the same set",
+            "data": data_desc + (", exact-kNN ground truth of the same set" if full else ""),
             "config": {"workload": args.workload, "n": n, "dim": d, "tables": T, "divisions": D, "m": m, "lambda": lam,
                        "code_bits": m * lam, "probes": P_eff, "hard_cap": HARD_CAP, "B": B, "k": k, "queries_per_gpu_per_step": Q, "queries_per_step": q_job,
                        "distinct_query_batches": NB, "route_counters": bool(args.route_counters), "passes_per_step": len(probe_passes),
@@ -1443,7 +1458,7 @@ def main():
             "recall_at_10": recall if k == 10 else None,
             "distance_ratio_at_10": ratio if k == 10 else None,
             "recall_at_k": {"k": k, "recall": recall, "distance_ratio": ratio},
-            "treeified": {"finished_on_host_while_packing": int(treeified_setup), "finished_on_host_in_checked_batch": int(treeified_batch0),
+            "treeified": {"finished_on_host_while_packing": int(treeified_setup), "finished_on_host_in_checked_batch": int(treeified_batch0) if full else None,
                           "flagged_and_left_empty_in_all_timed_and_untimed_runs": int(flagged_in_timed_runs),
                           "note": "queries whose HashMap<String,Long> bestScore treeifies a bin: flagged by the full select (count -1), finished by "
                                   "the library's JDK model on the host (fspann_route_resolve_dev), outside the timed region"},
@@ -1452,9 +1467,9 @@ def main():
                       "note": "fspann_build_index of the whole base set: H2D of the vectors, coding (MFMA pre-filter + exact re-check), "
                               "radix sorts + partition cut of every table on the GPU, treeify replay of the staging map on the host"},
             "groundtruth": {"kernel": "gt_dist_kernel + gt_select_kernel (exact, GroundtruthPrecompute semantics)", "queries": Q, "base": n,
-                            "ms": round(gt_ms, 1) if gt_ms is not None else None},
+                            "ms": round(gt_ms, 1) if gt_ms is not None else None} if full else None,
             "stages_ms": {"encode": round(float(st_mean[0]), 5), "route_select": round(float(st_mean[1]), 5),
-                          "stage_candidates": round(float(st_mean[2]), 5), "refine_topk": round(float(st_mean[3]), 5)},
+                          "stage_candidates": round(float(st_mean[2]), 5), "refine_topk": round(float(st_mean[3]), 5)} if full else None,
             "roofline": roofline,
             "encode_stage": encode_stage,
             "route_stage": route_info,

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: A/B of the default pipeline's step time against scan workgroups per CU and contexts per GPU (dev tool).
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/ab_stream; mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-extras --steps 400 --warmup 10"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extras --steps 400 --warmup 10"
 run() { tag=$1; shift; env "$@" $B $EXTRA > $O/$tag.json 2> $O/$tag.log; python3 - <<PY
 import json
 try:

@@ -3,7 +3,7 @@
 # usage (through gpurun): bash tools/profile_r02.sh <tag>
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=${1:-r02_v1}; O=$R/gpurun_out/prof_$TAG; rm -rf $O; mkdir -p $O
-B="$R/bench.py --no-cpu-baseline --no-extras"
+B="$R/bench.py --full --no-cpu-baseline --no-extras"
 # 1) the default command (concurrent contexts): what the driver's line is produced by
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/default -- python3 $B --steps 100 --warmup 10 > $O/default.json 2> $O/default.log
 # 2) one context, one stream: every kernel's duration is a solo duration

@@ -6,7 +6,7 @@ args=()
 while [ "$1" != "--" ]; do args+=("$1"); shift; done; shift
 for v in "$@"; do
   name=${v%%=*}; rest=${v#*=}; lib=${rest%%:*}; envs=""; [ "$rest" != "$lib" ] && envs=${rest#*:}
-  env AB_LIB=$lib $envs timeout -k 10 400 python tools/ab_bench.py "${args[@]}" > $out/$name.json 2> $out/$name.err || { tail -5 $out/$name.err; exit 1; }
+  env AB_LIB=$lib $envs timeout -k 10 400 python tools/ab_bench.py --full "${args[@]}" > $out/$name.json 2> $out/$name.err || { tail -5 $out/$name.err; exit 1; }
   python - <<PY
 import json
 d=json.loads(open("$out/$name.json").read().strip().splitlines()[-1])

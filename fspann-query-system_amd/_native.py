@@ -122,6 +122,8 @@ _SIGS = {
     "fspann_set_deleted": (_i, [_vp, _vp, _i64, _i]),
     "fspann_route_resolve_dev": (_i, [_vp, _i64, _vp, _i, _i32, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "fspann_search_store_finish_dev": (_i, [_vp, _i64, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "fspann_search_retry_dev": (_i, [_vp, _i64, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fspann_search_retry_finish_dev": (_i, [_vp, _i64, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "fspann_index_save": (_i, [_vp, C.c_char_p]),
     "fspann_index_load": (_i, [_vp, C.c_char_p]),
     "fspann_index_dims": (_i, [_vp, _i, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -171,6 +173,8 @@ _SIGS = {
     "fspann_pipeline_submit": (_i, [_vp, _i64, _vp, C.POINTER(C.c_uint64)]),
     "fspann_pipeline_collect": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(_i64), _vp, _vp, _vp]),
     "fspann_pipeline_stats": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
+    "fspann_pipeline_set_retry": (_i, [_vp, _i]),
+    "fspann_pipeline_retry_stats": (_i, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "fspann_pipeline_destroy": (None, [_vp]),
     "fspann_topk_bytes": (_sz, [_i64, _i]),
     "fspann_topk_dist_offset": (_sz, [_i64, _i]),

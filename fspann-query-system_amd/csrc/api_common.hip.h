@@ -93,4 +93,33 @@ inline fspann_ctx* index_owner(fspann_ctx* c) { return c->share_parent ? c->shar
     } while (0)
 
 
+
+// The work area of fspann_search_store_dev (codes | F_q ids | counts | bad, each rounded to 256 bytes), shared with the calls
+// that complete or extend it (fspann_search_store_finish_dev, fspann_search_retry_dev / _finish_dev): ONE layout.
+struct SearchArea {
+    const uint64_t* codes;
+    int32_t* sel;
+    int32_t* cnt;
+    int32_t* bad;
+};
+size_t search_area_bytes(const fspann_ctx* c, int64_t nq, int64_t B) {
+    const size_t cb = (static_cast<size_t>(nq) * c->TD * c->W * 8 + 255) & ~size_t(255);
+    const size_t ib = (static_cast<size_t>(nq) * B * 4 + 255) & ~size_t(255);
+    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
+    return cb + ib + 2 * nb;
+}
+// Pointers into the area (the caller's buffers where it passed them); false when no area of this size exists.
+bool search_area(const fspann_ctx* c, int64_t nq, int64_t B, int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, SearchArea& s) {
+    const size_t cb = (static_cast<size_t>(nq) * c->TD * c->W * 8 + 255) & ~size_t(255);
+    const size_t ib = (static_cast<size_t>(nq) * B * 4 + 255) & ~size_t(255);
+    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
+    if (!c->ws_search.p || c->ws_search.bytes < search_area_bytes(c, nq, B)) return false;
+    char* w = static_cast<char*>(c->ws_search.p);
+    s.codes = reinterpret_cast<const uint64_t*>(w);
+    s.sel = sel_ids_dev ? sel_ids_dev : reinterpret_cast<int32_t*>(w + cb);
+    s.cnt = sel_count_dev ? sel_count_dev : reinterpret_cast<int32_t*>(w + cb + ib);
+    s.bad = bad_dev ? bad_dev : reinterpret_cast<int32_t*>(w + cb + ib + nb);
+    return true;
+}
+
 }  // namespace

@@ -16,6 +16,9 @@ __global__ void set_deleted_bits_kernel(const int32_t* __restrict__ handles, int
     else atomicAnd(&bits[h >> 5], ~(1u << (h & 31)));
 }
 
+int resolve_queries(fspann_ctx* c, const std::vector<int64_t>& todo, const uint64_t* codes_dev, int probe_override, int32_t limit, int64_t cap,
+                    int32_t* ids_dev, int32_t* score_dev, int32_t* count_dev, int32_t* kept_dev, int32_t* raw_dev, int64_t* resolved_out, int64_t* left_out);
+
 // Finish the flagged queries (count == -1) of a Route call on the host.  Synchronises the context's stream.
 int resolve_unmodelled(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int probe_override, int32_t limit, int64_t cap, int32_t* ids_dev,
                        int32_t* score_dev, int32_t* count_dev, int32_t* kept_dev, int32_t* raw_dev, int64_t* resolved_out, int64_t* left_out) {
@@ -27,6 +30,13 @@ int resolve_unmodelled(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int
     std::vector<int64_t> todo;
     for (int64_t i = 0; i < nq; i++)
         if (cnt[i] == kRouteUnmodelled) todo.push_back(i);
+    if (todo.empty()) return FSPANN_OK;
+    return resolve_queries(c, todo, codes_dev, probe_override, limit, cap, ids_dev, score_dev, count_dev, kept_dev, raw_dev, resolved_out, left_out);
+}
+
+// The same for the queries `todo` (flagged, ascending; the stream has been synchronised).
+int resolve_queries(fspann_ctx* c, const std::vector<int64_t>& todo, const uint64_t* codes_dev, int probe_override, int32_t limit, int64_t cap,
+                    int32_t* ids_dev, int32_t* score_dev, int32_t* count_dev, int32_t* kept_dev, int32_t* raw_dev, int64_t* resolved_out, int64_t* left_out) {
     if (todo.empty()) return FSPANN_OK;
     fspann_ctx* root = index_owner(c);
     const int TD = c->TD, W = c->W;
@@ -118,14 +128,11 @@ int fspann_search_store_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev,
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
     // the work area of the fspann_search_store_dev call this one completes (codes, and F_q when the caller did not ask for it)
-    const size_t cb = (static_cast<size_t>(nq) * c->TD * c->W * 8 + 255) & ~size_t(255);
-    const size_t ib = (static_cast<size_t>(nq) * B * 4 + 255) & ~size_t(255);
-    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
-    if (!c->ws_search.p || c->ws_search.bytes < cb + ib + 2 * nb) return fail(FSPANN_E_STATE, "no fspann_search_store_dev call of this size precedes");
-    char* w = static_cast<char*>(c->ws_search.p);
-    const uint64_t* codes = reinterpret_cast<const uint64_t*>(w);
-    int32_t* sel = sel_ids_dev ? sel_ids_dev : reinterpret_cast<int32_t*>(w + cb);
-    int32_t* cnt = sel_count_dev ? sel_count_dev : reinterpret_cast<int32_t*>(w + cb + ib);
+    SearchArea sa;
+    if (!search_area(c, nq, B, sel_ids_dev, sel_count_dev, nullptr, sa)) return fail(FSPANN_E_STATE, "no fspann_search_store_dev call of this size precedes");
+    const uint64_t* codes = sa.codes;
+    int32_t* sel = sa.sel;
+    int32_t* cnt = sa.cnt;
     return guarded([&]() -> int {
         int64_t done = 0, left = 0;
         int rc = resolve_unmodelled(c, nq, codes, probe_override, static_cast<int32_t>(B), B, sel, nullptr, cnt, nullptr, nullptr, &done, &left);

@@ -131,6 +131,7 @@ int fspann_pointstore_stats(fspann_pointstore* ps, int64_t* opened, int64_t* fai
 
 }  // extern "C"
 namespace {
+int pipeline_retry(fspann_pipeline* p, fspann_pipeline::Slot& s);     // api_retry.hip.h
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 void pipeline_stage_a(fspann_pipeline* p) {
@@ -217,7 +218,11 @@ void pipeline_stage_c(fspann_pipeline* p) {
                         hipMemcpyAsync(s.ids_dev, s.ids_pin, rows * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
                         hipMemcpyAsync(s.kcnt_dev, s.kcnt_pin, static_cast<size_t>(s.nq) * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)) rc = FSPANN_E_DEVICE;
             if (!rc) rc = fspann_refine_dev(c, s.nq, s.q_dev, FSPANN_F32, s.cand_dev, FSPANN_F32, p->B, static_cast<int32_t*>(s.ids_dev), static_cast<int32_t*>(s.kcnt_dev),
-                                            p->k, static_cast<int32_t*>(s.oi_dev), static_cast<double*>(s.od_dev), static_cast<int32_t*>(s.oc_dev), nullptr);
+                                            p->k, static_cast<int32_t*>(s.oi_dev), static_cast<double*>(s.od_dev), static_cast<int32_t*>(s.oc_dev),
+                                            s.retry ? static_cast<int32_t*>(s.sc_dev) : nullptr);
+            if (!rc && s.retry) {       // QSI:327-337: the short queries of this batch, again with 10 probes
+                try { rc = pipeline_retry(p, s); } catch (...) { rc = FSPANN_E_NOMEM; }
+            }
             if (!rc && (hipMemcpyAsync(s.out_ids_pin, s.oi_dev, static_cast<size_t>(s.nq) * p->k * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                         hipMemcpyAsync(s.out_dist_pin, s.od_dev, static_cast<size_t>(s.nq) * p->k * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                         hipMemcpyAsync(s.out_cnt_pin, s.oc_dev, static_cast<size_t>(s.nq) * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -228,6 +233,7 @@ void pipeline_stage_c(fspann_pipeline* p) {
         {
             std::lock_guard<std::mutex> lk(p->mu);
             p->sum_route_ms += s.t_route_ms; p->sum_decrypt_ms += s.t_decrypt_ms; p->sum_refine_ms += s.t_refine_ms; p->batches++;
+            p->sum_retry_ms += s.t_retry_ms; p->sum_retried += s.retried;
             p->done_q.push_back(si);
         }
         p->cv.notify_all();
@@ -248,9 +254,11 @@ void fspann_pipeline_destroy(fspann_pipeline* p) {
     if (p->tc.joinable()) p->tc.join();
     if (p->ctx) { (void)hipSetDevice(p->ctx->device); (void)hipStreamSynchronize(p->ctx->stream); }
     for (auto& s : p->slot) {
-        void* pins[] = {s.q_pin, s.sel_pin, s.cnt_pin, s.cand_pin, s.ids_pin, s.kcnt_pin, s.out_ids_pin, s.out_dist_pin, s.out_cnt_pin};
+        void* pins[] = {s.q_pin, s.sel_pin, s.cnt_pin, s.cand_pin, s.ids_pin, s.kcnt_pin, s.out_ids_pin, s.out_dist_pin, s.out_cnt_pin,
+                        s.list_pin, s.rsel_pin, s.rselc_pin, s.rids_pin, s.rkcnt_pin, s.rcand_pin};
         for (void* x : pins) if (x) (void)hipHostFree(x);
-        void* devs[] = {s.q_dev, s.codes_dev, s.sel_dev, s.cnt_dev, s.cand_dev, s.ids_dev, s.kcnt_dev, s.oi_dev, s.od_dev, s.oc_dev, s.bad_dev};
+        void* devs[] = {s.q_dev, s.codes_dev, s.sel_dev, s.cnt_dev, s.cand_dev, s.ids_dev, s.kcnt_dev, s.oi_dev, s.od_dev, s.oc_dev, s.bad_dev,
+                        s.sc_dev, s.ret_dev, s.list_dev, s.lcnt_dev};
         for (void* x : devs) if (x) (void)hipFree(x);
     }
     delete p;
@@ -276,6 +284,7 @@ int fspann_pipeline_create(fspann_ctx* c, fspann_pointstore* ps, int64_t nq_max,
             dev(&s.q_dev, nq_max * d * 4); dev(&s.codes_dev, static_cast<size_t>(nq_max) * c->TD * c->W * 8); dev(&s.sel_dev, rows * 4); dev(&s.cnt_dev, nq_max * 4);
             dev(&s.cand_dev, rows * d * 4); dev(&s.ids_dev, rows * 4); dev(&s.kcnt_dev, nq_max * 4); dev(&s.oi_dev, nq_max * k * 4); dev(&s.od_dev, nq_max * k * 8);
             dev(&s.oc_dev, nq_max * 4); dev(&s.bad_dev, nq_max * 4);
+            pin(&s.list_pin, (nq_max + 1) * 4); dev(&s.sc_dev, nq_max * 4); dev(&s.ret_dev, nq_max * 4); dev(&s.list_dev, nq_max * 4); dev(&s.lcnt_dev, 256);
         }
         if (!ok) { fspann_pipeline_destroy(p); return fail(FSPANN_E_NOMEM, "pinned / device staging buffers: allocation failed"); }
         for (int i = 0; i < fspann_pipeline::kSlots; i++) p->free_q.push_back(i);
@@ -300,10 +309,11 @@ int fspann_pipeline_submit(fspann_pipeline* p, int64_t nq, const float* q_host, 
         si = p->free_q.front(); p->free_q.pop_front();
     }
     fspann_pipeline::Slot& s = p->slot[si];
-    s.nq = nq; s.rc = 0; s.unmodelled = 0;
+    s.nq = nq; s.rc = 0; s.unmodelled = 0; s.retried = 0; s.t_retry_ms = 0;
     std::memcpy(s.q_pin, q_host, static_cast<size_t>(nq) * p->ctx->cfg.dim * 4);
     {
         std::lock_guard<std::mutex> lk(p->mu);
+        s.retry = p->retry;
         s.ticket = p->next_ticket++;
         if (ticket) *ticket = s.ticket;
         p->qa.push_back(si);

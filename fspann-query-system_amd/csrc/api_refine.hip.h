@@ -7,7 +7,11 @@ namespace {
 template <typename TC, typename TQ, int DC, bool GATHER>
 int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids,
                      const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
-                     int32_t* scored) {
+                     int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
+    // qlist / qcount (device, the retry pass of fspann_search_retry_dev): only the queries qlist[0 .. *qcount) are scored, each at its
+    // own index; the launches are sized for nq and their workgroups past the count leave at once.  One partial list per chunk
+    // (no running top-k), no hand-over, no kernel-attached timing.
+    const bool listed = qlist != nullptr;
     constexpr int VN = VecOf<TC>::N;
     const int d = c->cfg.dim;
     const int nchunks = static_cast<int>((B + kRefRows - 1) / kRefRows);
@@ -19,7 +23,7 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
     // fill the grid (one query: one chunk per workgroup, as before).
     const int stream_wgs_m = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, 4) : 4;
     int npieces = 0, cpp = 0;
-    if (!GATHER && nchunks > 1 && k > kRefFilterMaxK && k <= kRunMaxK && c->knob_refine_run && stream_wgs_m > 0 && DC * sizeof(TC) == 128 &&
+    if (!listed && !GATHER && nchunks > 1 && k > kRefFilterMaxK && k <= kRunMaxK && c->knob_refine_run && stream_wgs_m > 0 && DC * sizeof(TC) == 128 &&
         (d % VN == 0) && ((reinterpret_cast<uintptr_t>(cand) & 15) == 0) && nq * nchunks < (int64_t(1) << 31)) {   // (= the streaming scan will run)
         const int64_t slots = static_cast<int64_t>(c->num_cus) * stream_wgs_m;
         int np = (nq * 2 >= slots) ? 1 : static_cast<int>(std::min<int64_t>(nchunks, (slots + nq - 1) / std::max<int64_t>(nq, 1)));
@@ -58,6 +62,34 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
     };
     int lrc = FSPANN_OK;
     bool streamed = false;
+    if (listed) {
+        const int stream_wgs_l = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, GATHER ? 3 : 4) : (GATHER ? 3 : 4);
+        bool done = false;
+        if constexpr (DC * sizeof(TC) == 128) if (vec && stream_wgs_l > 0 && nq * nchunks < (int64_t(1) << 31)) {
+            const unsigned sgrid = static_cast<unsigned>(std::min<int64_t>(nq * nchunks, static_cast<int64_t>(c->num_cus) * stream_wgs_l));
+            hipLaunchKernelGGL((refine_stream_list_kernel<TC, TQ, DC, GATHER>), dim3(sgrid), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
+            done = true;
+        }
+        if (!done) {
+            auto kern = vec ? refine_scan_list_kernel<TC, TQ, DC, true, GATHER> : refine_scan_list_kernel<TC, TQ, DC, false, GATHER>;
+            if (lds > 64 * 1024) FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
+        }
+        FSP_HIP(hipGetLastError());
+        if (nchunks > 1) {
+            const size_t mlds = static_cast<size_t>(nchunks) * k * 8 + static_cast<size_t>(nchunks) * 4 + 16;
+            if (mlds <= 72 * 1024) {
+                auto mk = refine_merge_list_kernel<true>;
+                if (mlds > 64 * 1024) FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mk), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
+                hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>(nq)), dim3(256), mlds, c->stream, partial, pcnt, nchunks, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+            } else {
+                hipLaunchKernelGGL(refine_merge_list_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(256), static_cast<size_t>(nchunks) * 4 + 16, c->stream, partial, pcnt,
+                                   nchunks, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+            }
+            FSP_HIP(hipGetLastError());
+        }
+        return FSPANN_OK;
+    }
     // workgroups per CU of the streaming scan: dense blocks run at 128 registers (4 per CU: a 1024-query batch is exactly one
     // unit per workgroup on 256 CUs), the store gather at 3 per CU; FSPANN_REFINE_STREAM overrides, 0 = per-query scan
     const int stream_wgs = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, GATHER ? 3 : 4) : (GATHER ? 3 : 4);
@@ -132,12 +164,27 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
 template <typename TC, typename TQ, bool GATHER>
 int launch_refine_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids,
                     const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
-                    int32_t* scored) {
+                    int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
     constexpr int DC0 = (sizeof(TC) == 4) ? 32 : 16;
     const int dc_env = c->knob_refine_dc;
-    if (dc_env == DC0 * 2) return launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored);
-    if (dc_env == DC0 * 4) return launch_refine_dc<TC, TQ, DC0 * 4, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored);
-    return launch_refine_dc<TC, TQ, DC0, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored);
+    if (dc_env == DC0 * 2) return launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    if (dc_env == DC0 * 4) return launch_refine_dc<TC, TQ, DC0 * 4, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    return launch_refine_dc<TC, TQ, DC0, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+}
+
+// fspann_refine_store_dev over the queries qlist[0 .. *qcount) only (device list; the retry pass and its host finish).
+int refine_store_list(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype, int64_t B, const int32_t* cand_ids_dev, const int32_t* cand_count_dev,
+                      int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev, const int32_t* qlist, const int32_t* qcount) {
+#define FSP_REF(TC, TQ)                                                                                            \
+    return launch_refine_t<TC, TQ, true>(c, nq, static_cast<const TQ*>(q_dev), static_cast<const TC*>(c->d_store), B, \
+                                         cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, \
+                                         scored_dev, qlist, qcount)
+    if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F32) FSP_REF(float, float);
+    if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F64) FSP_REF(float, double);
+    if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F32) FSP_REF(double, float);
+    if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F64) FSP_REF(double, double);
+#undef FSP_REF
+    return fail(FSPANN_E_ARG, "unknown dtype");
 }
 
 
@@ -373,16 +420,14 @@ int fspann_search_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     if (nq < 0 || B <= 0 || B > INT32_MAX) return fail(FSPANN_E_ARG, "nq < 0 or B out of range");
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
-    const size_t cb = (static_cast<size_t>(nq) * c->TD * c->W * 8 + 255) & ~size_t(255);
-    const size_t ib = (static_cast<size_t>(nq) * B * 4 + 255) & ~size_t(255);
-    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
     int rc;
-    if ((rc = ensure(c, c->ws_search, cb + ib + 2 * nb))) return rc;
-    char* w = static_cast<char*>(c->ws_search.p);
-    uint64_t* codes = reinterpret_cast<uint64_t*>(w);
-    int32_t* sel = sel_ids_dev ? sel_ids_dev : reinterpret_cast<int32_t*>(w + cb);
-    int32_t* cnt = sel_count_dev ? sel_count_dev : reinterpret_cast<int32_t*>(w + cb + ib);
-    int32_t* bad = bad_dev ? bad_dev : reinterpret_cast<int32_t*>(w + cb + ib + nb);
+    if ((rc = ensure(c, c->ws_search, search_area_bytes(c, nq, B)))) return rc;
+    SearchArea sa;
+    (void)search_area(c, nq, B, sel_ids_dev, sel_count_dev, bad_dev, sa);
+    uint64_t* codes = const_cast<uint64_t*>(sa.codes);
+    int32_t* sel = sa.sel;
+    int32_t* cnt = sa.cnt;
+    int32_t* bad = sa.bad;
     if ((rc = fspann_encode_dev(c, nq, q_dev, q_dtype, codes, nullptr, bad))) return rc;
     if ((rc = fspann_route_dev(c, nq, codes, probe_override, static_cast<int32_t>(B), B, sel, nullptr, cnt, nullptr, nullptr))) return rc;
     return fspann_refine_store_dev(c, nq, q_dev, q_dtype, B, sel, cnt, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev);

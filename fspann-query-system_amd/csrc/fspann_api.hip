@@ -34,3 +34,4 @@
 #include "api_misc.hip.h"
 #include "api_build.hip.h"
 #include "api_ext.hip.h"
+#include "api_retry.hip.h"

@@ -154,6 +154,7 @@ struct fspann_ctx {
     int rt_every = 1, rt_seen = 0;       // events go on every rt_every-th dispatch
     bool rt_on = false;
     fspann::DevBuf ws_search;        // codes / F_q ids / counts of fspann_search_store_dev
+    fspann::DevBuf ws_retry;         // pick list, its count, retried / scored of fspann_search_retry_dev (api_retry.hip.h)
     unsigned attr_mask = 0;          // kernels whose dynamic-LDS ceiling has been raised on this context's device
     int ovf_flip = 0;                // which of the two overflow counters the last bounded select used
     unsigned ovf_gen_seen = 0;       // ws_ovf.gen whose counters have been zeroed (0 = never)

@@ -39,9 +39,17 @@ struct fspann_pipeline {
         int32_t* out_cnt_pin = nullptr;
         void *q_dev = nullptr, *codes_dev = nullptr, *sel_dev = nullptr, *cnt_dev = nullptr, *cand_dev = nullptr, *ids_dev = nullptr, *kcnt_dev = nullptr,
              *oi_dev = nullptr, *od_dev = nullptr, *oc_dev = nullptr, *bad_dev = nullptr;
+        // adaptive retry (fspann_pipeline_set_retry): scored / retried / pick list + count on the device, the pick list and the
+        // compact F_q, rows, ids and counts of the retried queries on the host (r* allocated when the retry is first switched on)
+        void *sc_dev = nullptr, *ret_dev = nullptr, *list_dev = nullptr, *lcnt_dev = nullptr;
+        int32_t* list_pin = nullptr;     // [nq_max + 1]: the list, then its count
+        int32_t *rsel_pin = nullptr, *rselc_pin = nullptr, *rids_pin = nullptr, *rkcnt_pin = nullptr;
+        float* rcand_pin = nullptr;
+        bool retry = false;              // the pipeline's setting when the batch was submitted
         int rc = 0;
         int64_t unmodelled = 0;          // queries of this batch the host model could not finish either (count stays -1: empty result)
-        double t_route_ms = 0, t_decrypt_ms = 0, t_refine_ms = 0;
+        int64_t retried = 0;
+        double t_route_ms = 0, t_decrypt_ms = 0, t_refine_ms = 0, t_retry_ms = 0;
     };
     fspann_ctx* ctx = nullptr;
     fspann_pointstore* ps = nullptr;
@@ -56,6 +64,7 @@ struct fspann_pipeline {
     uint64_t next_ticket = 1;
     std::thread ta, tb, tc;
     std::mutex gpu_mu;                               // stage A and C take turns on the context
-    double sum_route_ms = 0, sum_decrypt_ms = 0, sum_refine_ms = 0;
-    long long batches = 0;
+    double sum_route_ms = 0, sum_decrypt_ms = 0, sum_refine_ms = 0, sum_retry_ms = 0;
+    long long batches = 0, sum_retried = 0;
+    bool retry = false;                              // QSI's adaptive retry in stage C (off by default)
 };

@@ -579,10 +579,14 @@ struct RefineNoFix {
 };
 // kMulti (dense blocks, several chunks per query, 32 < k <= kRunMaxK): the workgroup's units are RUNS of consecutive chunks of one
 // query (item = query * npieces + piece, items wg, wg + nwg, ...; a.cpp chunks per run) and the top-K is refine_topk_running.
-template <typename TC, typename TQ, int DC, bool GATHER, class FixFn = RefineNoFix, bool kMulti = false>
+// kList (the retry pass of fspann_search_retry_dev): `nq` counts list slots and unit u belongs to query qlist[u / nchunks]; every
+// row, count and output is addressed by that query's own index.
+template <typename TC, typename TQ, int DC, bool GATHER, class FixFn = RefineNoFix, bool kMulti = false, bool kList = false>
 __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, unsigned char* smem, const int64_t wg, const int64_t nwg,
-                                                  const int64_t nq, const bool counts_fresh, const FixFn fix = FixFn()) {
+                                                  const int64_t nq, const bool counts_fresh, const FixFn fix = FixFn(),
+                                                  const int32_t* __restrict__ qlist = nullptr) {
     static_assert(!(kMulti && (GATHER || FixFn::enabled)), "runs of chunks: dense blocks, no hand-over");
+    static_assert(!(kList && (kMulti || FixFn::enabled)), "list mode: one partial list per chunk, no hand-over");
     using V = typename VecOf<TC>::type;
     constexpr int VN = VecOf<TC>::N;
     constexpr int PITCH = DC + VN;
@@ -633,9 +637,10 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     // unit -> (query, first row): no division at all for one chunk per query, a 32-bit one otherwise (the launcher keeps
     // nunits below 2^31) — a 64-bit division is ~100 scalar instructions, and two of them sat in front of the first load
     auto split_unit = [&](const int64_t uu, int64_t& qi, int& r0) {
-        if (nchunks == 1) { qi = uu; r0 = 0; return; }
+        if (nchunks == 1) { qi = uu; r0 = 0; if constexpr (kList) qi = qlist[qi]; return; }
         const uint32_t qq = static_cast<uint32_t>(uu) / static_cast<uint32_t>(nchunks);
         qi = qq;
+        if constexpr (kList) qi = qlist[qi];
         r0 = static_cast<int>(static_cast<uint32_t>(uu) - qq * static_cast<uint32_t>(nchunks)) * kRefRows;
     };
     auto load_sources = [&](const int64_t u) {
@@ -851,6 +856,29 @@ __global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_kern
     refine_stream_run<TC, TQ, DC, GATHER, RefineNoFix, kMulti>(a, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), nq, false);
 }
 
+// List mode of the streaming scan (the retry pass): the units of the queries qlist[0 .. *qcount), launched with the grid of the whole
+// batch; a workgroup without a unit leaves at once.
+template <typename TC, typename TQ, int DC, bool GATHER>
+__global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_list_kernel(RefineArgs<TC, TQ> a, const int32_t* __restrict__ qlist,
+                                                                                      const int32_t* __restrict__ qcount) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int64_t nsel = *qcount;
+    if (static_cast<int64_t>(blockIdx.x) >= nsel * a.nchunks) return;
+    refine_stream_run<TC, TQ, DC, GATHER, RefineNoFix, false, true>(a, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), nsel, false,
+                                                                    RefineNoFix(), qlist);
+}
+
+// List mode of the one-workgroup-per-chunk scan (layouts the stream does not take): block = (slot, chunk) over the whole batch.
+template <typename TC, typename TQ, int DC, bool VEC, bool GATHER>
+__global__ __launch_bounds__(kRefRows, (DC * sizeof(TC) <= 128 ? 4 : (DC * sizeof(TC) <= 256 ? 2 : 1))) void refine_scan_list_kernel(
+        RefineArgs<TC, TQ> a, const int32_t* __restrict__ qlist, const int32_t* __restrict__ qcount) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int64_t slot = static_cast<int64_t>(blockIdx.x) / a.nchunks;
+    if (slot >= static_cast<int64_t>(*qcount)) return;
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) - slot * a.nchunks;
+    refine_scan_block<TC, TQ, DC, VEC, GATHER>(a, smem, static_cast<int64_t>(qlist[slot]) * a.nchunks + chunk);
+}
+
 // Merge of per-chunk sorted top-k lists (B > kRefRows).  Each list is sorted by
 // (key, pos) and chunks hold disjoint, increasing pos ranges, so the global rank of
 // an element is its own rank plus, per other chunk, an upper/lower bound.
@@ -869,6 +897,91 @@ __global__ __launch_bounds__(256) void refine_merge_kernel(const RefinePartial* 
     uint64_t* s_keys = reinterpret_cast<uint64_t*>(merge_smem);                       // [nchunks][k]            (KEYS_IN_LDS)
     int32_t* s_pref = reinterpret_cast<int32_t*>(merge_smem + (KEYS_IN_LDS ? static_cast<size_t>(nchunks) * k * 8 : 0));   // [nchunks] prefix lengths
     const int64_t qi = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int nelem = nchunks * k;
+    __shared__ int s_total, s_nvalid, s_short;
+    __shared__ unsigned long long s_cut;
+    auto key_at = [&](int c, int i) -> uint64_t { return KEYS_IN_LDS ? s_keys[c * k + i] : partial[(qi * nchunks + c) * k + i].key; };
+    if (tid == 0) { s_total = 0; s_nvalid = 0; s_short = 0; s_cut = 0ull; }
+    if constexpr (KEYS_IN_LDS)
+        for (int e = tid; e < nelem; e += blockDim.x) s_keys[e] = partial[qi * nelem + e].key;     // entries beyond a list's length are never read
+    __syncthreads();
+    // Only lists that HOLD j keys can vouch for j keys at or below the cut.  A query with fewer candidates than B leaves trailing
+    // lists empty or short (the common partial-count case): with m lists of at least ceil(k / nchunks) keys, j = ceil(k / m) is tried —
+    // the lists holding j vouch, and the cut stands when they vouch for k between them; the shorter lists are searched like the others.
+    __shared__ int s_m;
+    const int j0 = (k + nchunks - 1) / nchunks;
+    if (tid == 0) s_m = 0;
+    __syncthreads();
+    for (int c = tid; c < nchunks; c += blockDim.x) {
+        const int cc = partial_cnt[(qi * nchunks + c) * 2];
+        s_pref[c] = cc;                                            // the list's length until the cut is known
+        atomicAdd(&s_total, cc);
+        atomicAdd(&s_nvalid, partial_cnt[(qi * nchunks + c) * 2 + 1]);
+        if (cc >= j0) atomicAdd(&s_m, 1);
+    }
+    __syncthreads();
+    const int j = s_m > 0 ? (k + s_m - 1) / s_m : 0;
+    for (int c = tid; c < nchunks; c += blockDim.x) {
+        const int cc = s_pref[c];
+        if (j > 0 && cc >= j) { atomicAdd(&s_short, 1); atomicMax(&s_cut, static_cast<unsigned long long>(key_at(c, j - 1))); }   // s_short: lists that vouch
+    }
+    __syncthreads();
+    const int eff = min(k, s_total);
+    if (j > 0 && static_cast<long long>(s_short) * j >= k) {        // the vouching lists hold >= k keys <= cut between them
+        const uint64_t cut = s_cut;
+        for (int c = tid; c < nchunks; c += blockDim.x) {
+            int lo = 0, hi = s_pref[c];                            // first index with key > cut
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (key_at(c, mid) <= cut) lo = mid + 1; else hi = mid; }
+            s_pref[c] = lo;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < nelem; e += blockDim.x) {
+        const int c = e / k, rk = e - c * k;
+        if (rk >= s_pref[c]) continue;
+        const uint64_t mykey = key_at(c, rk);
+        int rank = rk;
+        for (int c2 = 0; c2 < nchunks && rank < eff; c2++) {
+            if (c2 == c) continue;
+            // c2 < c: count keys <= mykey (earlier positions win ties); c2 > c: keys < mykey
+            int lo = 0, hi = s_pref[c2];
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                const uint64_t km = key_at(c2, mid);
+                const bool before = (c2 < c) ? (km <= mykey) : (km < mykey);
+                if (before) lo = mid + 1; else hi = mid;
+            }
+            rank += lo;
+        }
+        if (rank < eff) {
+            out_ids[qi * k + rank] = partial[qi * nelem + e].id;
+            out_dist[qi * k + rank] = __longlong_as_double(static_cast<long long>(mykey));
+        }
+    }
+    for (int i = eff + tid; i < k; i += blockDim.x) {
+        out_ids[qi * k + i] = -1;
+        out_dist[qi * k + i] = __longlong_as_double(0x7FF0000000000000LL);
+    }
+    if (tid == 0) {
+        out_count[qi] = eff;
+        if (scored) scored[qi] = s_nvalid;
+    }
+}
+
+// List mode (the retry pass): workgroup `slot` merges query qlist[slot]; the grid is the whole batch, the workgroups past *qcount
+// leave at once.  (A copy of refine_merge_kernel's body, so that the kernel every batch runs keeps its code.)
+template <bool KEYS_IN_LDS>
+__global__ __launch_bounds__(256) void refine_merge_list_kernel(const RefinePartial* __restrict__ partial,
+                                                                const int32_t* __restrict__ partial_cnt, int nchunks, int k,
+                                                                int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
+                                                                int32_t* __restrict__ out_count, int32_t* __restrict__ scored,
+                                                                const int32_t* __restrict__ qlist, const int32_t* __restrict__ qcount) {
+    extern __shared__ __align__(16) unsigned char merge_smem[];
+    uint64_t* s_keys = reinterpret_cast<uint64_t*>(merge_smem);                       // [nchunks][k]            (KEYS_IN_LDS)
+    int32_t* s_pref = reinterpret_cast<int32_t*>(merge_smem + (KEYS_IN_LDS ? static_cast<size_t>(nchunks) * k * 8 : 0));   // [nchunks] prefix lengths
+    if (static_cast<int64_t>(blockIdx.x) >= static_cast<int64_t>(*qcount)) return;
+    const int64_t qi = qlist[blockIdx.x];
     const int tid = threadIdx.x;
     const int nelem = nchunks * k;
     __shared__ int s_total, s_nvalid, s_short;

@@ -422,6 +422,33 @@ __global__ __launch_bounds__(kProbeThreads) void route_probe_kernel(RouteParams 
     if (in_range && gl == 0) nprobe_out[item] = np;
 }
 
+// List mode (the retry pass of fspann_search_retry_dev): items are (slot, td) over the queries prm.qlist[0 .. *prm.qcount); each list
+// is written at its query's own index, where the selects read it.  The launch is sized for prm.nq: a workgroup past the count leaves.
+__global__ __launch_bounds__(kProbeThreads) void route_probe_list_kernel(RouteParams prm, int4* __restrict__ probe_out,
+                                                                        int32_t* __restrict__ nprobe_out, int G) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int TD = prm.TD, W = prm.W, P = prm.P;
+    const int nd = 2 * P - 1;
+    const int gpb = kProbeThreads / G;                 // groups per block (G: a power of two)
+    const int lgG = 31 - __clz(G);
+    const int grp_in_wave = lane >> lgG, gl = lane & (G - 1);
+    const int grp_in_block = tid >> lgG;
+    int32_t* w3 = reinterpret_cast<int32_t*>(smem) + static_cast<size_t>(grp_in_block) * nd * 3;  // [nd][3]
+
+    const int64_t item = static_cast<int64_t>(blockIdx.x) * gpb + grp_in_block;  // (slot, td) flattened
+    const int64_t nitems = static_cast<int64_t>(*prm.qcount) * TD;
+    if (static_cast<int64_t>(blockIdx.x) * gpb >= nitems) return;                  // (uniform: the whole workgroup is past the list)
+    const bool in_range = item < nitems;
+    const int64_t slot = in_range ? item / TD : 0;
+    const int td = in_range ? static_cast<int>(item - slot * TD) : 0;
+    const int64_t at = static_cast<int64_t>(prm.qlist[slot]) * TD + td;            // the query's own (q, td) place
+    const RouteTable tb = prm.tables[td];
+    const int np = route_probe_table(prm, in_range, prm.codes + at * W, tb, G, gl, grp_in_wave, w3, probe_out + at * P);
+    if (in_range && gl == 0) nprobe_out[at] = np;
+}
+
 // ------------------------------------------------------------------------------------------
 // Kernel 2: stage ids, dedupe, Java order, select.  One workgroup per query.
 // ------------------------------------------------------------------------------------------

@@ -120,7 +120,8 @@ __device__ __forceinline__ int wave_cut1024(const int32_t* bins, int need, int l
 // and division by T*D*P below is an immediate; left to run time the kernel computes ~60 scalars in its prologue, keeps them for the
 // whole query and — beyond the 102 scalar registers it has — parks them in vector-register lanes (v_writelane / v_readlane).
 // The host launches the specialised build for BASELINE config #2 / #3's shape (16 tables x 5 probes, blocks of 64).
-template <int kThreads, int kEnt = kLzEntriesMax, bool kChk = true, int kTD = 0, int kP = 0>
+// kList (the retry pass of fspann_search_retry_dev): the queries are prm.qlist[0 .. *prm.qcount), slots q_first, q_first + q_stride, ...
+template <int kThreads, int kEnt = kLzEntriesMax, bool kChk = true, int kTD = 0, int kP = 0, bool kList = false>
 __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned char* smem, const int64_t q_first, const int64_t q_stride, const int block_id) {
     int4* probe_in = prm.probe_g;          // not __restrict__: a handed-over query's lists are written here and read back
     int32_t* nprobe_in = prm.nprobe_g;
@@ -265,7 +266,9 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
         }                                                                                                             \
     } while (0)
 
-    for (int64_t qi = q_first; qi < prm.nq; qi += q_stride) {
+    const int64_t nq_eff = kList ? static_cast<int64_t>(*prm.qcount) : prm.nq;
+    for (int64_t qs = q_first; qs < nq_eff; qs += q_stride) {
+        const int64_t qi = kList ? static_cast<int64_t>(prm.qlist[qs]) : qs;
         LZ_STAMP(0);
         // ---- probe list of this query; unused steps get an impossible partition and sort last ------------------
         if (prm.probe_G > 0) {
@@ -802,7 +805,7 @@ __device__ __forceinline__ void route_lazy_run(const RouteParams& prm, unsigned 
                 prm.ovf_list[atomicAdd(prm.ovf_count, 1)] = static_cast<int32_t>(qi);
             }
         }
-        if (qi + q_stride >= prm.nq) {   // last query of this workgroup: nothing to tidy up, the stores drain on their own
+        if (qs + q_stride >= nq_eff) {   // last query of this workgroup: nothing to tidy up, the stores drain on their own
             LZ_STAMP(6);
             LZ_STAMP(7);
             break;
@@ -829,6 +832,17 @@ __global__ __launch_bounds__(kThreads, (kEnt <= 512 ? (kTD > 0 ? 8 : 6) : (kEnt 
     if (prm.dbg && threadIdx.x == 0) prm.dbg[blockIdx.x * 16 + 9] = dbg_hw_where();   // (slot 9: free among the phase stamps)
 #endif
     route_lazy_run<kThreads, kEnt, kChk, kTD, kP>(prm, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), static_cast<int>(blockIdx.x));
+}
+
+// List mode of the bounded select (the retry pass): launched with the grid of prm.nq, a workgroup past *prm.qcount leaves at once.
+template <int kThreads, int kEnt, bool kChk>
+__global__ __launch_bounds__(kThreads, (kEnt <= 512 ? 6 : (kEnt <= 1024 ? 4 : 2))) void route_select_lazy_list_kernel(RouteParams prm) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    if (static_cast<int64_t>(blockIdx.x) >= static_cast<int64_t>(*prm.qcount)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *prm.ovf_next = 0;     // (route_lazy_run's duty: the next call's overflow counter)
+        return;
+    }
+    route_lazy_run<kThreads, kEnt, kChk, 0, 0, true>(prm, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), static_cast<int>(blockIdx.x));
 }
 
 }  // namespace fspann

@@ -408,6 +408,24 @@ class FspannContext:
                                                out_count_ptr, scored_ptr or None, sel_ids_ptr or None, sel_count_ptr or None,
                                                bad_ptr or None))
 
+    def search_retry_dev(self, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr=0,
+                         sel_ids_ptr=0, sel_count_ptr=0, bad_ptr=0, retried_ptr=0):
+        """search_store_dev plus QueryServiceImpl's adaptive retry (QSI:327-337): the short queries are searched again with 10
+        probes on the device, in stream order; retried [nq] (optional) says which did."""
+        N.check(self.L.fspann_search_retry_dev(self._h, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr,
+                                               out_count_ptr, scored_ptr or None, sel_ids_ptr or None, sel_count_ptr or None,
+                                               bad_ptr or None, retried_ptr or None))
+
+    def search_retry_finish_dev(self, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr=0,
+                                sel_ids_ptr=0, sel_count_ptr=0, bad_ptr=0, retried_ptr=0) -> int:
+        """Completes the preceding search_retry_dev call (same arguments): queries Route flagged in either pass are finished on
+        the host and scored, a short one flagged in pass 1 takes its pass 2.  Returns how many were finished on the host."""
+        done = C.c_int64(0)
+        N.check(self.L.fspann_search_retry_finish_dev(self._h, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr,
+                                                      out_count_ptr, scored_ptr or None, sel_ids_ptr or None, sel_count_ptr or None,
+                                                      bad_ptr or None, retried_ptr or None, C.byref(done)))
+        return int(done.value)
+
     def groundtruth_dev(self, n, base_ptr, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr=0):
         """Exact k-NN (GroundtruthPrecompute semantics) of device-resident fp32 base / query rows."""
         N.check(self.L.fspann_groundtruth_dev(self._h, n, base_ptr, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr or None))

@@ -112,7 +112,7 @@ class PointStore:
 class Pipeline:
     """Route of batch i+1 | AES-GCM open of batch i on `host_threads` threads | H2D + Refine of batch i-1."""
 
-    def __init__(self, ctx, store: PointStore, nq_max: int, B: int, k: int, host_threads: int = 0):
+    def __init__(self, ctx, store: PointStore, nq_max: int, B: int, k: int, host_threads: int = 0, retry: bool = False):
         self.L = N.lib()
         self.ctx, self.store, self.nq_max, self.B, self.k = ctx, store, nq_max, B, k
         self.threads = host_threads or (os.cpu_count() or 1)
@@ -120,6 +120,12 @@ class Pipeline:
         N.check(self.L.fspann_pipeline_create(ctx.handle, store.handle, nq_max, B, k, self.threads, C.byref(h)))
         self._h = h
         self.in_flight = 0
+        if retry:
+            self.set_retry(True)
+
+    def set_retry(self, on: bool):
+        """QueryServiceImpl's adaptive retry (QSI:327-337) for the batches submitted from now on; refused while batches are in flight."""
+        N.check(self.L.fspann_pipeline_set_retry(self._h, 1 if on else 0))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -152,4 +158,6 @@ class Pipeline:
     def stats(self):
         a, b, c, n = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)
         N.check(self.L.fspann_pipeline_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
-        return dict(route_ms=a.value, decrypt_ms=b.value, refine_ms=c.value, batches=int(n.value))
+        r, rm = C.c_int64(0), C.c_double(0)
+        N.check(self.L.fspann_pipeline_retry_stats(self._h, C.byref(r), C.byref(rm)))
+        return dict(route_ms=a.value, decrypt_ms=b.value, refine_ms=c.value, batches=int(n.value), retried=int(r.value), retry_ms=rm.value)

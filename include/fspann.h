@@ -262,7 +262,7 @@ int fspann_refine_store_dev(fspann_ctx* ctx, int64_t nq, const void* q_dev, int 
                             double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev);
 /* QueryServiceImpl.search (QSI:101-352) for a batch whose candidate rows are resident in the store: encode ->
  * route(limit = B, counters not produced) -> refine_store, enqueued in stream order by one call.  The adaptive
- * retry (QSI:327-337) stays with the caller (out_count / scored say when).  Optional outputs may be NULL:
+ * retry (QSI:327-337) is left to the caller (out_count / scored say when); fspann_search_retry_dev below runs it.  Optional outputs may be NULL:
  * scored, sel_ids [nq][B] + sel_count [nq] (= F_q), bad [nq] (1 = query held NaN/Inf, QueryTokenFactory rejects). */
 int fspann_search_store_dev(fspann_ctx* ctx, int64_t nq, const void* q_dev, int q_dtype, int probe_override, int64_t B,
                             int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev,
@@ -272,6 +272,24 @@ int fspann_search_store_dev(fspann_ctx* ctx, int64_t nq, const void* q_dev, int 
 int fspann_search_store_finish_dev(fspann_ctx* ctx, int64_t nq, const void* q_dev, int q_dtype, int probe_override, int64_t B, int k,
                                    int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev,
                                    int32_t* sel_ids_dev, int32_t* sel_count_dev, int64_t* resolved);
+/* QueryServiceImpl.search for a batch INCLUDING its adaptive retry (QSI:327-337), in stream order with no host synchronisation:
+ * pass 1 is exactly fspann_search_store_dev (same arguments, the caller's probe_override); a query retries iff it is not bad,
+ * its Route count is not -1, scored > 0 and (out_count < k || scored < 10 k) (QSI:444-447) — scored == 0 (QSI:293) and
+ * kept == 0 (QSI:159) return [] without a retry; pass 2 runs over those queries only with 10 probes (QSI:333), reusing pass 1's
+ * codes, and overwrites their rows of sel_ids / sel_count / out_ids / out_dist / out_count / scored in place (the second answer
+ * is returned even when it is worse or empty).  When pass 1 already ran at 10 effective probes, pass 2 would reproduce it:
+ * it is not run, the queries are still reported as retried.  retried_dev [nq] (optional): 1 = the query took the second pass.
+ * Other optional outputs as fspann_search_store_dev. */
+int fspann_search_retry_dev(fspann_ctx* ctx, int64_t nq, const void* q_dev, int q_dtype, int probe_override, int64_t B, int k,
+                            int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev,
+                            int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, int32_t* retried_dev);
+/* Completes the fspann_search_retry_dev call that precedes it on this context (same arguments): synchronises; a query Route
+ * flagged in pass 1 (count -1) is finished on the host with pass 1's probes, scored, and takes its pass 2 if it is short; a
+ * query flagged in pass 2 is finished with 10 probes and scored.  *resolved = queries finished on the host. */
+int fspann_search_retry_finish_dev(fspann_ctx* ctx, int64_t nq, const void* q_dev, int q_dtype, int probe_override, int64_t B, int k,
+                                   int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev,
+                                   int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, int32_t* retried_dev,
+                                   int64_t* resolved);
 const void* fspann_store_dev_ptr(fspann_ctx* ctx, int* dtype);
 
 /* ---- one launch for three stages of three batches in flight --------------------------------------------------------------
@@ -379,6 +397,14 @@ int fspann_pipeline_create(fspann_ctx* ctx, fspann_pointstore* ps, int64_t nq_ma
 int fspann_pipeline_submit(fspann_pipeline* p, int64_t nq, const float* q_host, uint64_t* ticket);
 int fspann_pipeline_collect(fspann_pipeline* p, uint64_t* ticket, int64_t* nq, int32_t* out_ids, double* out_dist, int32_t* out_count);
 int fspann_pipeline_stats(fspann_pipeline* p, double* route_ms, double* decrypt_ms, double* refine_ms, int64_t* batches);
+/* QSI's adaptive retry in the pipeline (QSI:327-337, 444-447; off by default, then results are those of the pass alone).  On:
+ * after a batch's refine, the same pick as fspann_search_retry_dev (QSI:159, 293: empty lists are not retried); list-mode Route
+ * with 10 probes for the short queries only, only their F_q opened with fspann_pointstore_open_batch, their rows copied up and
+ * scored again in place.  A query flagged by Route (count -1) is finished by the host model in either pass.  Refused with
+ * FSPANN_E_STATE while batches are in flight (submitted, not collected).  Batches still complete in submission order. */
+int fspann_pipeline_set_retry(fspann_pipeline* p, int on);
+/* Queries that took the retry's second pass since the pipeline was created, and the mean time per batch spent in it. */
+int fspann_pipeline_retry_stats(fspann_pipeline* p, int64_t* retried, double* retry_ms);
 void fspann_pipeline_destroy(fspann_pipeline* p);
 
 /* ---- multi-GPU merge ---------------------------------------------------------

@@ -25,6 +25,7 @@ OUT = {
     ("fspann_pipeline_submit", "ticket"): "long", ("fspann_pipeline_collect", "ticket"): "long", ("fspann_pipeline_collect", "nq"): "long",
     ("fspann_pipeline_stats", "route_ms"): "double", ("fspann_pipeline_stats", "decrypt_ms"): "double",
     ("fspann_pipeline_stats", "refine_ms"): "double", ("fspann_pipeline_stats", "batches"): "long",
+    ("fspann_pipeline_retry_stats", "retried"): "long", ("fspann_pipeline_retry_stats", "retry_ms"): "double",
     ("fspann_comm_info", "world"): "int", ("fspann_comm_info", "rank"): "int",
     ("fspann_hbm_read_peak", "gb_per_s"): "double",
     ("fspann_hbm_read_window", "gb_per_s"): "double",

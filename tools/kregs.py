@@ -19,15 +19,22 @@ def kernels(so=SO):
         subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", os.path.join(td, "lib.so")], check=True, capture_output=True, cwd=td)
         obj = [f for f in os.listdir(td) if "gfx950" in f][0]
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", os.path.join(td, obj)], check=True, capture_output=True, text=True).stdout
-    out, cur = {}, None
+    # one kernel's map per "  - " item of amdhsa.kernels; its keys are sorted, so .group_segment_fixed_size comes before .name
+    out, blk = {}, {}
+    def commit():
+        if "name" in blk:
+            out[blk.pop("name")] = dict(blk)
+        blk.clear()
     for line in notes.splitlines():
+        if re.match(r"^  - ", line):
+            commit()
         m = re.search(r"\.name:\s+(\S+)", line)
         if m:
-            cur = m.group(1)
-            out.setdefault(cur, {})
+            blk["name"] = m.group(1)
         m = re.search(r"\.(private_segment_fixed_size|vgpr_count|sgpr_count|agpr_count|group_segment_fixed_size):\s+(\d+)", line)
-        if m and cur:
-            out[cur][m.group(1)] = int(m.group(2))
+        if m:
+            blk[m.group(1)] = int(m.group(2))
+    commit()
     names = [k for k in out if k.startswith("_Z")]
     dem = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.splitlines()
     return {d: out[n] for n, d in zip(names, dem)}

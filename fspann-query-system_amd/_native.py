@@ -150,6 +150,9 @@ _SIGS = {
     "fspann_store_attach_dev": (_i, [_vp, _i64, _vp, _i]),
     "fspann_store_gather_dev": (_i, [_vp, _i64, _vp, _vp, _i64, _vp]),
     "fspann_store_dev_ptr": (_vp, [_vp, C.POINTER(_i)]),
+    "fspann_touch_enable": (_i, [_vp, _i]),
+    "fspann_touch_count": (_i, [_vp, C.POINTER(_i64)]),
+    "fspann_touch_drain": (_i, [_vp, _vp, _i64, C.POINTER(_i64), _i]),
     "fspann_route_handover_bytes": (_sz, [_vp, _i64, _i]),
     "fspann_tick_dev": (_i, [_vp, C.POINTER(Tick)]),
     "fspann_last_tick_fused": (_i, [_vp]),

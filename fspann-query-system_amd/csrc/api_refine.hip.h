@@ -167,9 +167,13 @@ int launch_refine_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int6
                     int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
     constexpr int DC0 = (sizeof(TC) == 4) ? 32 : 16;
     const int dc_env = c->knob_refine_dc;
-    if (dc_env == DC0 * 2) return launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    if (dc_env == DC0 * 4) return launch_refine_dc<TC, TQ, DC0 * 4, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    return launch_refine_dc<TC, TQ, DC0, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    int rc;
+    if (dc_env == DC0 * 2) rc = launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    else if (dc_env == DC0 * 4) rc = launch_refine_dc<TC, TQ, DC0 * 4, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    else rc = launch_refine_dc<TC, TQ, DC0, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    if (rc) return rc;
+    // the touched-record set (api_touch.hip.h): the rows this launch scores, marked behind it (nothing while tracking is off)
+    return touch_mark<TC, TQ, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, qlist, qcount);
 }
 
 // fspann_refine_store_dev over the queries qlist[0 .. *qcount) only (device list; the retry pass and its host finish).
@@ -328,6 +332,7 @@ int fspann_store_set(fspann_ctx* c, int64_t n, const void* vectors, int dtype) {
     FSP_HIP(hipMemcpy(c->d_store, vectors, bytes, hipMemcpyHostToDevice));
     c->store_dtype = dtype;
     c->store_n = n;
+    c->store_gen++;
     return FSPANN_OK;
 }
 
@@ -346,6 +351,7 @@ int fspann_store_attach_dev(fspann_ctx* c, int64_t n, const void* vectors_dev, i
     c->store_owned = false;
     c->store_dtype = dtype;
     c->store_n = n;
+    c->store_gen++;
     return FSPANN_OK;
 }
 

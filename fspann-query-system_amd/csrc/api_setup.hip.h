@@ -354,6 +354,8 @@ void fspann_ctx_destroy(fspann_ctx* c) {
     free_devt(c->d_tables); free_devt(c->d_recs); free_devt(c->d_ids); free_devt(c->d_dir);
     free_devt(c->d_java_hash); free_devt(c->d_unmodelled);
     if (uint32_t* db = c->d_deleted_bits.exchange(nullptr)) (void)hipFree(db);
+    if (uint8_t* ts = c->d_touch.exchange(nullptr)) (void)hipFree(ts);
+    free_dev(c->store_ok.p); free_dev(c->ws_touch.p);
     if (c->store_owned) free_dev(c->d_store);
     free_dev(c->ws_tickfix.p); free_dev(c->d_fixparams); free_dev(c->ws_gt.p); free_dev(c->bld_codes.p);
     free_dev(c->ws_route.p); free_dev(c->ws_refine.p); free_dev(c->ws_probe.p); free_dev(c->ws_ovf.p); free_dev(c->ws_search.p); free_dev(c->ws_retry.p); free_devt(c->d_inv); free_devt(c->d_ids_bk); free_devt(c->d_bin16);
@@ -601,6 +603,13 @@ int fspann_set_id_meta(fspann_ctx* c, int64_t n_ids, const int32_t* java_hash, c
     c->meta_epoch++;             // d_inv / d_ids_bk were built for the previous hashes: the bounded select waits for the next finalize
     c->dev_index_dirty = true;
     c->n_ids = n_ids;
+    {   // a touched set in use follows the new handle count, cleared (no clone is alive here: CHECK_UNSHARED)
+        std::lock_guard<std::mutex> tl(c->touch_mu);
+        if (c->d_touch.load(std::memory_order_acquire) && c->touch_n != n_ids) {
+            int rc = touch_alloc(c, c);
+            if (rc) return rc;
+        }
+    }
     return FSPANN_OK;
     });
 }

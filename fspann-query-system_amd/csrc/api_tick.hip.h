@@ -263,7 +263,15 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
             hipLaunchKernelGGL(fk, dim3(static_cast<unsigned>(total)), dim3(kTickThreads), lds, c->stream, p, eaT, routeT);
         }
         FSP_HIP(hipGetLastError());
-    } else if ((rc = gather ? launch(tick_kernel<true>, 128u) : launch(tick_kernel<false>, 256u))) return rc;
+    } else {
+        if ((rc = gather ? launch(tick_kernel<true>, 128u) : launch(tick_kernel<false>, 256u))) return rc;
+        // the refine role's rows, from F_q as the tick leaves it (PENDING queries finished); the stand-alone paths above mark
+        // inside their refine calls
+        if (F && (rc = gather ? touch_mark<float, float, true>(c, t->nq_refine, static_cast<const float*>(t->ref_q_dev), static_cast<const float*>(rows),
+                                                                t->ref_B, t->ref_ids_dev, t->ref_count_dev)
+                              : touch_mark<float, float, false>(c, t->nq_refine, static_cast<const float*>(t->ref_q_dev), static_cast<const float*>(rows),
+                                                                 t->ref_B, t->ref_ids_dev, t->ref_count_dev))) return rc;
+    }
     if (R && !t->route_handover_dev) {
         // no buffer travels with the batch: queries the bounded select handed over are finished now (normally none)
         RouteParams q2 = pR;

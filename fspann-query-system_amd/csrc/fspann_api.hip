@@ -20,11 +20,13 @@
 #include "route.hip.h"
 #include "route_lazy.hip.h"
 #include "tick.hip.h"
+#include "touch.hip.h"
 #include "../host/route_replay.hpp"
 
 
 // The entry points, by stage (one translation unit: the kernels above are templates shared by several of them).
 #include "api_common.hip.h"
+#include "api_touch.hip.h"
 #include "api_encode.hip.h"
 #include "api_setup.hip.h"
 #include "api_route.hip.h"

@@ -172,12 +172,24 @@ struct fspann_ctx {
     std::mutex deleted_mu;
     std::vector<int32_t> h_java_hash;
     bool decimal_ids = false;  // ids are Long.toString(handle): String.hashCode computed in-kernel
+    // touched-record set of selective re-encryption (api_touch.hip.h): one byte per handle, whole kTouchTile tiles (padding zero).
+    // Owned by the index owner like the deleted bits; the owner and all its clones mark into it.  Allocated / reallocated under
+    // touch_mu, and published before touch_on: a context that sees touch_on sees the set.  Count and drain hold touch_mu.
+    std::mutex touch_mu;
+    std::atomic<uint8_t*> d_touch{nullptr};
+    int64_t touch_n = 0;             // handles the set covers (n_ids when it was allocated)
+    size_t touch_bytes = 0;
+    std::atomic<bool> touch_on{false};
 
     // plaintext store (test / bench harness)
     void* d_store = nullptr;
     bool store_owned = false;        // false: rows attached from caller-owned device memory (fspann_store_attach_dev)
     int store_dtype = FSPANN_F32;
     int64_t store_n = 0;
+    unsigned store_gen = 1;          // bumped by fspann_store_set / fspann_store_attach_dev
+    unsigned store_ok_gen = 0;       // store_gen that store_ok was computed for (0: none)
+    fspann::DevBuf store_ok;         // per store row: 1 = all dim values finite (api_touch.hip.h, computed at the first mark)
+    fspann::DevBuf ws_touch;         // tile counts / offsets / total / handles of fspann_touch_count / _drain
 
     // scratch arenas (grown on demand, reused across calls)
     fspann::DevBuf ws_route;   // global hash/sort fallback for the route kernel

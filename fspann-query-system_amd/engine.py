@@ -231,6 +231,28 @@ class FspannContext:
         N.check(self.L.fspann_unmodelled_queries(self._h, C.byref(v), 1 if reset else 0))
         return int(v.value)
 
+    # -- touched records (selective re-encryption) ---------------------------------------------------
+    def touch_enable(self, on=True):
+        """Start (or stop) marking the records every Refine of this index family scores (fspann_touch_enable); the set
+        belongs to the index owner and is shared by its clones."""
+        N.check(self.L.fspann_touch_enable(self._h, 1 if on else 0))
+
+    def touched_count(self) -> int:
+        """ReencryptionTracker.uniqueCount(): touched handles (synchronises this context's stream)."""
+        v = C.c_int64(0)
+        N.check(self.L.fspann_touch_count(self._h, C.byref(v)))
+        return int(v.value)
+
+    def drain_touched(self, reset=True, cap=None) -> np.ndarray:
+        """ReencryptionTracker.drainTouchedIds(): the touched handles, ascending (int32).  cap bounds how many are returned (the
+        smallest); reset clears exactly those returned.  cap None: all of them, sized from a count."""
+        if cap is None:
+            cap = self.touched_count()
+        out = np.empty(max(int(cap), 1), np.int32)
+        n = C.c_int64(0)
+        N.check(self.L.fspann_touch_drain(self._h, out.ctypes.data_as(C.c_void_p), int(cap), C.byref(n), 1 if reset else 0))
+        return out[:min(int(cap), int(n.value))].copy()
+
     def route_max_candidates(self, probe_override=-1):
         return int(self.L.fspann_route_max_candidates(self._h, probe_override))
 

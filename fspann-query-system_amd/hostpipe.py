@@ -161,3 +161,18 @@ class Pipeline:
         r, rm = C.c_int64(0), C.c_double(0)
         N.check(self.L.fspann_pipeline_retry_stats(self._h, C.byref(r), C.byref(rm)))
         return dict(route_ms=a.value, decrypt_ms=b.value, refine_ms=c.value, batches=int(n.value), retried=int(r.value), retry_ms=rm.value)
+
+
+def reencrypt_touched(ctx, store: PointStore, threads: int = 1):
+    """SelectiveReencCoordinator.runSelective (keymanagement/.../KeyRotationServiceImpl.java:215-289 over
+    ReencryptionTracker.drainTouchedIds): drains the context family's touched set (fspann_touch_drain, reset) and moves exactly
+    those records to the store's current key version.  Returns (touched, reencrypted, already_current).
+    Like the reference's copy-then-clear drain, the handles leave the set BEFORE their records are re-encrypted: when
+    PointStore.reencrypt raises, the exception carries them as `touched_handles`, and the caller retries those."""
+    handles = ctx.drain_touched(reset=True)
+    try:
+        done = store.reencrypt(handles, threads) if len(handles) else 0
+    except Exception as e:
+        e.touched_handles = handles
+        raise
+    return len(handles), done, len(handles) - done

@@ -671,3 +671,26 @@ class QueryServiceImpl:
         if self.tokenFactory is None:
             raise N.FspannStateError("QueryTokenFactory not available")
         return self.tokenFactory.derive(base, k)
+
+
+# --------------------------------------------------------------------------------------
+# ReencryptionTracker — the touched set, kept on the device (crypto/.../ReencryptionTracker.java:23-45)
+# --------------------------------------------------------------------------------------
+class DeviceReencryptionTracker:
+    """ReencryptionTracker whose set is the context family's touched-record set (fspann_touch_*): every Refine the library runs
+    marks the rows it scores, so record() has nothing left to do and is accepted as a no-op (setReencryptionTracker takes this
+    object).  idOf maps a handle to its id string (PartitionedIndexService.idOf; default: the decimal handle)."""
+
+    def __init__(self, ctx: FspannContext, idOf=None):
+        self.ctx = ctx
+        self.idOf = idOf or str
+        ctx.touch_enable(True)
+
+    def record(self, ids):  # QSI:348-349 — the device marked them already
+        pass
+
+    def uniqueCount(self) -> int:
+        return self.ctx.touched_count()
+
+    def drainTouchedIds(self) -> set:  # ReencryptionTracker.java:35-41: copy, then clear
+        return {self.idOf(int(h)) for h in self.ctx.drain_touched(reset=True)}

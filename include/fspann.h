@@ -292,6 +292,30 @@ int fspann_search_retry_finish_dev(fspann_ctx* ctx, int64_t nq, const void* q_de
                                    int64_t* resolved);
 const void* fspann_store_dev_ptr(fspann_ctx* ctx, int* dtype);
 
+/* ---- touched records: ReencryptionTracker (selective re-encryption) --------------------------------------------------------
+ * Replaces QSI's touchedThisSession (cleared per token at QSI:120, one id added per candidate scored at QSI:263, handed to
+ * ReencryptionTracker.record at QSI:348-349) and the tracker itself (crypto/.../ReencryptionTracker.java:23-45), which
+ * ForwardSecureANNSystem.runSelectiveReencryptionIfNeeded drains after the query loop (FSA:1739-1804).  While tracking is on, every
+ * Refine of fspann_refine[_dev], fspann_refine_store[_dev], fspann_search_store_dev / _finish_dev, fspann_search_retry_dev /
+ * _finish_dev (both passes), fspann_tick_dev (its refine part) and the native pipeline (stage C and its retry pass) marks the rows it
+ * counts in `scored` (QSI.lastCandDecrypted): row j < count of a query whose count is >= 0 and whose vector is finite, that loaded
+ * (store: 0 <= id < store_n; caller rows: present) and is finite.  Marks are separate kernels enqueued behind the Refine they mirror:
+ * no host synchronisation, and every other output stays bit-identical.  Handles outside [0, n_ids) are never marked.
+ * One set per index family (like the deleted bits): the owner and its clones mark into it, and any of them may enable, count or
+ * drain.  Count and drain synchronise the calling context's stream: they include every mark enqueued on it and every mark of another
+ * context of the family that the caller has synchronised.  A mark racing a resetting drain lands in that drain or in the next one,
+ * never in neither (the reference's copy-then-clear drainTouchedIds gives no more).  Count and drain of one family are serialised.
+ *   enable: on != 0 allocates the set (zeroed, n_ids entries) on first use, or again when n_ids changed; off stops marking and keeps
+ *           the set.  fspann_set_id_meta with a different n_ids (fspann_index_load included) reallocates and clears it.  Replacing
+ *           a set is refused (FSPANN_E_STATE) while clones are alive; when it fails, the previous set stays in use.
+ *   count:  *unique = touched handles (ReencryptionTracker.uniqueCount()).
+ *   drain:  drainTouchedIds(): writes the min(*n, cap) SMALLEST touched handles into the host buffer, ascending; *n = touched count
+ *           before the call; reset != 0 clears exactly the handles written (a short buffer loses nothing: call again).
+ * FSPANN_E_STATE from count / drain before tracking was ever enabled.                                                       */
+int fspann_touch_enable(fspann_ctx* ctx, int on);
+int fspann_touch_count(fspann_ctx* ctx, int64_t* unique);
+int fspann_touch_drain(fspann_ctx* ctx, int32_t* handles, int64_t cap, int64_t* n, int reset);
+
 /* ---- one launch for three stages of three batches in flight --------------------------------------------------------------
  * The stages of ONE batch depend on each other (QSI:101-352 runs them in sequence), but a serving loop keeps batches in
  * flight — in production the host loads + decrypts batch t's candidates (PIS:717-724, AesGcmCryptoService.java:126-166)

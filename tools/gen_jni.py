@@ -19,6 +19,7 @@ OUT = {
     ("fspann_unmodelled_queries", "total"): "long",
     ("fspann_refine_timing_end", "launches"): "int", ("fspann_refine_timing_end", "total_ms"): "double",
     ("fspann_store_dev_ptr", "dtype"): "int",
+    ("fspann_touch_count", "unique"): "long", ("fspann_touch_drain", "n"): "long",
     ("fspann_pointstore_rotate", "new_version"): "int", ("fspann_pointstore_reencrypt", "reencrypted"): "long",
     ("fspann_pointstore_get_record", "version"): "int",
     ("fspann_pointstore_stats", "opened"): "long", ("fspann_pointstore_stats", "failed"): "long",

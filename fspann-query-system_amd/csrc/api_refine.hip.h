@@ -118,6 +118,22 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
                 c->refine_fix_used = true;
             }
         }
+        if constexpr (std::is_same<TC, uint8_t>::value && std::is_same<TQ, float>::value && DC == 128) {
+            if (c->refine_fix_dev && nchunks == 1) {
+                // FSPANN_U8 rows: the same hand-over, the kernel with the row type as a template parameter
+                auto fk = refine_stream_fix_kernel<uint8_t, GATHER>;
+                const size_t flds = std::max(lds, c->refine_fix_lds);
+                const unsigned abit = GATHER ? (1u << 24) : (1u << 25);
+                if (!(c->attr_mask & abit)) {
+                    FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
+                    c->attr_mask |= abit;
+                }
+                if (timed) hipExtLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ev0, ev1, 0, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
+                else hipLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
+                fixed = true;
+                c->refine_fix_used = true;
+            }
+        }
         if (!fixed) {
             if constexpr (!GATHER) {
                 if (npieces > 0) {
@@ -168,7 +184,9 @@ int launch_refine_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int6
     constexpr int DC0 = (sizeof(TC) == 4) ? 32 : 16;
     const int dc_env = c->knob_refine_dc;
     int rc;
-    if (dc_env == DC0 * 2) rc = launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    // FSPANN_U8 rows: a tile is 128 bytes = 128 dims; FSPANN_REFINE_DC (32 / 64 / 128 dims) is an fp32 notion and is ignored
+    if constexpr (std::is_same<TC, uint8_t>::value) rc = launch_refine_dc<TC, TQ, 128, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    else if (dc_env == DC0 * 2) rc = launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
     else if (dc_env == DC0 * 4) rc = launch_refine_dc<TC, TQ, DC0 * 4, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
     else rc = launch_refine_dc<TC, TQ, DC0, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
     if (rc) return rc;
@@ -187,7 +205,10 @@ int refine_store_list(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
     if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F64) FSP_REF(float, double);
     if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F32) FSP_REF(double, float);
     if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F64) FSP_REF(double, double);
+    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F32) FSP_REF(uint8_t, float);
+    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F64) FSP_REF(uint8_t, double);
 #undef FSP_REF
+    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     return fail(FSPANN_E_ARG, "unknown dtype");
 }
 
@@ -214,7 +235,10 @@ int fspann_refine_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
     if (cand_dtype == FSPANN_F32 && q_dtype == FSPANN_F64) FSP_REF(float, double);
     if (cand_dtype == FSPANN_F64 && q_dtype == FSPANN_F32) FSP_REF(double, float);
     if (cand_dtype == FSPANN_F64 && q_dtype == FSPANN_F64) FSP_REF(double, double);
+    if (cand_dtype == FSPANN_U8 && q_dtype == FSPANN_F32) FSP_REF(uint8_t, float);
+    if (cand_dtype == FSPANN_U8 && q_dtype == FSPANN_F64) FSP_REF(uint8_t, double);
 #undef FSP_REF
+    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     return fail(FSPANN_E_ARG, "unknown dtype");
 }
 
@@ -226,6 +250,7 @@ int fspann_refine(fspann_ctx* c, int64_t nq, const void* q, const void* cand, in
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
     if (!q || !cand || !cand_ids || !cand_count || !out_ids || !out_dist || !out_count) return fail(FSPANN_E_NULL, "refine buffer is null");
+    if (dtype == FSPANN_U8) return fail(FSPANN_E_ARG, "dtype FSPANN_U8: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (byte rows: fspann_refine_dev)");
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     const size_t esz = dtype == FSPANN_F64 ? 8 : 4;
     const int d = c->cfg.dim;
@@ -321,8 +346,8 @@ int fspann_store_set(fspann_ctx* c, int64_t n, const void* vectors, int dtype) {
     if (c->share_children.load() > 0) return fail(FSPANN_E_STATE, "the store is shared with %d clone(s): destroy them first", c->share_children.load());
     if (!vectors) return fail(FSPANN_E_NULL, "vectors is null");
     if (n <= 0) return fail(FSPANN_E_ARG, "n <= 0");
-    if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
-    const size_t bytes = static_cast<size_t>(n) * c->cfg.dim * (dtype == FSPANN_F64 ? 8 : 4);
+    if (dtype != FSPANN_F32 && dtype != FSPANN_F64 && dtype != FSPANN_U8) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
+    const size_t bytes = static_cast<size_t>(n) * c->cfg.dim * dtype_size(dtype);
     FSP_HIP(hipStreamSynchronize(c->stream));
     if (c->store_owned) free_dev(c->d_store);
     c->d_store = nullptr;
@@ -343,7 +368,7 @@ int fspann_store_attach_dev(fspann_ctx* c, int64_t n, const void* vectors_dev, i
     if (c->share_children.load() > 0) return fail(FSPANN_E_STATE, "the store is shared with %d clone(s): destroy them first", c->share_children.load());
     if (!vectors_dev) return fail(FSPANN_E_NULL, "vectors is null");
     if (n <= 0) return fail(FSPANN_E_ARG, "n <= 0");
-    if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
+    if (dtype != FSPANN_F32 && dtype != FSPANN_F64 && dtype != FSPANN_U8) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     if (reinterpret_cast<uintptr_t>(vectors_dev) & 15) return fail(FSPANN_E_ARG, "store rows must be 16-byte aligned");
     FSP_HIP(hipStreamSynchronize(c->stream));
     if (c->store_owned) free_dev(c->d_store);
@@ -375,7 +400,10 @@ int fspann_refine_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F64) FSP_REF(float, double);
     if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F32) FSP_REF(double, float);
     if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F64) FSP_REF(double, double);
+    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F32) FSP_REF(uint8_t, float);
+    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F64) FSP_REF(uint8_t, double);
 #undef FSP_REF
+    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     return fail(FSPANN_E_ARG, "unknown dtype");
 }
 
@@ -388,7 +416,7 @@ int fspann_refine_store(fspann_ctx* c, int64_t nq, const void* q, int q_dtype, i
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
     if (!q || !cand_ids || !cand_count || !out_ids || !out_dist || !out_count) return fail(FSPANN_E_NULL, "refine buffer is null");
-    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", q_dtype);
+    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * (q_dtype == FSPANN_F64 ? 8 : 4);
     const size_t ib = static_cast<size_t>(nq) * B * 4, nb = static_cast<size_t>(nq) * 4;
     const size_t ob_i = static_cast<size_t>(nq) * k * 4, ob_d = static_cast<size_t>(nq) * k * 8;
@@ -458,6 +486,10 @@ int fspann_store_gather_dev(fspann_ctx* c, int64_t nq, const int32_t* sel_ids_de
         const int vec_ok = (d % 4 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
         hipLaunchKernelGGL(store_gather_kernel<float>, dim3(grid), dim3(256), 0, c->stream, static_cast<const float*>(c->d_store), d,
                            sel_ids_dev, sel_count_dev, B, nq, static_cast<float*>(cand_dev), vec_ok);
+    } else if (c->store_dtype == FSPANN_U8) {
+        const int vec_ok = (d % 16 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
+        hipLaunchKernelGGL(store_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, c->stream, static_cast<const uint8_t*>(c->d_store), d,
+                           sel_ids_dev, sel_count_dev, B, nq, static_cast<uint8_t*>(cand_dev), vec_ok);
     } else {
         const int vec_ok = (d % 2 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
         hipLaunchKernelGGL(store_gather_kernel<double>, dim3(grid), dim3(256), 0, c->stream, static_cast<const double*>(c->d_store), d,

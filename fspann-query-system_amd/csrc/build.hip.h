@@ -21,6 +21,19 @@ constexpr int kRsRounds = 8;                                   // 64-item rounds
 constexpr int kRsTile = kRsThreads * kRsRounds;                // items per workgroup
 constexpr int kRsWaves = kRsThreads / 64;
 
+// Setup input as bytes (FSPANN_U8: the integers 0..255): widened to fp32 on the device, exactly, four elements per thread; the
+// encode kernels then see what an F32 build would have uploaded.
+__global__ __launch_bounds__(256) void build_widen_u8_kernel(const uint8_t* __restrict__ in, int64_t n, float* __restrict__ out) {
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (i + 4 <= n) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(in + i);
+        *reinterpret_cast<float4*>(out + i) = make_float4(static_cast<float>(w & 0xFFu), static_cast<float>((w >> 8) & 0xFFu),
+                                                          static_cast<float>((w >> 16) & 0xFFu), static_cast<float>(w >> 24));
+    } else {
+        for (int64_t j = i; j < n; j++) out[j] = static_cast<float>(in[j]);
+    }
+}
+
 __global__ __launch_bounds__(kRsThreads) void rs_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
                                                              int nblocks, uint32_t* __restrict__ tot) {
     __shared__ uint32_t h[256];

@@ -43,6 +43,9 @@ inline int fail(int code, const char* fmt, ...) {
                                   __LINE__);                                                       \
     } while (0)
 
+// bytes per element of a dtype of include/fspann.h (the callers have checked which dtypes they take)
+inline size_t dtype_size(int dtype) { return dtype == FSPANN_F64 ? 8 : (dtype == FSPANN_U8 ? 1 : 4); }
+
 // ---- order-key bit budget (DESIGN.md "Java order key") ----------------------------
 // key = score(10) | bucket(20) | seq(22); seq = (td*P + step)*S + pos is unique per tuple.
 constexpr int kSeqBits = 22;

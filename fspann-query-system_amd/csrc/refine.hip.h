@@ -43,6 +43,12 @@ typedef float fsp_f32x4 __attribute__((ext_vector_type(4)));
 typedef double fsp_f64x2 __attribute__((ext_vector_type(2)));
 template <> struct VecOf<float> { using type = fsp_f32x4; static constexpr int N = 4; };
 template <> struct VecOf<double> { using type = fsp_f64x2; static constexpr int N = 2; };
+// FSPANN_U8 rows: a 16-byte slot is 16 elements, held as four dwords (byte e of the slot = bits [8 (e % 4), 8 (e % 4) + 8) of
+// dword e / 4); a row element is the integer 0..255, always finite.
+typedef uint32_t fsp_u32x4 __attribute__((ext_vector_type(4)));
+template <> struct VecOf<uint8_t> { using type = fsp_u32x4; static constexpr int N = 16; };
+template <typename T> struct RowIsBytes { static constexpr bool value = false; };
+template <> struct RowIsBytes<uint8_t> { static constexpr bool value = true; };
 
 template <typename T> __device__ __forceinline__ bool finite_t(T x) {
     return fabs(static_cast<double>(x)) <= 1.79769313486231570815e+308;
@@ -50,6 +56,11 @@ template <typename T> __device__ __forceinline__ bool finite_t(T x) {
 
 __device__ __forceinline__ double vcomp(fsp_f32x4 v, int e) { return static_cast<double>(v[e]); }
 __device__ __forceinline__ double vcomp(fsp_f64x2 v, int e) { return v[e]; }
+// Exact widening of byte e of a slot (e is a constant after unrolling): a bit-field extract and v_cvt_f64_u32.  Measured against
+// v_cvt_f32_ubyte0..3 + v_cvt_f64_f32, against building 2^52 + byte in the mantissa and subtracting 2^52 (no conversion at all),
+// and against keeping the query's tile as fp64 in LDS instead of converting it per element: within 5 % of each other
+//  — every vector instruction of this loop issues at the same rate, so the plain expression stays.
+__device__ __forceinline__ double vcomp(fsp_u32x4 v, int e) { return static_cast<double>((v[e >> 2] >> (8 * (e & 3))) & 0xFFu); }
 
 constexpr int kRefFilterMaxK = 32;   // top-k via per-wave k-th-smallest filter up to this k
 
@@ -521,7 +532,7 @@ __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, u
                     for (int e = 0; e < VN; e += 2) {
                         const double q0 = static_cast<double>(qrow[c0 + kk + e]);      // uniform address -> scalar load
                         const double q1 = static_cast<double>(qrow[c0 + kk + e + 1]);
-                        ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]);   // v_cmp_class on the raw element
+                        if constexpr (!RowIsBytes<TC>::value) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]);   // v_cmp_class on the raw element (a byte is always finite)
                         const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   // exact widening
                         const double d0 = q0 - x0;                               // QSI.java:368
                         const double p0 = d0 * d0;
@@ -594,7 +605,11 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     // fp32 rows against an fp32 query: |q - x| < 2^129, so the fp64 sum of squares cannot overflow, and a NaN or an infinity
     // in the row always reaches the sum — "every element finite" (QSI.isValid, QSI:407-413) is "the sum is finite", one test
     // per row instead of one per element (a sixth of the scan's vector instructions).
-    constexpr bool kSumTellsFinite = (sizeof(TC) == 4 && sizeof(TQ) == 4);
+    // Byte rows (FSPANN_U8) are always finite, so no row element is ever tested; against an fp32 query the sum tells about the
+    // QUERY in the same way (|q - x| < 2^129 again).  Against an fp64 query it does not (1e200 squared overflows with every element
+    // finite): there the per-query check stays, and such a row is scored with distance +inf as the reference scores it.
+    constexpr bool kByteRows = RowIsBytes<TC>::value;
+    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows) && sizeof(TQ) == 4);
     const TC* __restrict__ cand = a.cand;
     const int64_t store_n = a.store_n, B = a.B;
     const int d = a.d, nchunks = a.nchunks;
@@ -795,7 +810,7 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
                     _Pragma("unroll") for (int e = 0; e < VN; e += 2) {                                             \
                         const double q0 = static_cast<double>(qrow[(C0) + kk + e]);      /* uniform address -> scalar load */ \
                         const double q1 = static_cast<double>(qrow[(C0) + kk + e + 1]);                             \
-                        if constexpr (!kSumTellsFinite) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]); \
+                        if constexpr (!kSumTellsFinite && !kByteRows) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]); \
                         const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   /* exact widening */                \
                         const double d0 = q0 - x0;                               /* QSI.java:368 */                  \
                         const double p0 = d0 * d0;                                                                  \

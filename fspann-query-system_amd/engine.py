@@ -51,6 +51,8 @@ def _dt(a):
         return N.F32
     if a.dtype == np.float64:
         return N.F64
+    if a.dtype == np.uint8:     # rows only (FSPANN_U8): the library refuses it wherever a query dtype is given
+        return N.U8
     raise N.FspannArgumentError(f"unsupported dtype {a.dtype}")
 
 
@@ -144,8 +146,9 @@ class FspannContext:
         N.check(self.L.fspann_finalize(self._h))
 
     def build_index(self, vectors, order=None):
+        """A uint8 array goes to the library as bytes (FSPANN_U8: widened on the device; same tables, a quarter of the traffic)."""
         v = np.ascontiguousarray(vectors)
-        if v.dtype not in (np.float32, np.float64):
+        if v.dtype not in (np.float32, np.float64, np.uint8):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
         o = None if order is None else _c(order, np.int32)
@@ -157,7 +160,7 @@ class FspannContext:
 
     def build_append(self, rows):
         v = np.ascontiguousarray(rows)
-        if v.dtype not in (np.float32, np.float64):
+        if v.dtype not in (np.float32, np.float64, np.uint8):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
         N.check(self.L.fspann_build_append(self._h, v.shape[0], _p(v), _dt(v)))
@@ -373,16 +376,30 @@ class FspannContext:
         return dict(ids=out_ids, dist=out_dist, count=out_count, scored=scored)
 
     # -- plaintext store (test / bench harness) --------------------------------------
-    def store_set(self, vectors):
+    def store_set(self, vectors, dtype=None):
+        """dtype=np.uint8 keeps the rows as bytes (FSPANN_U8): only for data whose values are the integers 0..255 (a uint8
+        array, or an array holding nothing else), where a byte is exactly what the reference's double[] holds.  Without it a
+        uint8 array is widened to float64 like every other non-float array."""
         v = np.ascontiguousarray(vectors)
-        if v.dtype not in (np.float32, np.float64):
+        if dtype is not None and np.dtype(dtype) == np.uint8:
+            if v.dtype != np.uint8:
+                with np.errstate(invalid="ignore"):
+                    exact = bool(np.all((v >= 0) & (v <= 255) & (v == np.floor(v))))
+                if not exact:
+                    raise N.FspannArgumentError("store_set(dtype=uint8): every value must be an integer in 0..255")
+                v = v.astype(np.uint8)
+        elif dtype is not None:
+            v = v.astype(np.dtype(dtype))
+            if v.dtype not in (np.float32, np.float64):
+                raise N.FspannArgumentError(f"unsupported dtype {v.dtype}")
+        elif v.dtype not in (np.float32, np.float64):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
         N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), _dt(v)))
         self.store_dtype = v.dtype
 
     def store_attach_dev(self, n, ptr, dtype):
-        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive)."""
+        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64 or N.U8."""
         N.check(self.L.fspann_store_attach_dev(self._h, int(n), ptr, dtype))
 
     def hbm_read_peak(self, nbytes=1 << 32, reps=5) -> float:

@@ -50,6 +50,15 @@ extern "C" {
 
 #define FSPANN_F32 0
 #define FSPANN_F64 1
+/* Unsigned bytes, value = the integer 0..255 (SIFT .bvecs data: a byte holds exactly what the reference's double[] holds, so
+ * distances over bytes widened on the fly are bit-identical to those over fp32 / fp64 rows, at a quarter / an eighth of the
+ * bytes).  A ROW dtype only: accepted by fspann_store_set / _attach_dev (and everything that reads the store), by the
+ * cand_dtype of fspann_refine_dev, the ref_cand_dtype of fspann_tick_dev and the dtype of fspann_build_index / _append;
+ * refused with FSPANN_E_ARG wherever a QUERY dtype is given (q_dtype, fspann_encode[_dev], fspann_refine with its one dtype
+ * for query and rows) and as dst_dtype of fspann_pointstore_open_batch.  tick_kernel (all three roles in one launch) is
+ * fp32-only: a tick over U8 rows that would have fused runs the stand-alone kernels in stream order (fspann_last_tick_fused
+ * says 0), results identical.                                                                                              */
+#define FSPANN_U8 2
 
 typedef struct fspann_ctx fspann_ctx;
 

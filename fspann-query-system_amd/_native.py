@@ -160,6 +160,8 @@ _SIGS = {
     "fspann_last_front_encode_mfma": (_i, [_vp]),
     "fspann_groundtruth_dev": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _vp]),
     "fspann_eval_metrics_dev": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "fspann_groundtruth_typed_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _vp]),
+    "fspann_eval_metrics_typed_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
     "fspann_pointstore_create": (_i, [_i64, _i, C.POINTER(_vp)]),
     "fspann_pointstore_destroy": (None, [_vp]),
     "fspann_pointstore_set_master_key": (_i, [_vp, _vp]),

@@ -12,8 +12,8 @@ int fspann_groundtruth_dev(fspann_ctx* c, int64_t n, const float* base_dev, int6
     if (n <= 0 || n >= (1LL << 31) || nq < 0 || dim <= 0) return fail(FSPANN_E_ARG, "Empty or malformed vector files (zero records).");
     if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
-    // the [chunk x n] fp64 distance matrix lives in scratch: at most ~8 GB at a time
-    const int64_t chunk = std::max<int64_t>(kGtQT, std::min<int64_t>(nq, ((1LL << 33) / (n * 8)) / kGtQT * kGtQT));
+    // the [chunk x n] fp64 distance matrix lives in scratch: at most the context's budget at a time (FSPANN_GT_SCRATCH_MB, 8 GiB)
+    const int64_t chunk = std::max<int64_t>(kGtQT, std::min<int64_t>(nq, (c->gt_scratch_bytes / (n * 8)) / kGtQT * kGtQT));
     int rc = ensure(c, c->ws_gt, static_cast<size_t>(chunk) * n * 8);
     if (rc) return rc;
     double* dist = static_cast<double*>(c->ws_gt.p);
@@ -38,6 +38,98 @@ int fspann_eval_metrics_dev(fspann_ctx* c, int64_t n, const float* base_dev, int
     if (nq == 0) return FSPANN_OK;
     hipLaunchKernelGGL(gt_metrics_kernel, dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base_dev, n, q_dev, dim, k, ann_ids_dev, ann_stride,
                        ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+    FSP_HIP(hipGetLastError());
+    return FSPANN_OK;
+}
+
+}  // extern "C"
+namespace {
+const char* gt_dtype_name(int dt) { return dt == FSPANN_F32 ? "FSPANN_F32" : dt == FSPANN_F64 ? "FSPANN_F64" : dt == FSPANN_U8 ? "FSPANN_U8" : "unknown dtype"; }
+int gt8_digits(uint64_t v) {      // 8-bit digits that hold v
+    int nd = 1;
+    while (nd < 4 && (v >> (8 * nd)) != 0) nd++;
+    return nd;
+}
+}  // namespace
+extern "C" {
+
+// Ground truth over typed rows.  (U8, U8): integer distances on the int8 matrix cores (groundtruth_u8.hip.h).
+int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev, int q_dtype, int dim, int k,
+                                 int32_t* out_ids_dev, double* out_d2_dev) {
+    CHECK_CTX(c);
+    if (!base_dev || !q_dev || !out_ids_dev) return fail(FSPANN_E_NULL, "ground truth buffer is null");
+    if (base_dtype != q_dtype || (base_dtype != FSPANN_F32 && base_dtype != FSPANN_U8))
+        return fail(FSPANN_E_ARG, "Base and query types must match (both fvecs or both bvecs): base %s, query %s", gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
+    if (base_dtype == FSPANN_F32)
+        return fspann_groundtruth_dev(c, n, static_cast<const float*>(base_dev), nq, static_cast<const float*>(q_dev), dim, k, out_ids_dev, out_d2_dev);
+    if (n <= 0 || n >= (1LL << 31) || nq < 0 || dim <= 0) return fail(FSPANN_E_ARG, "Empty or malformed vector files (zero records).");
+    if (dim > kGt8MaxDim) return fail(FSPANN_E_ARG, "dim %d > %d: FSPANN_U8 distances would not fit 32 bits", dim, kGt8MaxDim);
+    if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
+    if (nq == 0) return FSPANN_OK;
+    const uint8_t* base = static_cast<const uint8_t*>(base_dev);
+    const uint8_t* q = static_cast<const uint8_t*>(q_dev);
+    // scratch: |x'|^2 [n], |q'|^2 [chunk], then the [chunk x ld] uint32 distances, every part 256-byte aligned, rows 16-byte aligned
+    const int64_t ld = (n + 3) & ~int64_t(3);
+    const int64_t nbt = (n + kGt8Rows - 1) / kGt8Rows;
+    int64_t chunk = std::max<int64_t>(32, std::min<int64_t>((nq + 31) / 32 * 32, (c->gt_scratch_bytes / (ld * 4)) / 32 * 32));
+    chunk = std::min<int64_t>(chunk, std::max<int64_t>(kGt8Q, ((int64_t(1) << 31) - 1) / nbt / 2 * kGt8Q));      // the distance grid stays below 2^31 workgroups
+    const size_t xn_bytes = (static_cast<size_t>(n) * 4 + 255) & ~size_t(255);
+    const size_t qn_bytes = (static_cast<size_t>(chunk) * 4 + 255) & ~size_t(255);
+    int rc = ensure(c, c->ws_gt, xn_bytes + qn_bytes + static_cast<size_t>(chunk) * ld * 4);
+    if (rc) return rc;
+    unsigned* xn = static_cast<unsigned*>(c->ws_gt.p);
+    unsigned* qn = reinterpret_cast<unsigned*>(static_cast<char*>(c->ws_gt.p) + xn_bytes);
+    unsigned* dist = reinterpret_cast<unsigned*>(static_cast<char*>(c->ws_gt.p) + xn_bytes + qn_bytes);
+    // rows that start at odd addresses (dim % 16, or a matrix off a 16-byte boundary) take the byte-load instantiation
+    const bool aligned = (dim % 16 == 0) && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(q)) & 15) == 0;
+    const int ndd = gt8_digits(static_cast<uint64_t>(dim) * 255 * 255), ndi = gt8_digits(static_cast<uint64_t>(n - 1));
+    const dim3 ngrid(static_cast<unsigned>((n + 255) / 256));
+    if (aligned) hipLaunchKernelGGL(gt8_norm_kernel<true>, ngrid, dim3(256), 0, c->stream, base, n, dim, xn);
+    else hipLaunchKernelGGL(gt8_norm_kernel<false>, ngrid, dim3(256), 0, c->stream, base, n, dim, xn);
+    FSP_HIP(hipGetLastError());
+    for (int64_t s = 0; s < nq; s += chunk) {
+        const int64_t cq = std::min(chunk, nq - s);
+        const uint8_t* qs = q + s * dim;
+        const bool qal = aligned && (reinterpret_cast<uintptr_t>(qs) & 15) == 0;      // (dim % 16 == 0: every chunk starts aligned)
+        const int nqb = static_cast<int>((cq + kGt8Q - 1) / kGt8Q);
+        const dim3 qgrid(static_cast<unsigned>((cq + 255) / 256)), dgrid(static_cast<unsigned>(nbt * nqb));
+        if (qal) {
+            hipLaunchKernelGGL(gt8_norm_kernel<true>, qgrid, dim3(256), 0, c->stream, qs, cq, dim, qn);
+            hipLaunchKernelGGL(gt8_dist_kernel<true>, dgrid, dim3(256), 0, c->stream, base, n, qs, cq, dim, xn, qn, dist, ld, nqb);
+        } else {
+            hipLaunchKernelGGL(gt8_norm_kernel<false>, qgrid, dim3(256), 0, c->stream, qs, cq, dim, qn);
+            hipLaunchKernelGGL(gt8_dist_kernel<false>, dgrid, dim3(256), 0, c->stream, base, n, qs, cq, dim, xn, qn, dist, ld, nqb);
+        }
+        FSP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(gt8_select_kernel, dim3(static_cast<unsigned>(cq)), dim3(kGt8SelThreads), 0, c->stream, dist, ld, n, k, ndd, ndi,
+                           out_ids_dev + s * k, out_d2_dev ? out_d2_dev + s * k : nullptr);
+        FSP_HIP(hipGetLastError());
+    }
+    return FSPANN_OK;
+}
+
+int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev, int q_dtype, int dim, int k,
+                                  const int32_t* ann_ids_dev, int64_t ann_stride, const int32_t* ann_count_dev, const int32_t* gt_ids_dev,
+                                  int64_t gt_stride, double* recall_dev, double* ratio_dev) {
+    CHECK_CTX(c);
+    if (!base_dev || !q_dev || !ann_ids_dev || !gt_ids_dev || !recall_dev || !ratio_dev) return fail(FSPANN_E_NULL, "metrics buffer is null");
+    const bool f32 = base_dtype == FSPANN_F32 && q_dtype == FSPANN_F32;
+    const bool u8 = base_dtype == FSPANN_U8 && (q_dtype == FSPANN_U8 || q_dtype == FSPANN_F32);
+    if (!f32 && !u8)
+        return fail(FSPANN_E_ARG, "metrics take FSPANN_F32 rows with FSPANN_F32 queries, or FSPANN_U8 rows with FSPANN_U8 / FSPANN_F32 queries: base %s, query %s",
+                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
+    if (f32)
+        return fspann_eval_metrics_dev(c, n, static_cast<const float*>(base_dev), nq, static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride,
+                                       ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+    if (n <= 0 || nq < 0 || dim <= 0 || k <= 0 || k > kGtMaxK || gt_stride < k || ann_stride <= 0) return fail(FSPANN_E_ARG, "k must be in [1, %d] and gt must hold >= k ids per query", kGtMaxK);
+    if (nq == 0) return FSPANN_OK;
+    const uint8_t* base = static_cast<const uint8_t*>(base_dev);
+    if (q_dtype == FSPANN_U8)
+        hipLaunchKernelGGL((gt_metrics_typed_kernel<uint8_t, uint8_t>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base, n, static_cast<const uint8_t*>(q_dev), dim, k,
+                           ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+    else
+        hipLaunchKernelGGL((gt_metrics_typed_kernel<uint8_t, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base, n, static_cast<const float*>(q_dev), dim, k,
+                           ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
 }

@@ -308,6 +308,7 @@ int fspann_ctx_create(int device, const fspann_cfg* cfg, fspann_ctx** out) {
         c->knob_tick_fuse = env_int("FSPANN_TICK_FUSE", 1) != 0;
         c->knob_wave_sort = env_int("FSPANN_ROUTE_WAVE_SORT", 1);      // 1: per-wave group sorts, 0: whole-workgroup group sorts, -1: general sort only
         c->knob_tick_front = std::min(100, std::max(0, env_int("FSPANN_TICK_FRONT", 100)));
+        c->gt_scratch_bytes = static_cast<int64_t>(std::min(1 << 20, std::max(1, env_int("FSPANN_GT_SCRATCH_MB", 8192)))) << 20;
         {
             const char* fe = getenv("FSPANN_FRONT_ENCODE");
             c->knob_front_encode = (fe && std::strcmp(fe, "exact") == 0) ? 0 : 1;   // unset / "mfma": the MFMA role

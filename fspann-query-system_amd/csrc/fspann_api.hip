@@ -15,6 +15,7 @@
 #include "build.hip.h"
 #include "encode.hip.h"
 #include "groundtruth.hip.h"
+#include "groundtruth_u8.hip.h"
 #include "hostpipe.hip.h"
 #include "refine.hip.h"
 #include "route.hip.h"

@@ -105,6 +105,7 @@ struct fspann_ctx {
     int knob_tick_fuse = 1;          // FSPANN_TICK_FUSE=0: fspann_tick_dev always uses the stand-alone kernels
     int knob_front_encode = 1;       // FSPANN_FRONT_ENCODE: encode role of the front launch, mfma (1, default) or exact (0: encode_exact_block; dev A/B)
     int knob_tick_front = 100;       // FSPANN_TICK_FRONT: percent of a tick's Route workgroups that head the grid
+    int64_t gt_scratch_bytes = int64_t(8192) << 20;   // FSPANN_GT_SCRATCH_MB: budget of the ground truth's [query chunk x n] distance matrix
     int knob_bincheck = -1;          // FSPANN_ROUTE_BINCHECK: the bounded select's exact treeify check (-1: on for opaque ids, off for decimal ordinals; 0 / 1 force)
     bool knob_shape_spec = true;     // FSPANN_ROUTE_SHAPE_SPEC=0: the bounded select's build with run-time tables x probes also for 16 x 5 (dev A/B)
     int knob_mfma_tile = 0;          // FSPANN_ENCODE_MFMA_TILE=1: the 32 x 128 block tile of the MFMA encode for every batch size (dev A/B)
@@ -198,7 +199,7 @@ struct fspann_ctx {
     fspann::DevBuf ws_route;   // global hash/sort fallback for the route kernel
     fspann::DevBuf ws_probe;   // probe lists handed from route_probe_kernel to route_select_kernel
     fspann::DevBuf ws_refine;  // per-chunk partial top-k
-    fspann::DevBuf ws_gt;      // [query chunk][n] fp64 distance matrix of fspann_groundtruth_dev
+    fspann::DevBuf ws_gt;      // [query chunk][n] distance matrix of fspann_groundtruth_dev (fp64) / _typed_dev over bytes (uint32, + the norms)
     fspann::DevBuf ws_tickfix; // arenas of the full select run by the refine role of a tick for PENDING queries
     static constexpr int kFixSlots = 8;
     void* d_fixparams = nullptr;         // kFixSlots RouteParams blocks in device memory (parameters of that redo) ...

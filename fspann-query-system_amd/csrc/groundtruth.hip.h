@@ -193,4 +193,68 @@ __global__ __launch_bounds__(64) void gt_metrics_kernel(const float* __restrict_
     }
 }
 
+// gt_metrics_kernel over typed rows and queries (fspann_eval_metrics_typed_dev): TB = uint8_t (FSPANN_U8: the integer 0..255,
+// exact in fp64), TQ = uint8_t or float; the same fp64 arithmetic and the same ordered fold, statement for statement.  The
+// fp32 kernel above stays as it is and is what fspann_eval_metrics_dev launches: routed through this template it compiled to
+// the same instructions but for the operand order of one integer add, and that kernel is kept instruction-identical.
+template <typename TB, typename TQ>
+__global__ __launch_bounds__(64) void gt_metrics_typed_kernel(const TB* __restrict__ base, int64_t n, const TQ* __restrict__ q, int d, int k,
+                                                              const int32_t* __restrict__ ann, int64_t ann_stride, const int32_t* __restrict__ ann_count,
+                                                              const int32_t* __restrict__ gt, int64_t gt_stride, double* __restrict__ recall,
+                                                              double* __restrict__ ratio) {
+    const int64_t qi = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int na = ann_count ? max(0, min(ann_count[qi], static_cast<int>(ann_stride))) : static_cast<int>(ann_stride);
+    const int32_t* a = ann + qi * ann_stride;
+    const int32_t* g = gt + qi * gt_stride;
+    // recall: hits among the first min(k, na) results that are in gt[0..k)  (a Set: a repeated id counts each time it appears, like the Java loop)
+    int hits = 0;
+    for (int i = lane; i < min(k, na); i += 64) {
+        const int32_t id = a[i];
+        bool in = false;
+        for (int j = 0; j < k; j++) in = in || (g[j] == id);
+        hits += in ? 1 : 0;
+    }
+    for (int off = 32; off > 0; off >>= 1) hits += __shfl_xor(hits, off);
+    // ratio: needs k results; BaseVectorReader.l2 = sqrt(sum (q_i - v_i)^2), q widened to double first (FSA:1017-1073)
+    // the reference adds the k terms in index order: rounds of 64 terms, lane l holds term 64 r + l, and a sequential fold over
+    // the lanes inside every round reproduces the Java sum exactly (any k)
+    double tot = 0.0;
+    int usedt = 0;
+    if (na >= k) {
+        const TQ* qr = q + qi * d;
+        for (int i0 = 0; i0 < k; i0 += 64) {
+            const int i = i0 + lane;
+            double term = 0.0;
+            int used = 0;
+            if (i < k) {
+                const int32_t ai = a[i], gi = g[i];
+                if (!(ai < 0 || ai >= n || gi < 0 || gi >= n)) {
+                    double sg = 0.0, sa = 0.0;
+                    for (int t = 0; t < d; t++) {
+                        const double qv = static_cast<double>(qr[t]);
+                        const double dg = qv - static_cast<double>(base[static_cast<int64_t>(gi) * d + t]);
+                        const double pg = dg * dg;
+                        sg = sg + pg;
+                        const double da = qv - static_cast<double>(base[static_cast<int64_t>(ai) * d + t]);
+                        const double pa = da * da;
+                        sa = sa + pa;
+                    }
+                    const double dGt = sqrt(sg);
+                    if (dGt > 0) { term = sqrt(sa) / dGt; used = 1; }
+                }
+            }
+            for (int l = 0; l < 64; l++) {
+                const double v = __shfl(term, l);
+                const int u = __shfl(used, l);
+                if (u) { tot = tot + v; usedt += u; }
+            }
+        }
+    }
+    if (lane == 0) {
+        recall[qi] = static_cast<double>(hits) / static_cast<double>(k);
+        ratio[qi] = (na >= k && usedt == k) ? tot / static_cast<double>(k) : __longlong_as_double(0x7FF8000000000000LL);
+    }
+}
+
 }  // namespace fspann

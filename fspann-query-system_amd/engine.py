@@ -474,6 +474,46 @@ class FspannContext:
         N.check(self.L.fspann_eval_metrics_dev(self._h, n, base_ptr, nq, q_ptr, dim, k, ann_ptr, ann_stride, ann_count_ptr or None, gt_ptr, gt_stride,
                                                recall_ptr, ratio_ptr))
 
+    def groundtruth_typed_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, out_ids_ptr, out_d2_ptr=0):
+        """Exact k-NN of device-resident rows: (N.F32, N.F32) as groundtruth_dev, (N.U8, N.U8) over bytes on the int8 matrix
+        cores, ids and squared distances bit-identical to the reference's."""
+        N.check(self.L.fspann_groundtruth_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, out_ids_ptr, out_d2_ptr or None))
+
+    def eval_metrics_typed_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride, ann_count_ptr, gt_ptr, gt_stride,
+                               recall_ptr, ratio_ptr):
+        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries."""
+        N.check(self.L.fspann_eval_metrics_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride,
+                                                     ann_count_ptr or None, gt_ptr, gt_stride, recall_ptr, ratio_ptr))
+
+    def groundtruth(self, base, q, k):
+        """Exact k-NN of host arrays: uint8 arrays stay bytes on the device, anything else goes as fp32 (base and q alike).
+        Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n)."""
+        base, q = np.asarray(base), np.asarray(q)
+        if (base.dtype == np.uint8) != (q.dtype == np.uint8):
+            raise N.FspannArgumentError("Base and query types must match (both fvecs or both bvecs)")
+        dt = np.uint8 if base.dtype == np.uint8 else np.float32
+        b, qq = _c(base, dt), _c(q, dt)
+        if b.ndim != 2 or qq.ndim != 2 or b.shape[1] != qq.shape[1]:
+            raise N.FspannArgumentError("base [n][dim] and q [nq][dim] must share dim")
+        (n, dim), nq = b.shape, qq.shape[0]
+        ids, d2 = np.empty((nq, k), np.int32), np.empty((nq, k), np.float64)
+        ptrs = []
+        try:
+            for nbytes in (b.nbytes, qq.nbytes, ids.nbytes, d2.nbytes):
+                p = C.c_void_p()
+                N.check(self.L.fspann_dev_alloc(self._h, nbytes, C.byref(p)))
+                ptrs.append(p)
+            bd, qd, idd, d2d = ptrs
+            N.check(self.L.fspann_h2d(self._h, bd, _p(b), b.nbytes))
+            N.check(self.L.fspann_h2d(self._h, qd, _p(qq), qq.nbytes))
+            self.groundtruth_typed_dev(n, bd, _dt(b), nq, qd, _dt(qq), dim, k, idd, d2d)
+            N.check(self.L.fspann_d2h(self._h, _p(ids), idd, ids.nbytes))
+            N.check(self.L.fspann_d2h(self._h, _p(d2), d2d, d2.nbytes))
+        finally:
+            for p in ptrs:
+                self.L.fspann_dev_free(self._h, p)
+        return ids, d2
+
     def route_handover_bytes(self, nq, probe_override=-1) -> int:
         return int(self.L.fspann_route_handover_bytes(self._h, nq, probe_override))
 

@@ -391,6 +391,24 @@ int fspann_groundtruth_dev(fspann_ctx* ctx, int64_t n, const float* base_dev, in
 int fspann_eval_metrics_dev(fspann_ctx* ctx, int64_t n, const float* base_dev, int64_t nq, const float* q_dev, int dim, int k,
                             const int32_t* ann_ids_dev, int64_t ann_stride, const int32_t* ann_count_dev, const int32_t* gt_ids_dev,
                             int64_t gt_stride, double* recall_dev, double* ratio_dev);
+/* The same over typed rows, as GroundtruthPrecompute.run takes .bvecs for base and queries (:103-108,148-149,218-228) and
+ * BaseVectorReader.l2sq reads .bvecs bases (FSA:1027-1032).
+ * fspann_groundtruth_typed_dev: (FSPANN_F32, FSPANN_F32) is fspann_groundtruth_dev.  (FSPANN_U8, FSPANN_U8): base [n][dim]
+ * and q [nq][dim] packed bytes in device memory, any alignment, dim in 1..32768; sums of squares of byte differences are
+ * integers, exact in fp64 in any order, so they are computed as 32-bit integers on the int8 matrix cores and out_ids / out_d2
+ * equal the reference's bit for bit (out_d2: the integers as fp64).  fspann_store_dev_ptr of a U8 store is a valid base_dev.
+ * Any other pair, FSPANN_F64, dim > 32768 with bytes, k outside 1..1024: FSPANN_E_ARG ("Base and query types must match
+ * (both fvecs or both bvecs)", :226-228).
+ * fspann_eval_metrics_typed_dev: FSPANN_F32 rows with FSPANN_F32 queries (= fspann_eval_metrics_dev), or FSPANN_U8 rows
+ * with FSPANN_U8 or FSPANN_F32 queries (searches are made with fp32 queries); the same fp64 arithmetic and ordered fold.
+ * The [query chunk x n] distance matrix of either ground-truth call (fp64, or uint32 over bytes) lives in library scratch of at
+ * most FSPANN_GT_SCRATCH_MB MiB (environment, read at fspann_ctx_create; default 8192); more queries run in chunks.         */
+int fspann_groundtruth_typed_dev(fspann_ctx* ctx, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev,
+                                 int q_dtype, int dim, int k, int32_t* out_ids_dev, double* out_d2_dev);
+int fspann_eval_metrics_typed_dev(fspann_ctx* ctx, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev,
+                                  int q_dtype, int dim, int k, const int32_t* ann_ids_dev, int64_t ann_stride,
+                                  const int32_t* ann_count_dev, const int32_t* gt_ids_dev, int64_t gt_stride, double* recall_dev,
+                                  double* ratio_dev);
 
 /* ---- host candidate pipeline -------------------------------------------------------------------
  * QSI stage B's host half at batch scale: for every id of F_q the reference does loadPointIfActive (one RocksDB get + one

@@ -20,6 +20,7 @@ HIPCC_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off"
 OK, E_STATE, E_ARG, E_NULL, E_DEVICE, E_NOMEM, E_RANGE = 0, -1, -2, -3, -4, -5, -6
 F32, F64 = 0, 1
 U8 = 2     # rows only: unsigned bytes, value = the integer 0..255 (FSPANN_U8)
+F16 = 3    # rows only: IEEE binary16, value = the half widened exactly (FSPANN_F16)
 INT32_MAX = 2**31 - 1
 
 

@@ -24,7 +24,8 @@ int build_begin_impl(fspann_ctx* c, int64_t n) {
 int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype) {
     const int d = c->cfg.dim, TD = c->TD, W = c->W;
     const size_t esz = dtype_size(dtype);
-    const bool bytes_in = dtype == FSPANN_U8;   // byte rows go up as bytes and are widened to fp32 on the device: the codes are those of the F32 build
+    // byte rows and half rows go up as they are and are widened to fp32 on the device, exactly: the codes are those of the F32 build
+    const bool bytes_in = dtype == FSPANN_U8, halves_in = dtype == FSPANN_F16, widen = bytes_in || halves_in;
     const int64_t chunk = 1 << 18;
     int rc;
     if (c->bld_done + nrows > c->bld_n) {       // more rows than the hint: grow the code buffer, keep what is coded
@@ -41,7 +42,7 @@ int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype)
     }
     if ((rc = ensure(c, c->ws_io[0], static_cast<size_t>(std::min(chunk, nrows)) * d * esz))) return rc;
     if ((rc = ensure(c, c->ws_io[2], static_cast<size_t>(std::min(chunk, nrows)) * 4))) return rc;
-    if (bytes_in && (rc = ensure(c, c->ws_io[1], static_cast<size_t>(std::min(chunk, nrows)) * d * 4))) return rc;
+    if (widen && (rc = ensure(c, c->ws_io[1], static_cast<size_t>(std::min(chunk, nrows)) * d * 4))) return rc;
     uint64_t* codes_all = static_cast<uint64_t*>(c->bld_codes.p);
     std::vector<int32_t> bad(static_cast<size_t>(std::min(chunk, nrows)));
     for (int64_t s = 0; s < nrows; s += chunk) {
@@ -54,8 +55,13 @@ int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype)
             hipLaunchKernelGGL(build_widen_u8_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
                                static_cast<const uint8_t*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
             FSP_HIP(hipGetLastError());
+        } else if (halves_in) {
+            const int64_t ne = cn * d;
+            hipLaunchKernelGGL(build_widen_f16_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
+                               static_cast<const _Float16*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
+            FSP_HIP(hipGetLastError());
         }
-        rc = fspann_encode_dev(c, cn, bytes_in ? c->ws_io[1].p : c->ws_io[0].p, bytes_in ? FSPANN_F32 : dtype, cdst, nullptr, static_cast<int32_t*>(c->ws_io[2].p));
+        rc = fspann_encode_dev(c, cn, widen ? c->ws_io[1].p : c->ws_io[0].p, widen ? FSPANN_F32 : dtype, cdst, nullptr, static_cast<int32_t*>(c->ws_io[2].p));
         if (rc) return rc;
         FSP_HIP(hipMemcpyAsync(bad.data(), c->ws_io[2].p, static_cast<size_t>(cn) * 4, hipMemcpyDeviceToHost, c->stream));
         FSP_HIP(hipStreamSynchronize(c->stream));
@@ -76,7 +82,7 @@ int fspann_build_index(fspann_ctx* c, int64_t n, const void* vectors, int dtype,
     if (!vectors) return fail(FSPANN_E_NULL, "vector cannot be null");
     if (n <= 0) return fail(FSPANN_E_ARG, "n <= 0");
     if (c->n_ids < n) return fail(FSPANN_E_STATE, "set id metadata for at least n handles first");
-    if (dtype != FSPANN_F32 && dtype != FSPANN_F64 && dtype != FSPANN_U8) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
+    if (!is_row_dtype(dtype)) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     return guarded([&]() -> int {
         int rc = build_begin_impl(c, n);
         if (!rc) rc = build_append_impl(c, n, vectors, dtype);
@@ -101,7 +107,7 @@ int fspann_build_append(fspann_ctx* c, int64_t n_rows, const void* rows, int dty
     if (n_rows < 0) return fail(FSPANN_E_ARG, "n_rows < 0");
     if (n_rows == 0) return FSPANN_OK;
     if (!rows) return fail(FSPANN_E_NULL, "vector cannot be null");
-    if (dtype != FSPANN_F32 && dtype != FSPANN_F64 && dtype != FSPANN_U8) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
+    if (!is_row_dtype(dtype)) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     return guarded([&]() -> int { return build_append_impl(c, n_rows, rows, dtype); });
 }
 int fspann_build_finish(fspann_ctx* c, const int32_t* order) {

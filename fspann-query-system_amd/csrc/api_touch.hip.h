@@ -41,6 +41,9 @@ int touch_store_ok(fspann_ctx* c) {
     const unsigned grid = static_cast<unsigned>((c->store_n + kTouchThreads / 64 - 1) / (kTouchThreads / 64));
     if (c->store_dtype == FSPANN_U8)      // a byte is always finite: every row is valid
         FSP_HIP(hipMemsetAsync(c->store_ok.p, 1, static_cast<size_t>(c->store_n), c->stream));
+    else if (c->store_dtype == FSPANN_F16)  // a half can be +-inf or NaN, like a float
+        hipLaunchKernelGGL(touch_store_valid_kernel<_Float16>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const _Float16*>(c->d_store),
+                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
     else if (c->store_dtype == FSPANN_F64)
         hipLaunchKernelGGL(touch_store_valid_kernel<double>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const double*>(c->d_store),
                            c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));

@@ -34,6 +34,19 @@ __global__ __launch_bounds__(256) void build_widen_u8_kernel(const uint8_t* __re
     }
 }
 
+// Setup input as halves (FSPANN_F16): widened to fp32 on the device, exactly (every half, subnormals, infinities and NaN
+// included, is an fp32 value), four elements per thread; a non-finite element is then refused by the encode as in an F32 build.
+__global__ __launch_bounds__(256) void build_widen_f16_kernel(const _Float16* __restrict__ in, int64_t n, float* __restrict__ out) {
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (i + 4 <= n) {
+        const h4 w = *reinterpret_cast<const h4*>(in + i);
+        *reinterpret_cast<float4*>(out + i) = make_float4(static_cast<float>(w[0]), static_cast<float>(w[1]), static_cast<float>(w[2]), static_cast<float>(w[3]));
+    } else {
+        for (int64_t j = i; j < n; j++) out[j] = static_cast<float>(in[j]);
+    }
+}
+
 __global__ __launch_bounds__(kRsThreads) void rs_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
                                                              int nblocks, uint32_t* __restrict__ tot) {
     __shared__ uint32_t h[256];

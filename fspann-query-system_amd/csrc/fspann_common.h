@@ -44,7 +44,13 @@ inline int fail(int code, const char* fmt, ...) {
     } while (0)
 
 // bytes per element of a dtype of include/fspann.h (the callers have checked which dtypes they take)
-inline size_t dtype_size(int dtype) { return dtype == FSPANN_F64 ? 8 : (dtype == FSPANN_U8 ? 1 : 4); }
+inline size_t dtype_size(int dtype) { return dtype == FSPANN_F64 ? 8 : (dtype == FSPANN_U8 ? 1 : (dtype == FSPANN_F16 ? 2 : 4)); }
+// the row dtypes: what fspann_store_set / _attach_dev, fspann_build_index / _append and the rows of a refinement take
+inline bool is_row_dtype(int dtype) { return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16; }
+// FSPANN_F16 given where no half can stand (a query, the point store, the ground truth): refused by name
+inline int refuse_f16(const char* what) {
+    return fail(FSPANN_E_ARG, "%s FSPANN_F16: half precision is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
+}
 
 // ---- order-key bit budget (DESIGN.md "Java order key") ----------------------------
 // key = score(10) | bucket(20) | seq(22); seq = (td*P + step)*S + pos is unique per tuple.

@@ -49,6 +49,12 @@ typedef uint32_t fsp_u32x4 __attribute__((ext_vector_type(4)));
 template <> struct VecOf<uint8_t> { using type = fsp_u32x4; static constexpr int N = 16; };
 template <typename T> struct RowIsBytes { static constexpr bool value = false; };
 template <> struct RowIsBytes<uint8_t> { static constexpr bool value = true; };
+// FSPANN_F16 rows: a 16-byte slot is 8 IEEE binary16 elements (four dwords, two halves each); an element is the half widened
+// exactly (half -> float -> double: every finite half, subnormals included, is a double), and unlike a byte it can be +-inf or NaN.
+typedef _Float16 fsp_f16x8 __attribute__((ext_vector_type(8)));
+template <> struct VecOf<_Float16> { using type = fsp_f16x8; static constexpr int N = 8; };
+template <typename T> struct RowIsHalf { static constexpr bool value = false; };
+template <> struct RowIsHalf<_Float16> { static constexpr bool value = true; };
 
 template <typename T> __device__ __forceinline__ bool finite_t(T x) {
     return fabs(static_cast<double>(x)) <= 1.79769313486231570815e+308;
@@ -61,6 +67,9 @@ __device__ __forceinline__ double vcomp(fsp_f64x2 v, int e) { return v[e]; }
 // and against keeping the query's tile as fp64 in LDS instead of converting it per element: within 5 % of each other
 //  — every vector instruction of this loop issues at the same rate, so the plain expression stays.
 __device__ __forceinline__ double vcomp(fsp_u32x4 v, int e) { return static_cast<double>((v[e >> 2] >> (8 * (e & 3))) & 0xFFu); }
+// Exact widening of half e of a slot: v_cvt_f32_f16 (the high half of a dword through SDWA src0_sel:WORD_1, no shift), then
+// v_cvt_f64_f32.  Kernels keep fp16 denormals (float_denorm_mode_16_64 = 3), so a subnormal half arrives as its value.
+__device__ __forceinline__ double vcomp(fsp_f16x8 v, int e) { return static_cast<double>(static_cast<float>(v[e])); }
 
 constexpr int kRefFilterMaxK = 32;   // top-k via per-wave k-th-smallest filter up to this k
 
@@ -608,8 +617,10 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     // Byte rows (FSPANN_U8) are always finite, so no row element is ever tested; against an fp32 query the sum tells about the
     // QUERY in the same way (|q - x| < 2^129 again).  Against an fp64 query it does not (1e200 squared overflows with every element
     // finite): there the per-query check stays, and such a row is scored with distance +inf as the reference scores it.
+    // Half rows (FSPANN_F16) can hold +-inf and NaN like fp32 rows, and |x| <= 65504: against an fp32 query the sum tells again
+    // (|q - x| < 2^129); against an fp64 query every raw half is tested (v_cmp_class_f16).
     constexpr bool kByteRows = RowIsBytes<TC>::value;
-    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows) && sizeof(TQ) == 4);
+    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows || RowIsHalf<TC>::value) && sizeof(TQ) == 4);
     const TC* __restrict__ cand = a.cand;
     const int64_t store_n = a.store_n, B = a.B;
     const int d = a.d, nchunks = a.nchunks;

@@ -17,9 +17,9 @@
 // batch) is redone with the full select by the workgroup that refines it one tick later — before it scans.  That removes
 // the hand-back launch of fspann_route_dev (an empty dependent kernel costs ~4.5 us on this runtime).
 //
-// tick_kernel is fp32-only (queries and rows).  A tick over FSPANN_U8 rows that would have fused runs the stand-alone kernels in
+// tick_kernel is fp32-only (queries and rows).  A tick over FSPANN_U8 or FSPANN_F16 rows that would have fused runs the stand-alone kernels in
 // stream order instead (fspann_last_tick_fused says 0; results identical); a refine-only tick with a hand-over buffer keeps its
-// one launch through the U8 refine_stream_fix_kernel below.
+// one launch through the typed refine_stream_fix_kernel overload below.
 #pragma once
 #include "encode.hip.h"
 #include "refine.hip.h"
@@ -159,14 +159,14 @@ __global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_fix_
                                                                 RefineRouteFix{fix_dev, smem});
 }
 
-// The same kernel over FSPANN_U8 rows (one 128-byte tile per 128 dims; an overload with the row type as a template parameter, so
-// that the fp32 kernel above keeps its symbol and its code): a U8 batch keeps the front pipeline.
+// The same kernel over FSPANN_U8 / FSPANN_F16 rows (one 128-byte tile per 128 / 64 dims; an overload with the row type as a template parameter, so
+// that the fp32 kernel above keeps its symbol and its code): a U8 or F16 batch keeps the front pipeline.
 template <typename TC, bool GATHER>
 __global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_fix_kernel(const RefineArgs<TC, float> a, const int64_t nq,
                                                                                        const RouteParams* __restrict__ fix_dev) {
-    static_assert(sizeof(TC) == 1, "fp32 rows: refine_stream_fix_kernel<GATHER>");
+    static_assert(sizeof(TC) <= 2, "fp32 rows: refine_stream_fix_kernel<GATHER>");
     extern __shared__ __align__(16) unsigned char smem[];
-    refine_stream_run<TC, float, 128, GATHER, RefineRouteFix>(a, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), nq, true,
+    refine_stream_run<TC, float, 128 / static_cast<int>(sizeof(TC)), GATHER, RefineRouteFix>(a, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), nq, true,
                                                               RefineRouteFix{fix_dev, smem});
 }
 

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kTouchThreads) void touch_mark_rows_kernel(const TQ
         if (id < 0 || id >= n_set) continue;          // (wave-uniform) not a handle of this index: nothing to mark
         const TC* r = rows + (qi * B + j) * d;
         bool bad = false;
-        if constexpr (sizeof(TC) > 1)                 // (FSPANN_U8 rows: a byte is always finite)
+        if constexpr (sizeof(TC) > 1)                 // (FSPANN_U8 rows: a byte is always finite; FSPANN_F16 rows are tested like floats)
             for (int i = lane; i < d; i += 64) bad = bad || !__builtin_isfinite(r[i]);
         const bool any_bad = __any(bad);
         if (lane == 0 && !any_bad) set[id] = 1;

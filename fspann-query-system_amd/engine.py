@@ -53,6 +53,8 @@ def _dt(a):
         return N.F64
     if a.dtype == np.uint8:     # rows only (FSPANN_U8): the library refuses it wherever a query dtype is given
         return N.U8
+    if a.dtype == np.float16:   # rows only (FSPANN_F16): refused likewise
+        return N.F16
     raise N.FspannArgumentError(f"unsupported dtype {a.dtype}")
 
 
@@ -146,9 +148,10 @@ class FspannContext:
         N.check(self.L.fspann_finalize(self._h))
 
     def build_index(self, vectors, order=None):
-        """A uint8 array goes to the library as bytes (FSPANN_U8: widened on the device; same tables, a quarter of the traffic)."""
+        """A uint8 array goes to the library as bytes (FSPANN_U8: widened on the device; same tables, a quarter of the traffic),
+        a float16 array as halves (FSPANN_F16: same tables, half the traffic)."""
         v = np.ascontiguousarray(vectors)
-        if v.dtype not in (np.float32, np.float64, np.uint8):
+        if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
         o = None if order is None else _c(order, np.int32)
@@ -160,7 +163,7 @@ class FspannContext:
 
     def build_append(self, rows):
         v = np.ascontiguousarray(rows)
-        if v.dtype not in (np.float32, np.float64, np.uint8):
+        if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
         N.check(self.L.fspann_build_append(self._h, v.shape[0], _p(v), _dt(v)))
@@ -379,7 +382,10 @@ class FspannContext:
     def store_set(self, vectors, dtype=None):
         """dtype=np.uint8 keeps the rows as bytes (FSPANN_U8): only for data whose values are the integers 0..255 (a uint8
         array, or an array holding nothing else), where a byte is exactly what the reference's double[] holds.  Without it a
-        uint8 array is widened to float64 like every other non-float array."""
+        uint8 array is widened to float64 like every other non-float array.
+        dtype=np.float16 keeps the rows as halves (FSPANN_F16): a float16 array as it is, any other array only if every value
+        already is a half (it survives astype(float16) and back unchanged, NaN counting as NaN) — the library never rounds for
+        the caller.  Without it a float16 array is widened to float64 as well."""
         v = np.ascontiguousarray(vectors)
         if dtype is not None and np.dtype(dtype) == np.uint8:
             if v.dtype != np.uint8:
@@ -388,6 +394,16 @@ class FspannContext:
                 if not exact:
                     raise N.FspannArgumentError("store_set(dtype=uint8): every value must be an integer in 0..255")
                 v = v.astype(np.uint8)
+        elif dtype is not None and np.dtype(dtype) == np.float16:
+            if v.dtype != np.float16:
+                with np.errstate(over="ignore", invalid="ignore"):
+                    h = v.astype(np.float16)
+                    back = h.astype(v.dtype)
+                    exact = bool(np.all((back == v) | ((back != back) & (v != v))))
+                if not exact:
+                    raise N.FspannArgumentError("store_set(dtype=float16): every value must be exactly representable as an IEEE half "
+                                                "(round the data yourself: the library never does)")
+                v = h
         elif dtype is not None:
             v = v.astype(np.dtype(dtype))
             if v.dtype not in (np.float32, np.float64):
@@ -399,7 +415,7 @@ class FspannContext:
         self.store_dtype = v.dtype
 
     def store_attach_dev(self, n, ptr, dtype):
-        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64 or N.U8."""
+        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8 or N.F16."""
         N.check(self.L.fspann_store_attach_dev(self._h, int(n), ptr, dtype))
 
     def hbm_read_peak(self, nbytes=1 << 32, reps=5) -> float:
@@ -481,7 +497,8 @@ class FspannContext:
 
     def eval_metrics_typed_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride, ann_count_ptr, gt_ptr, gt_stride,
                                recall_ptr, ratio_ptr):
-        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries."""
+        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries, or N.F16 rows with
+        N.F32 queries (recall and ratio against a resident half store without an fp32 copy)."""
         N.check(self.L.fspann_eval_metrics_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride,
                                                      ann_count_ptr or None, gt_ptr, gt_stride, recall_ptr, ratio_ptr))
 

@@ -59,6 +59,16 @@ extern "C" {
  * fp32-only: a tick over U8 rows that would have fused runs the stand-alone kernels in stream order (fspann_last_tick_fused
  * says 0), results identical.                                                                                              */
 #define FSPANN_U8 2
+/* IEEE binary16 (half precision), value = the half widened exactly: every finite half, subnormals included, is a double, so
+ * distances over halves widened on the fly are bit-identical to those over the same values held as fp32 / fp64, at half / a
+ * quarter of the bytes.  The library never rounds: the caller hands over halves.  A ROW dtype only, with the standing of
+ * FSPANN_U8: accepted by fspann_store_set / _attach_dev (and everything that reads the store), by the cand_dtype of
+ * fspann_refine_dev, the ref_cand_dtype of fspann_tick_dev, the dtype of fspann_build_index / _append, and as the base of
+ * fspann_eval_metrics_typed_dev with FSPANN_F32 queries; refused with FSPANN_E_ARG and a message naming FSPANN_F16 wherever a
+ * QUERY dtype is given, by fspann_pointstore_encrypt / _open_batch, by fspann_groundtruth_typed_dev and by metrics with any
+ * other query type.  A row holding +-inf or NaN is skipped, not scored (QSI.isValid).  A three-role tick over F16 rows runs the
+ * stand-alone kernels in stream order (fspann_last_tick_fused says 0), results identical.                                      */
+#define FSPANN_F16 3
 
 typedef struct fspann_ctx fspann_ctx;
 

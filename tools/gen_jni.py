@@ -123,6 +123,8 @@ def main():
             '    private FspannNative() {}', '', '    public static final int F32 = 0, F64 = 1;',
             '    /** Rows only (FSPANN_U8): unsigned bytes, value = the integer 0..255; refused wherever a query dtype is given. */',
             '    public static final int U8 = 2;',
+            '    /** Rows only (FSPANN_F16): IEEE binary16 halves, value = the half widened exactly; refused wherever a query dtype is given. */',
+            '    public static final int F16 = 3;',
             '    public static final int OK = 0, E_STATE = -1, E_ARG = -2, E_NULL = -3, E_DEVICE = -4, E_NOMEM = -5, E_RANGE = -6;',
             '    /** fspann_tick field order for the long[] passed to tickDev. */',
             '    public static final String[] TICK_FIELDS = {' + ", ".join('"%s"' % f for f in TICK_FIELDS) + '};', '']

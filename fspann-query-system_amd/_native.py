@@ -21,6 +21,7 @@ OK, E_STATE, E_ARG, E_NULL, E_DEVICE, E_NOMEM, E_RANGE = 0, -1, -2, -3, -4, -5, 
 F32, F64 = 0, 1
 U8 = 2     # rows only: unsigned bytes, value = the integer 0..255 (FSPANN_U8)
 F16 = 3    # rows only: IEEE binary16, value = the half widened exactly (FSPANN_F16)
+BF16 = 4   # rows only: bfloat16 bit patterns, value = the fp32 with the bits b << 16 (FSPANN_BF16)
 INT32_MAX = 2**31 - 1
 
 

@@ -44,6 +44,9 @@ int touch_store_ok(fspann_ctx* c) {
     else if (c->store_dtype == FSPANN_F16)  // a half can be +-inf or NaN, like a float
         hipLaunchKernelGGL(touch_store_valid_kernel<_Float16>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const _Float16*>(c->d_store),
                            c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
+    else if (c->store_dtype == FSPANN_BF16) // so can a bfloat16
+        hipLaunchKernelGGL(touch_store_valid_kernel<fsp_bf16>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const fsp_bf16*>(c->d_store),
+                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
     else if (c->store_dtype == FSPANN_F64)
         hipLaunchKernelGGL(touch_store_valid_kernel<double>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const double*>(c->d_store),
                            c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));

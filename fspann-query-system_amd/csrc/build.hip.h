@@ -47,6 +47,20 @@ __global__ __launch_bounds__(256) void build_widen_f16_kernel(const _Float16* __
     }
 }
 
+// Setup input as bfloat16 bit patterns (FSPANN_BF16): widened to fp32 on the device by a shift — the pattern b becomes the float with
+// the bits b << 16, exact for every bfloat16 — four elements per thread (one 8-byte load, one 16-byte store); a non-finite element is
+// then refused by the encode as in an F32 build.
+__global__ __launch_bounds__(256) void build_widen_bf16_kernel(const fsp_bf16* __restrict__ in, int64_t n, float* __restrict__ out) {
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (i + 4 <= n) {
+        const uint2 w = *reinterpret_cast<const uint2*>(in + i);
+        *reinterpret_cast<float4*>(out + i) = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u),
+                                                          __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u));
+    } else {
+        for (int64_t j = i; j < n; j++) out[j] = static_cast<float>(in[j]);
+    }
+}
+
 __global__ __launch_bounds__(kRsThreads) void rs_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
                                                              int nblocks, uint32_t* __restrict__ tot) {
     __shared__ uint32_t h[256];

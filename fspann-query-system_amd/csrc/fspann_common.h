@@ -44,13 +44,31 @@ inline int fail(int code, const char* fmt, ...) {
     } while (0)
 
 // bytes per element of a dtype of include/fspann.h (the callers have checked which dtypes they take)
-inline size_t dtype_size(int dtype) { return dtype == FSPANN_F64 ? 8 : (dtype == FSPANN_U8 ? 1 : (dtype == FSPANN_F16 ? 2 : 4)); }
+inline size_t dtype_size(int dtype) { return dtype == FSPANN_F64 ? 8 : (dtype == FSPANN_U8 ? 1 : ((dtype == FSPANN_F16 || dtype == FSPANN_BF16) ? 2 : 4)); }
 // the row dtypes: what fspann_store_set / _attach_dev, fspann_build_index / _append and the rows of a refinement take
-inline bool is_row_dtype(int dtype) { return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16; }
+inline bool is_row_dtype(int dtype) {
+    return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16 || dtype == FSPANN_BF16;
+}
 // FSPANN_F16 given where no half can stand (a query, the point store, the ground truth): refused by name
 inline int refuse_f16(const char* what) {
     return fail(FSPANN_E_ARG, "%s FSPANN_F16: half precision is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
 }
+// FSPANN_BF16 likewise
+inline int refuse_bf16(const char* what) {
+    return fail(FSPANN_E_ARG, "%s FSPANN_BF16: bfloat16 is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
+}
+
+// One FSPANN_BF16 row element: 16 bits b, value = the fp32 whose bit pattern is b << 16 (every bfloat16, subnormals, +-0, +-inf and
+// NaN included).  A type of its own, so that a bf16 row is never taken for a half or for a uint16_t id.  Widening is a shift: exact,
+// no conversion instruction that could round or flush.
+struct fsp_bf16 {
+    uint16_t b;
+    __host__ __device__ __forceinline__ explicit operator float() const { return __builtin_bit_cast(float, static_cast<uint32_t>(b) << 16); }
+    __host__ __device__ __forceinline__ explicit operator double() const { return static_cast<double>(static_cast<float>(*this)); }
+};
+static_assert(sizeof(fsp_bf16) == 2 && alignof(fsp_bf16) == 2, "a bf16 row element is two bytes");
+// an element is +-inf or NaN iff its exponent field is all ones
+__host__ __device__ __forceinline__ bool bf16_finite(fsp_bf16 x) { return (x.b & 0x7f80u) != 0x7f80u; }
 
 // ---- order-key bit budget (DESIGN.md "Java order key") ----------------------------
 // key = score(10) | bucket(20) | seq(22); seq = (td*P + step)*S + pos is unique per tuple.

@@ -55,6 +55,14 @@ typedef _Float16 fsp_f16x8 __attribute__((ext_vector_type(8)));
 template <> struct VecOf<_Float16> { using type = fsp_f16x8; static constexpr int N = 8; };
 template <typename T> struct RowIsHalf { static constexpr bool value = false; };
 template <> struct RowIsHalf<_Float16> { static constexpr bool value = true; };
+// FSPANN_BF16 rows: the same 2-byte geometry (a 16-byte slot is 8 elements in four dwords, low element in the low 16 bits).  The
+// slot is held as four SIGNED dwords: a native vector like the others (a struct could not be a nontemporal load's result), and a
+// type of its own, so that no overload takes it for the unsigned dwords of a byte slot.  An element is the fp32 whose bit pattern
+// is the 16 bits shifted up, and can be +-inf or NaN.
+typedef int32_t fsp_bf16x8 __attribute__((ext_vector_type(4)));
+template <> struct VecOf<fsp_bf16> { using type = fsp_bf16x8; static constexpr int N = 8; };
+template <typename T> struct RowIsBf16 { static constexpr bool value = false; };
+template <> struct RowIsBf16<fsp_bf16> { static constexpr bool value = true; };
 
 template <typename T> __device__ __forceinline__ bool finite_t(T x) {
     return fabs(static_cast<double>(x)) <= 1.79769313486231570815e+308;
@@ -70,6 +78,20 @@ __device__ __forceinline__ double vcomp(fsp_u32x4 v, int e) { return static_cast
 // Exact widening of half e of a slot: v_cvt_f32_f16 (the high half of a dword through SDWA src0_sel:WORD_1, no shift), then
 // v_cvt_f64_f32.  Kernels keep fp16 denormals (float_denorm_mode_16_64 = 3), so a subnormal half arrives as its value.
 __device__ __forceinline__ double vcomp(fsp_f16x8 v, int e) { return static_cast<double>(static_cast<float>(v[e])); }
+// Exact widening of bf16 e of a slot (e is a constant after unrolling): the low element of a dword is dword << 16, the high one
+// dword & 0xffff0000, each taken as the bits of a float — one integer VALU op — then v_cvt_f64_f32.  No conversion that could
+// round; nothing depends on the fp16 denormal mode, but a bf16 subnormal is an fp32 subnormal and must survive v_cvt_f64_f32
+// (kernels keep fp32 denormals, float_denorm_mode_32 = 3).
+__device__ __forceinline__ float vcomp_f32(fsp_bf16x8 v, int e) {
+    const uint32_t w = static_cast<uint32_t>(v[e >> 1]);
+    return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
+}
+__device__ __forceinline__ double vcomp(fsp_bf16x8 v, int e) { return static_cast<double>(vcomp_f32(v, e)); }
+// raw elements e and e + 1 both finite.  (b & 0x7f80) == 0x7f80 is +-inf or NaN, and that exponent field is the widened float's:
+// one v_cmp_class_f32 on the float the widening has made anyway, instead of a mask and a compare on the raw dword.
+__device__ __forceinline__ bool vpair_finite(fsp_bf16x8 v, int e) {
+    return __builtin_isfinite(vcomp_f32(v, e)) && __builtin_isfinite(vcomp_f32(v, e + 1));
+}
 
 constexpr int kRefFilterMaxK = 32;   // top-k via per-wave k-th-smallest filter up to this k
 
@@ -541,7 +563,8 @@ __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, u
                     for (int e = 0; e < VN; e += 2) {
                         const double q0 = static_cast<double>(qrow[c0 + kk + e]);      // uniform address -> scalar load
                         const double q1 = static_cast<double>(qrow[c0 + kk + e + 1]);
-                        if constexpr (!RowIsBytes<TC>::value) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]);   // v_cmp_class on the raw element (a byte is always finite)
+                        if constexpr (RowIsBf16<TC>::value) ok = ok && vpair_finite(xv, e);   // the exponent fields of the two raw elements
+                        else if constexpr (!RowIsBytes<TC>::value) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]);   // v_cmp_class on the raw element (a byte is always finite)
                         const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   // exact widening
                         const double d0 = q0 - x0;                               // QSI.java:368
                         const double p0 = d0 * d0;
@@ -619,8 +642,10 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     // finite): there the per-query check stays, and such a row is scored with distance +inf as the reference scores it.
     // Half rows (FSPANN_F16) can hold +-inf and NaN like fp32 rows, and |x| <= 65504: against an fp32 query the sum tells again
     // (|q - x| < 2^129); against an fp64 query every raw half is tested (v_cmp_class_f16).
+    // bfloat16 rows (FSPANN_BF16) have fp32's range and are fp32 values: the fp32-row argument word for word against an fp32 query;
+    // against an fp64 query every raw element's exponent field is tested ((b & 0x7f80) == 0x7f80 is +-inf or NaN).
     constexpr bool kByteRows = RowIsBytes<TC>::value;
-    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows || RowIsHalf<TC>::value) && sizeof(TQ) == 4);
+    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows || RowIsHalf<TC>::value || RowIsBf16<TC>::value) && sizeof(TQ) == 4);
     const TC* __restrict__ cand = a.cand;
     const int64_t store_n = a.store_n, B = a.B;
     const int d = a.d, nchunks = a.nchunks;
@@ -821,7 +846,8 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
                     _Pragma("unroll") for (int e = 0; e < VN; e += 2) {                                             \
                         const double q0 = static_cast<double>(qrow[(C0) + kk + e]);      /* uniform address -> scalar load */ \
                         const double q1 = static_cast<double>(qrow[(C0) + kk + e + 1]);                             \
-                        if constexpr (!kSumTellsFinite && !kByteRows) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]); \
+                        if constexpr (!kSumTellsFinite && RowIsBf16<TC>::value) ok = ok && vpair_finite(xv, e);             \
+                        else if constexpr (!kSumTellsFinite && !kByteRows) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]); \
                         const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   /* exact widening */                \
                         const double d0 = q0 - x0;                               /* QSI.java:368 */                  \
                         const double p0 = d0 * d0;                                                                  \

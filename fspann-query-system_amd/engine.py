@@ -46,6 +46,47 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+class _Bfloat16:
+    """Marker for bfloat16 rows (FSPANN_BF16), passed as dtype= where numpy has no dtype to name: `pkg.bfloat16`."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "bfloat16"
+
+
+bfloat16 = _Bfloat16()
+
+
+def _bf16_bits(x, what):
+    """The uint16 bit patterns of rows handed over as bfloat16: a CPU torch.bfloat16 tensor as it is, a uint16 array as bit patterns,
+    a float array only if every value already is a bfloat16 (exact in fp32 with the low 16 bits of the pattern zero; NaN counts as
+    NaN).  The library never rounds for the caller."""
+    if type(x).__module__.split(".")[0] == "torch":
+        import torch
+        if x.dtype != torch.bfloat16:
+            raise N.FspannArgumentError(f"{what}(dtype=bfloat16): a torch tensor must be torch.bfloat16, not {x.dtype}")
+        if x.device.type != "cpu":
+            raise N.FspannArgumentError(f"{what}(dtype=bfloat16): the tensor must be on the CPU (device rows: store_attach_dev)")
+        return np.ascontiguousarray(x.contiguous().view(torch.int16).numpy()).view(np.uint16)
+    v = np.ascontiguousarray(x)
+    if v.dtype == np.uint16:
+        return v
+    if v.dtype.kind != "f":
+        raise N.FspannArgumentError(f"{what}(dtype=bfloat16): rows are a torch.bfloat16 tensor, uint16 bit patterns or a float array, not {v.dtype}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = v.astype(np.float32)
+        back = f.astype(v.dtype)
+        bits = f.view(np.uint32)
+        nan = v != v
+        exact = bool(np.all(((back == v) & ((bits & 0xFFFF) == 0)) | nan))
+    if not exact:
+        raise N.FspannArgumentError(f"{what}(dtype=bfloat16): every value must be exactly representable as a bfloat16 "
+                                    "(round the data yourself: the library never does)")
+    hi = (bits >> 16).astype(np.uint16)
+    hi[nan & ((hi & 0x7F) == 0)] |= 0x40       # a NaN whose payload sat in the low bits only stays a NaN
+    return hi
+
+
 def _dt(a):
     if a.dtype == np.float32:
         return N.F32
@@ -147,9 +188,18 @@ class FspannContext:
     def finalize(self):
         N.check(self.L.fspann_finalize(self._h))
 
-    def build_index(self, vectors, order=None):
+    def build_index(self, vectors, order=None, dtype=None):
         """A uint8 array goes to the library as bytes (FSPANN_U8: widened on the device; same tables, a quarter of the traffic),
-        a float16 array as halves (FSPANN_F16: same tables, half the traffic)."""
+        a float16 array as halves (FSPANN_F16: same tables, half the traffic).  dtype=bfloat16 (the package's marker): the rows
+        go up as bfloat16 bit patterns (FSPANN_BF16; a torch.bfloat16 tensor, uint16 patterns, or floats that already are
+        bfloat16 values, as in store_set): same tables, half the traffic."""
+        if dtype is bfloat16:
+            v = _bf16_bits(vectors, "build_index").reshape(-1, self.cfg.dim)
+            o = None if order is None else _c(order, np.int32)
+            N.check(self.L.fspann_build_index(self._h, v.shape[0], _p(v), N.BF16, _p(o)))
+            return
+        if dtype is not None:
+            raise N.FspannArgumentError("build_index(dtype=): only the bfloat16 marker is given by name; other rows are typed by their array")
         v = np.ascontiguousarray(vectors)
         if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
             v = v.astype(np.float64)
@@ -161,7 +211,13 @@ class FspannContext:
         """Incremental Setup: begin(n) -> append(rows of the next handles) ... -> finish(order) (fspann_build_begin / _append / _finish)."""
         N.check(self.L.fspann_build_begin(self._h, int(n_total)))
 
-    def build_append(self, rows):
+    def build_append(self, rows, dtype=None):
+        if dtype is bfloat16:
+            v = _bf16_bits(rows, "build_append").reshape(-1, self.cfg.dim)
+            N.check(self.L.fspann_build_append(self._h, v.shape[0], _p(v), N.BF16))
+            return
+        if dtype is not None:
+            raise N.FspannArgumentError("build_append(dtype=): only the bfloat16 marker is given by name; other rows are typed by their array")
         v = np.ascontiguousarray(rows)
         if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
             v = v.astype(np.float64)
@@ -385,7 +441,15 @@ class FspannContext:
         uint8 array is widened to float64 like every other non-float array.
         dtype=np.float16 keeps the rows as halves (FSPANN_F16): a float16 array as it is, any other array only if every value
         already is a half (it survives astype(float16) and back unchanged, NaN counting as NaN) — the library never rounds for
-        the caller.  Without it a float16 array is widened to float64 as well."""
+        the caller.  Without it a float16 array is widened to float64 as well.
+        dtype=bfloat16 (the package's marker; numpy has no such dtype) keeps the rows as bfloat16 (FSPANN_BF16): a CPU
+        torch.bfloat16 tensor as it is, a uint16 array as bit patterns, a float array only if every value already is a bfloat16
+        (exact in fp32 with the low 16 bits of the pattern zero, NaN counting as NaN).  store_dtype then reports the marker."""
+        if dtype is bfloat16:
+            v = _bf16_bits(vectors, "store_set").reshape(-1, self.cfg.dim)      # (raises before the store is touched)
+            N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), N.BF16))
+            self.store_dtype = bfloat16
+            return
         v = np.ascontiguousarray(vectors)
         if dtype is not None and np.dtype(dtype) == np.uint8:
             if v.dtype != np.uint8:
@@ -415,7 +479,7 @@ class FspannContext:
         self.store_dtype = v.dtype
 
     def store_attach_dev(self, n, ptr, dtype):
-        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8 or N.F16."""
+        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8, N.F16 or N.BF16."""
         N.check(self.L.fspann_store_attach_dev(self._h, int(n), ptr, dtype))
 
     def hbm_read_peak(self, nbytes=1 << 32, reps=5) -> float:
@@ -497,8 +561,8 @@ class FspannContext:
 
     def eval_metrics_typed_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride, ann_count_ptr, gt_ptr, gt_stride,
                                recall_ptr, ratio_ptr):
-        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries, or N.F16 rows with
-        N.F32 queries (recall and ratio against a resident half store without an fp32 copy)."""
+        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries, or N.F16 / N.BF16 rows
+        with N.F32 queries (recall and ratio against a resident half or bfloat16 store without an fp32 copy)."""
         N.check(self.L.fspann_eval_metrics_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride,
                                                      ann_count_ptr or None, gt_ptr, gt_stride, recall_ptr, ratio_ptr))
 

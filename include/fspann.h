@@ -69,6 +69,17 @@ extern "C" {
  * other query type.  A row holding +-inf or NaN is skipped, not scored (QSI.isValid).  A three-role tick over F16 rows runs the
  * stand-alone kernels in stream order (fspann_last_tick_fused says 0), results identical.                                      */
 #define FSPANN_F16 3
+/* bfloat16, handed over as 16-bit patterns b, value = the fp32 whose bit pattern is b << 16: that covers every bfloat16,
+ * subnormals, +-0, +-inf and NaN included, and each finite one is a double, so distances over bf16 rows widened on the fly are
+ * bit-identical to those over the same values held as fp32 / fp64, at half / a quarter of the bytes.  The library never rounds:
+ * the caller hands over bf16 bit patterns.  A ROW dtype only, with the standing of FSPANN_F16: accepted by fspann_store_set /
+ * _attach_dev (and everything that reads the store), by the cand_dtype of fspann_refine_dev, the ref_cand_dtype of
+ * fspann_tick_dev, the dtype of fspann_build_index / _append, and as the base of fspann_eval_metrics_typed_dev with FSPANN_F32
+ * queries; refused with FSPANN_E_ARG and a message naming FSPANN_BF16 wherever a QUERY dtype is given, by
+ * fspann_pointstore_encrypt / _open_batch, by fspann_groundtruth_typed_dev and by metrics with any other query type.  A row
+ * holding +-inf or NaN is skipped, not scored (QSI.isValid).  A three-role tick over BF16 rows runs the stand-alone kernels in
+ * stream order (fspann_last_tick_fused says 0), results identical.                                                            */
+#define FSPANN_BF16 4
 
 typedef struct fspann_ctx fspann_ctx;
 

@@ -125,6 +125,8 @@ def main():
             '    public static final int U8 = 2;',
             '    /** Rows only (FSPANN_F16): IEEE binary16 halves, value = the half widened exactly; refused wherever a query dtype is given. */',
             '    public static final int F16 = 3;',
+            '    /** Rows only (FSPANN_BF16): bfloat16 bit patterns, value = the fp32 with the bits b << 16; refused wherever a query dtype is given. */',
+            '    public static final int BF16 = 4;',
             '    public static final int OK = 0, E_STATE = -1, E_ARG = -2, E_NULL = -3, E_DEVICE = -4, E_NOMEM = -5, E_RANGE = -6;',
             '    /** fspann_tick field order for the long[] passed to tickDev. */',
             '    public static final String[] TICK_FIELDS = {' + ", ".join('"%s"' % f for f in TICK_FIELDS) + '};', '']

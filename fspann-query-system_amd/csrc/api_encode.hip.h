@@ -113,6 +113,7 @@ int fspann_encode_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int dtype, u
     if (dtype == FSPANN_F32) return launch_encode<float>(c, nq, static_cast<const float*>(q_dev), codes_dev, hashes_dev, bad_dev);
     if (dtype == FSPANN_F16) return refuse_f16("dtype");
     if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
+    if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
     return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
 }
 
@@ -124,6 +125,7 @@ int fspann_encode(fspann_ctx* c, int64_t nq, const void* q, int dtype, uint64_t*
     if (!q || !codes) return fail(FSPANN_E_NULL, "query vector is null");
     if (dtype == FSPANN_F16) return refuse_f16("dtype");
     if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
+    if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     const size_t esz = dtype == FSPANN_F64 ? 8 : 4;
     const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * esz;

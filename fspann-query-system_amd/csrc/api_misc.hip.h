@@ -44,7 +44,7 @@ int fspann_eval_metrics_dev(fspann_ctx* c, int64_t n, const float* base_dev, int
 
 }  // extern "C"
 namespace {
-const char* gt_dtype_name(int dt) { return dt == FSPANN_F32 ? "FSPANN_F32" : dt == FSPANN_F64 ? "FSPANN_F64" : dt == FSPANN_U8 ? "FSPANN_U8" : dt == FSPANN_F16 ? "FSPANN_F16" : dt == FSPANN_BF16 ? "FSPANN_BF16" : "unknown dtype"; }
+const char* gt_dtype_name(int dt) { return dt == FSPANN_F32 ? "FSPANN_F32" : dt == FSPANN_F64 ? "FSPANN_F64" : dt == FSPANN_U8 ? "FSPANN_U8" : dt == FSPANN_F16 ? "FSPANN_F16" : dt == FSPANN_BF16 ? "FSPANN_BF16" : dt == FSPANN_F8E4M3 ? "FSPANN_F8E4M3" : "unknown dtype"; }
 int gt8_digits(uint64_t v) {      // 8-bit digits that hold v
     int nd = 1;
     while (nd < 4 && (v >> (8 * nd)) != 0) nd++;
@@ -63,6 +63,9 @@ int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev,
                     gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
     if (base_dtype == FSPANN_BF16 || q_dtype == FSPANN_BF16)   // likewise: and a query is never a bfloat16
         return fail(FSPANN_E_ARG, "no ground truth over FSPANN_BF16 (base and query are both FSPANN_F32 or both FSPANN_U8): base %s, query %s",
+                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
+    if (base_dtype == FSPANN_F8E4M3 || q_dtype == FSPANN_F8E4M3)   // likewise: and a query is never an fp8
+        return fail(FSPANN_E_ARG, "no ground truth over FSPANN_F8E4M3 (base and query are both FSPANN_F32 or both FSPANN_U8): base %s, query %s",
                     gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
     if (base_dtype != q_dtype || (base_dtype != FSPANN_F32 && base_dtype != FSPANN_U8))
         return fail(FSPANN_E_ARG, "Base and query types must match (both fvecs or both bvecs): base %s, query %s", gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
@@ -129,7 +132,11 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
     if (!bf16 && (base_dtype == FSPANN_BF16 || q_dtype == FSPANN_BF16))
         return fail(FSPANN_E_ARG, "metrics take FSPANN_BF16 rows with FSPANN_F32 queries only (a query is never FSPANN_BF16): base %s, query %s",
                     gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    if (!f32 && !u8 && !f16 && !bf16)
+    const bool f8 = base_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32;
+    if (!f8 && (base_dtype == FSPANN_F8E4M3 || q_dtype == FSPANN_F8E4M3))
+        return fail(FSPANN_E_ARG, "metrics take FSPANN_F8E4M3 rows with FSPANN_F32 queries only (a query is never FSPANN_F8E4M3): base %s, query %s",
+                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
+    if (!f32 && !u8 && !f16 && !bf16 && !f8)
         return fail(FSPANN_E_ARG, "metrics take FSPANN_F32 rows with FSPANN_F32 queries, or FSPANN_U8 rows with FSPANN_U8 / FSPANN_F32 queries: base %s, query %s",
                     gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
     if (f32)
@@ -143,6 +150,9 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
                            static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     else if (bf16)    // a resident bfloat16 store, likewise
         hipLaunchKernelGGL((gt_metrics_typed_kernel<fsp_bf16, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const fsp_bf16*>(base_dev), n,
+                           static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+    else if (f8)      // a resident fp8 store, likewise
+        hipLaunchKernelGGL((gt_metrics_typed_kernel<fsp_f8e4m3, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const fsp_f8e4m3*>(base_dev), n,
                            static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     else if (q_dtype == FSPANN_U8)
         hipLaunchKernelGGL((gt_metrics_typed_kernel<uint8_t, uint8_t>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base, n, static_cast<const uint8_t*>(q_dev), dim, k,

@@ -47,6 +47,9 @@ int touch_store_ok(fspann_ctx* c) {
     else if (c->store_dtype == FSPANN_BF16) // so can a bfloat16
         hipLaunchKernelGGL(touch_store_valid_kernel<fsp_bf16>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const fsp_bf16*>(c->d_store),
                            c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
+    else if (c->store_dtype == FSPANN_F8E4M3)   // an fp8 has no infinity but two NaN patterns
+        hipLaunchKernelGGL(touch_store_valid_kernel<fsp_f8e4m3>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const fsp_f8e4m3*>(c->d_store),
+                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
     else if (c->store_dtype == FSPANN_F64)
         hipLaunchKernelGGL(touch_store_valid_kernel<double>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const double*>(c->d_store),
                            c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));

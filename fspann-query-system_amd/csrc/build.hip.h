@@ -61,6 +61,21 @@ __global__ __launch_bounds__(256) void build_widen_bf16_kernel(const fsp_bf16* _
     }
 }
 
+// Setup input as fp8 e4m3fn bytes (FSPANN_F8E4M3): widened to fp32 on the device by the hardware conversion (two v_cvt_pk_f32_fp8
+// per dword), exact for every e4m3 value — four elements per thread (one 4-byte load, one 16-byte store); a NaN element is then
+// refused by the encode as in an F32 build.
+__global__ __launch_bounds__(256) void build_widen_f8_kernel(const fsp_f8e4m3* __restrict__ in, int64_t n, float* __restrict__ out) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (i + 4 <= n) {
+        const int w = *reinterpret_cast<const int*>(in + i);
+        const f2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+        *reinterpret_cast<float4*>(out + i) = make_float4(lo[0], lo[1], hi[0], hi[1]);
+    } else {
+        for (int64_t j = i; j < n; j++) out[j] = static_cast<float>(in[j]);
+    }
+}
+
 __global__ __launch_bounds__(kRsThreads) void rs_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
                                                              int nblocks, uint32_t* __restrict__ tot) {
     __shared__ uint32_t h[256];

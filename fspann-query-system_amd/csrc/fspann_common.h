@@ -44,10 +44,12 @@ inline int fail(int code, const char* fmt, ...) {
     } while (0)
 
 // bytes per element of a dtype of include/fspann.h (the callers have checked which dtypes they take)
-inline size_t dtype_size(int dtype) { return dtype == FSPANN_F64 ? 8 : (dtype == FSPANN_U8 ? 1 : ((dtype == FSPANN_F16 || dtype == FSPANN_BF16) ? 2 : 4)); }
+inline size_t dtype_size(int dtype) {
+    return dtype == FSPANN_F64 ? 8 : ((dtype == FSPANN_U8 || dtype == FSPANN_F8E4M3) ? 1 : ((dtype == FSPANN_F16 || dtype == FSPANN_BF16) ? 2 : 4));
+}
 // the row dtypes: what fspann_store_set / _attach_dev, fspann_build_index / _append and the rows of a refinement take
 inline bool is_row_dtype(int dtype) {
-    return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16 || dtype == FSPANN_BF16;
+    return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16 || dtype == FSPANN_BF16 || dtype == FSPANN_F8E4M3;
 }
 // FSPANN_F16 given where no half can stand (a query, the point store, the ground truth): refused by name
 inline int refuse_f16(const char* what) {
@@ -56,6 +58,10 @@ inline int refuse_f16(const char* what) {
 // FSPANN_BF16 likewise
 inline int refuse_bf16(const char* what) {
     return fail(FSPANN_E_ARG, "%s FSPANN_BF16: bfloat16 is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
+}
+// FSPANN_F8E4M3 likewise
+inline int refuse_f8(const char* what) {
+    return fail(FSPANN_E_ARG, "%s FSPANN_F8E4M3: fp8 e4m3fn is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
 }
 
 // One FSPANN_BF16 row element: 16 bits b, value = the fp32 whose bit pattern is b << 16 (every bfloat16, subnormals, +-0, +-inf and
@@ -69,6 +75,28 @@ struct fsp_bf16 {
 static_assert(sizeof(fsp_bf16) == 2 && alignof(fsp_bf16) == 2, "a bf16 row element is two bytes");
 // an element is +-inf or NaN iff its exponent field is all ones
 __host__ __device__ __forceinline__ bool bf16_finite(fsp_bf16 x) { return (x.b & 0x7f80u) != 0x7f80u; }
+
+// One FSPANN_F8E4M3 row element: the OCP fp8 e4m3fn byte b = S EEEE MMM, bias 7 (E = 0: +-M/8 * 2^-6; else +-(1 + M/8) * 2^(E-7);
+// 0x7F / 0xFF NaN, no infinity, |x| <= 448).  A type of its own, so that an fp8 row is never taken for a uint8_t row or a flag
+// byte.  On the device the widening is the hardware's v_cvt_f32_fp8 (gfx950 converts the OCP format): exact, every e4m3 value is
+// a float; the host spells the definition out.
+struct fsp_f8e4m3 {
+    uint8_t b;
+    __host__ __device__ __forceinline__ explicit operator float() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(b), 0);
+#else
+        const int e = (b >> 3) & 15, m = b & 7;
+        const float mag = (e == 15 && m == 7) ? __builtin_nanf("") : e == 0 ? __builtin_ldexpf(static_cast<float>(m), -9)
+                                                                         : __builtin_ldexpf(static_cast<float>(8 + m), e - 10);
+        return (b & 0x80) ? -mag : mag;
+#endif
+    }
+    __host__ __device__ __forceinline__ explicit operator double() const { return static_cast<double>(static_cast<float>(*this)); }
+};
+static_assert(sizeof(fsp_f8e4m3) == 1 && alignof(fsp_f8e4m3) == 1, "an fp8 row element is one byte");
+// an element is NaN iff all seven bits under the sign are set (the format has no infinity)
+__host__ __device__ __forceinline__ bool f8e4m3_finite(fsp_f8e4m3 x) { return (x.b & 0x7fu) != 0x7fu; }
 
 // ---- order-key bit budget (DESIGN.md "Java order key") ----------------------------
 // key = score(10) | bucket(20) | seq(22); seq = (td*P + step)*S + pos is unique per tuple.

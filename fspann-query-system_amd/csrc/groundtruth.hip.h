@@ -194,7 +194,7 @@ __global__ __launch_bounds__(64) void gt_metrics_kernel(const float* __restrict_
 }
 
 // gt_metrics_kernel over typed rows and queries (fspann_eval_metrics_typed_dev): TB = uint8_t (FSPANN_U8: the integer 0..255,
-// exact in fp64) with TQ = uint8_t or float, or TB = _Float16 (FSPANN_F16: the half widened exactly) or fsp_bf16 (FSPANN_BF16: the bits shifted up, exact) with TQ = float; the same fp64 arithmetic and the same ordered fold, statement for statement.  The
+// exact in fp64) with TQ = uint8_t or float, or TB = _Float16 (FSPANN_F16: the half widened exactly) or fsp_bf16 (FSPANN_BF16: the bits shifted up, exact) or fsp_f8e4m3 (FSPANN_F8E4M3: the hardware conversion, exact) with TQ = float; the same fp64 arithmetic and the same ordered fold, statement for statement.  The
 // fp32 kernel above stays as it is and is what fspann_eval_metrics_dev launches: routed through this template it compiled to
 // the same instructions but for the operand order of one integer add, and that kernel is kept instruction-identical.
 template <typename TB, typename TQ>

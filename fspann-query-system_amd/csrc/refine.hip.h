@@ -63,6 +63,21 @@ typedef int32_t fsp_bf16x8 __attribute__((ext_vector_type(4)));
 template <> struct VecOf<fsp_bf16> { using type = fsp_bf16x8; static constexpr int N = 8; };
 template <typename T> struct RowIsBf16 { static constexpr bool value = false; };
 template <> struct RowIsBf16<fsp_bf16> { static constexpr bool value = true; };
+// FSPANN_F8E4M3 rows: the byte geometry of FSPANN_U8 (a 16-byte slot is 16 elements, byte e of the slot = bits [8 (e % 4),
+// 8 (e % 4) + 8) of dword e / 4).  The slot is held as two unsigned qwords: a native vector like the others, and a type of its
+// own, so that no overload takes it for a byte slot (unsigned dwords) or a bf16 slot (signed dwords); sixteen separate bytes would
+// be the natural spelling, but a conditional load of such a vector is legalised byte by byte and ends in scratch.  An element is an
+// OCP e4m3fn value and, unlike a byte, can be NaN (0x7F / 0xFF; the format has no infinity).
+typedef uint64_t fsp_f8x16 __attribute__((ext_vector_type(2)));
+template <> struct VecOf<fsp_f8e4m3> { using type = fsp_f8x16; static constexpr int N = 16; };
+template <typename T> struct RowIsF8 { static constexpr bool value = false; };
+template <> struct RowIsF8<fsp_f8e4m3> { static constexpr bool value = true; };
+// Which hardware conversion widens an fp8 slot (both exact; a switch so that the two can be A/B-ed): 0 = v_cvt_pk_f32_fp8, one
+// instruction per two elements (the word of the dword through SDWA src0_sel:WORD_1); 1 = v_cvt_f32_fp8, one per element (the byte
+// through SDWA src0_sel:BYTE_n).
+#ifndef FSPANN_F8_WIDEN
+#define FSPANN_F8_WIDEN 0
+#endif
 
 template <typename T> __device__ __forceinline__ bool finite_t(T x) {
     return fabs(static_cast<double>(x)) <= 1.79769313486231570815e+308;
@@ -91,6 +106,31 @@ __device__ __forceinline__ double vcomp(fsp_bf16x8 v, int e) { return static_cas
 // one v_cmp_class_f32 on the float the widening has made anyway, instead of a mask and a compare on the raw dword.
 __device__ __forceinline__ bool vpair_finite(fsp_bf16x8 v, int e) {
     return __builtin_isfinite(vcomp_f32(v, e)) && __builtin_isfinite(vcomp_f32(v, e + 1));
+}
+// Exact widening of fp8 e of a slot (e is a constant after unrolling): the hardware's OCP e4m3fn conversion of dword e / 4 — every
+// e4m3 value, subnormals included, is a normal fp32, so nothing depends on a denormal mode — then v_cvt_f64_f32.  The two elements
+// of a pair (e, e + 1) come out of one v_cvt_pk_f32_fp8.
+__device__ __forceinline__ float vcomp_f32(fsp_f8x16 v, int e) {
+    const int w = static_cast<int>(__builtin_bit_cast(fsp_u32x4, v)[e >> 2]);
+#if FSPANN_F8_WIDEN == 0
+    return (e & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true)[e & 1] : __builtin_amdgcn_cvt_pk_f32_fp8(w, false)[e & 1];
+#else
+    switch (e & 3) {
+    case 0: return __builtin_amdgcn_cvt_f32_fp8(w, 0);
+    case 1: return __builtin_amdgcn_cvt_f32_fp8(w, 1);
+    case 2: return __builtin_amdgcn_cvt_f32_fp8(w, 2);
+    default: return __builtin_amdgcn_cvt_f32_fp8(w, 3);
+    }
+#endif
+}
+__device__ __forceinline__ double vcomp(fsp_f8x16 v, int e) { return static_cast<double>(vcomp_f32(v, e)); }
+// raw elements e and e + 1 both finite.  (b & 0x7f) == 0x7f is NaN and nothing else is non-finite, so the four bytes of a dword
+// are tested at once, with the dword's first pair: under the mask 0x7f7f7f7f adding 1 to every byte carries into its bit 7 iff its
+// seven bits were all ones, and never into the next byte — three integer operations per four elements, nothing for the second pair.
+__device__ __forceinline__ bool vpair_finite(fsp_f8x16 v, int e) {
+    if (e & 2) return true;
+    const uint32_t w = __builtin_bit_cast(fsp_u32x4, v)[e >> 2];
+    return (((w & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u) == 0;
 }
 
 constexpr int kRefFilterMaxK = 32;   // top-k via per-wave k-th-smallest filter up to this k
@@ -563,7 +603,7 @@ __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, u
                     for (int e = 0; e < VN; e += 2) {
                         const double q0 = static_cast<double>(qrow[c0 + kk + e]);      // uniform address -> scalar load
                         const double q1 = static_cast<double>(qrow[c0 + kk + e + 1]);
-                        if constexpr (RowIsBf16<TC>::value) ok = ok && vpair_finite(xv, e);   // the exponent fields of the two raw elements
+                        if constexpr (RowIsBf16<TC>::value || RowIsF8<TC>::value) ok = ok && vpair_finite(xv, e);   // the exponent fields of the two raw elements (fp8: their NaN patterns)
                         else if constexpr (!RowIsBytes<TC>::value) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]);   // v_cmp_class on the raw element (a byte is always finite)
                         const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   // exact widening
                         const double d0 = q0 - x0;                               // QSI.java:368
@@ -644,8 +684,10 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     // (|q - x| < 2^129); against an fp64 query every raw half is tested (v_cmp_class_f16).
     // bfloat16 rows (FSPANN_BF16) have fp32's range and are fp32 values: the fp32-row argument word for word against an fp32 query;
     // against an fp64 query every raw element's exponent field is tested ((b & 0x7f80) == 0x7f80 is +-inf or NaN).
+    // fp8 rows (FSPANN_F8E4M3) are one byte but NOT always finite: 0x7F / 0xFF are NaN (no infinity, |x| <= 448).  Against an fp32
+    // query the sum tells (a NaN reaches it, |q - x| < 2^129 cannot overflow); against an fp64 query every element is tested.
     constexpr bool kByteRows = RowIsBytes<TC>::value;
-    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows || RowIsHalf<TC>::value || RowIsBf16<TC>::value) && sizeof(TQ) == 4);
+    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows || RowIsHalf<TC>::value || RowIsBf16<TC>::value || RowIsF8<TC>::value) && sizeof(TQ) == 4);
     const TC* __restrict__ cand = a.cand;
     const int64_t store_n = a.store_n, B = a.B;
     const int d = a.d, nchunks = a.nchunks;
@@ -846,7 +888,7 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
                     _Pragma("unroll") for (int e = 0; e < VN; e += 2) {                                             \
                         const double q0 = static_cast<double>(qrow[(C0) + kk + e]);      /* uniform address -> scalar load */ \
                         const double q1 = static_cast<double>(qrow[(C0) + kk + e + 1]);                             \
-                        if constexpr (!kSumTellsFinite && RowIsBf16<TC>::value) ok = ok && vpair_finite(xv, e);             \
+                        if constexpr (!kSumTellsFinite && (RowIsBf16<TC>::value || RowIsF8<TC>::value)) ok = ok && vpair_finite(xv, e); \
                         else if constexpr (!kSumTellsFinite && !kByteRows) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]); \
                         const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   /* exact widening */                \
                         const double d0 = q0 - x0;                               /* QSI.java:368 */                  \

@@ -14,9 +14,10 @@ constexpr int kTouchThreads = 256;
 constexpr int64_t kTouchTile = int64_t(kTouchThreads) * 16;   // handles per tile: one 16-byte load per thread
 constexpr int kTouchScanThreads = 1024;
 
-// an element of a row is finite (FSPANN_BF16: tested on its bits, like the float it widens to)
+// an element of a row is finite (FSPANN_BF16 / FSPANN_F8E4M3: tested on its bits, like the float it widens to)
 template <typename T> __device__ __forceinline__ bool touch_finite(T x) { return __builtin_isfinite(x); }
 __device__ __forceinline__ bool touch_finite(fsp_bf16 x) { return bf16_finite(x); }
+__device__ __forceinline__ bool touch_finite(fsp_f8e4m3 x) { return f8e4m3_finite(x); }
 
 // 1 per store row whose dim values are all finite — Refine's `ok` for a store row (QSI.isValid, QSI:407-413).  One wave per row.
 template <typename T>
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(kTouchThreads) void touch_mark_rows_kernel(const TQ
         if (id < 0 || id >= n_set) continue;          // (wave-uniform) not a handle of this index: nothing to mark
         const TC* r = rows + (qi * B + j) * d;
         bool bad = false;
-        if constexpr (sizeof(TC) > 1)                 // (FSPANN_U8 rows: a byte is always finite; FSPANN_F16 / FSPANN_BF16 rows are tested like floats)
+        if constexpr (!std::is_same<TC, uint8_t>::value)  // (FSPANN_U8 rows: a byte is always finite; F16 / BF16 / F8E4M3 rows are tested like floats)
             for (int i = lane; i < d; i += 64) bad = bad || !touch_finite(r[i]);
         const bool any_bad = __any(bad);
         if (lane == 0 && !any_bad) set[id] = 1;

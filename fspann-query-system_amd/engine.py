@@ -87,6 +87,50 @@ def _bf16_bits(x, what):
     return hi
 
 
+class _Float8E4M3:
+    """Marker for OCP fp8 e4m3fn rows (FSPANN_F8E4M3), passed as dtype= where numpy has no dtype to name: `pkg.float8_e4m3fn`."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "float8_e4m3fn"
+
+
+float8_e4m3fn = _Float8E4M3()
+
+
+def _f8_bits(x, what):
+    """The uint8 bit patterns of rows handed over as fp8 e4m3fn (S EEEE MMM, bias 7, no infinity, 0x7F / 0xFF NaN): a CPU
+    torch.float8_e4m3fn tensor as it is, a uint8 array as bit patterns, a float array only if every value already is an e4m3 value
+    (a multiple of 2^-9 with at most four significant bits and magnitude <= 448; NaN becomes 0x7F, -0.0 keeps its sign, +-inf is
+    refused: the format has none).  The library never rounds for the caller."""
+    if type(x).__module__.split(".")[0] == "torch":
+        import torch
+        if x.dtype != torch.float8_e4m3fn:
+            raise N.FspannArgumentError(f"{what}(dtype=float8_e4m3fn): a torch tensor must be torch.float8_e4m3fn, not {x.dtype}")
+        if x.device.type != "cpu":
+            raise N.FspannArgumentError(f"{what}(dtype=float8_e4m3fn): the tensor must be on the CPU (device rows: store_attach_dev)")
+        return np.ascontiguousarray(x.contiguous().view(torch.uint8).numpy())
+    v = np.ascontiguousarray(x)
+    if v.dtype == np.uint8:
+        return v
+    if v.dtype.kind != "f":
+        raise N.FspannArgumentError(f"{what}(dtype=float8_e4m3fn): rows are a torch.float8_e4m3fn tensor, uint8 bit patterns or a float array, not {v.dtype}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = v.astype(np.float64)                # (exact from every float type)
+        nan = f != f
+        a = np.where(nan, 0.0, np.abs(f))
+        m, e = np.frexp(a)                      # a = m * 2^e, m in [0.5, 1) (0 for a = 0)
+        exact = bool(np.all((a <= 448.0) & (a * 512.0 == np.floor(a * 512.0)) & (m * 16.0 == np.floor(m * 16.0))))
+    if not exact:
+        raise N.FspannArgumentError(f"{what}(dtype=float8_e4m3fn): every value must be exactly representable as an fp8 e4m3fn "
+                                    "(round the data yourself: the library never does)")
+    sub = a < 2.0 ** -6                         # subnormals and zero: M / 8 * 2^-6
+    bits = np.where(sub, a * 512.0, (e + 6) * 8 + (m * 16.0 - 8.0)).astype(np.uint8)
+    bits |= (np.signbit(f) & ~nan).astype(np.uint8) << 7
+    bits[nan] = 0x7F
+    return bits
+
+
 def _dt(a):
     if a.dtype == np.float32:
         return N.F32
@@ -192,14 +236,20 @@ class FspannContext:
         """A uint8 array goes to the library as bytes (FSPANN_U8: widened on the device; same tables, a quarter of the traffic),
         a float16 array as halves (FSPANN_F16: same tables, half the traffic).  dtype=bfloat16 (the package's marker): the rows
         go up as bfloat16 bit patterns (FSPANN_BF16; a torch.bfloat16 tensor, uint16 patterns, or floats that already are
-        bfloat16 values, as in store_set): same tables, half the traffic."""
+        bfloat16 values, as in store_set): same tables, half the traffic.  dtype=float8_e4m3fn likewise (FSPANN_F8E4M3; a
+        torch.float8_e4m3fn tensor, uint8 patterns, or floats that already are e4m3 values): same tables, a quarter of the traffic."""
         if dtype is bfloat16:
             v = _bf16_bits(vectors, "build_index").reshape(-1, self.cfg.dim)
             o = None if order is None else _c(order, np.int32)
             N.check(self.L.fspann_build_index(self._h, v.shape[0], _p(v), N.BF16, _p(o)))
             return
+        if dtype is float8_e4m3fn:
+            v = _f8_bits(vectors, "build_index").reshape(-1, self.cfg.dim)
+            o = None if order is None else _c(order, np.int32)
+            N.check(self.L.fspann_build_index(self._h, v.shape[0], _p(v), N.F8E4M3, _p(o)))
+            return
         if dtype is not None:
-            raise N.FspannArgumentError("build_index(dtype=): only the bfloat16 marker is given by name; other rows are typed by their array")
+            raise N.FspannArgumentError("build_index(dtype=): only the bfloat16 and float8_e4m3fn markers are given by name; other rows are typed by their array")
         v = np.ascontiguousarray(vectors)
         if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
             v = v.astype(np.float64)
@@ -216,8 +266,12 @@ class FspannContext:
             v = _bf16_bits(rows, "build_append").reshape(-1, self.cfg.dim)
             N.check(self.L.fspann_build_append(self._h, v.shape[0], _p(v), N.BF16))
             return
+        if dtype is float8_e4m3fn:
+            v = _f8_bits(rows, "build_append").reshape(-1, self.cfg.dim)
+            N.check(self.L.fspann_build_append(self._h, v.shape[0], _p(v), N.F8E4M3))
+            return
         if dtype is not None:
-            raise N.FspannArgumentError("build_append(dtype=): only the bfloat16 marker is given by name; other rows are typed by their array")
+            raise N.FspannArgumentError("build_append(dtype=): only the bfloat16 and float8_e4m3fn markers are given by name; other rows are typed by their array")
         v = np.ascontiguousarray(rows)
         if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
             v = v.astype(np.float64)
@@ -444,7 +498,15 @@ class FspannContext:
         the caller.  Without it a float16 array is widened to float64 as well.
         dtype=bfloat16 (the package's marker; numpy has no such dtype) keeps the rows as bfloat16 (FSPANN_BF16): a CPU
         torch.bfloat16 tensor as it is, a uint16 array as bit patterns, a float array only if every value already is a bfloat16
-        (exact in fp32 with the low 16 bits of the pattern zero, NaN counting as NaN).  store_dtype then reports the marker."""
+        (exact in fp32 with the low 16 bits of the pattern zero, NaN counting as NaN).  store_dtype then reports the marker.
+        dtype=float8_e4m3fn (the package's marker) keeps the rows as OCP fp8 e4m3fn (FSPANN_F8E4M3): a CPU torch.float8_e4m3fn
+        tensor as it is, a uint8 array as bit patterns, a float array only if every value already is an e4m3 value (NaN becomes
+        0x7F; +-inf is refused, the format has none).  store_dtype then reports the marker."""
+        if dtype is float8_e4m3fn:
+            v = _f8_bits(vectors, "store_set").reshape(-1, self.cfg.dim)        # (raises before the store is touched)
+            N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), N.F8E4M3))
+            self.store_dtype = float8_e4m3fn
+            return
         if dtype is bfloat16:
             v = _bf16_bits(vectors, "store_set").reshape(-1, self.cfg.dim)      # (raises before the store is touched)
             N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), N.BF16))
@@ -479,7 +541,7 @@ class FspannContext:
         self.store_dtype = v.dtype
 
     def store_attach_dev(self, n, ptr, dtype):
-        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8, N.F16 or N.BF16."""
+        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8, N.F16, N.BF16 or N.F8E4M3."""
         N.check(self.L.fspann_store_attach_dev(self._h, int(n), ptr, dtype))
 
     def hbm_read_peak(self, nbytes=1 << 32, reps=5) -> float:
@@ -561,8 +623,8 @@ class FspannContext:
 
     def eval_metrics_typed_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride, ann_count_ptr, gt_ptr, gt_stride,
                                recall_ptr, ratio_ptr):
-        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries, or N.F16 / N.BF16 rows
-        with N.F32 queries (recall and ratio against a resident half or bfloat16 store without an fp32 copy)."""
+        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries, or N.F16 / N.BF16 /
+        N.F8E4M3 rows with N.F32 queries (recall and ratio against a resident half, bfloat16 or fp8 store without an fp32 copy)."""
         N.check(self.L.fspann_eval_metrics_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride,
                                                      ann_count_ptr or None, gt_ptr, gt_stride, recall_ptr, ratio_ptr))
 

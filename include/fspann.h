@@ -80,6 +80,19 @@ extern "C" {
  * holding +-inf or NaN is skipped, not scored (QSI.isValid).  A three-role tick over BF16 rows runs the stand-alone kernels in
  * stream order (fspann_last_tick_fused says 0), results identical.                                                            */
 #define FSPANN_BF16 4
+/* OCP fp8 e4m3fn, handed over as bytes b = S EEEE MMM (bias 7): E = 0 is +-M/8 * 2^-6 (subnormals, +-0), E = 1..15 is
+ * +-(1 + M/8) * 2^(E-7); 0x7F and 0xFF are NaN and there is no infinity; the largest finite value is 448 (0x7E), the smallest
+ * subnormal 2^-9 (0x01).  Every finite value is a multiple of 2^-9 of magnitude <= 448, hence exactly a half, a float and a
+ * double, so distances over fp8 rows widened on the fly are bit-identical to those over the same values held as FSPANN_F16 /
+ * FSPANN_F32 / FSPANN_F64, at a half / a quarter / an eighth of the bytes.  The library never rounds or scales: the caller hands
+ * over e4m3 bit patterns.  A ROW dtype only, with the standing of FSPANN_BF16: accepted by fspann_store_set / _attach_dev (and
+ * everything that reads the store), by the cand_dtype of fspann_refine_dev, the ref_cand_dtype of fspann_tick_dev, the dtype of
+ * fspann_build_index / _append, and as the base of fspann_eval_metrics_typed_dev with FSPANN_F32 queries; refused with
+ * FSPANN_E_ARG and a message naming FSPANN_F8E4M3 wherever a QUERY dtype is given, by fspann_pointstore_encrypt / _open_batch,
+ * by fspann_groundtruth_typed_dev and by metrics with any other query type.  A row holding a NaN is skipped, not scored
+ * (QSI.isValid).  A three-role tick over F8E4M3 rows runs the stand-alone kernels in stream order (fspann_last_tick_fused says
+ * 0), results identical.                                                                                                    */
+#define FSPANN_F8E4M3 5
 
 typedef struct fspann_ctx fspann_ctx;
 
@@ -421,7 +434,8 @@ int fspann_eval_metrics_dev(fspann_ctx* ctx, int64_t n, const float* base_dev, i
  * Any other pair, FSPANN_F64, dim > 32768 with bytes, k outside 1..1024: FSPANN_E_ARG ("Base and query types must match
  * (both fvecs or both bvecs)", :226-228).
  * fspann_eval_metrics_typed_dev: FSPANN_F32 rows with FSPANN_F32 queries (= fspann_eval_metrics_dev), or FSPANN_U8 rows
- * with FSPANN_U8 or FSPANN_F32 queries (searches are made with fp32 queries); the same fp64 arithmetic and ordered fold.
+ * with FSPANN_U8 or FSPANN_F32 queries (searches are made with fp32 queries), or FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 rows
+ * with FSPANN_F32 queries (a resident half, bfloat16 or fp8 store as it is); the same fp64 arithmetic and ordered fold.
  * The [query chunk x n] distance matrix of either ground-truth call (fp64, or uint32 over bytes) lives in library scratch of at
  * most FSPANN_GT_SCRATCH_MB MiB (environment, read at fspann_ctx_create; default 8192); more queries run in chunks.         */
 int fspann_groundtruth_typed_dev(fspann_ctx* ctx, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev,

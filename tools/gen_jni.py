@@ -127,6 +127,8 @@ def main():
             '    public static final int F16 = 3;',
             '    /** Rows only (FSPANN_BF16): bfloat16 bit patterns, value = the fp32 with the bits b << 16; refused wherever a query dtype is given. */',
             '    public static final int BF16 = 4;',
+            '    /** Rows only (FSPANN_F8E4M3): OCP fp8 e4m3fn bit patterns (S EEEE MMM, bias 7, no infinity, 0x7F / 0xFF NaN); refused wherever a query dtype is given. */',
+            '    public static final int F8E4M3 = 5;',
             '    public static final int OK = 0, E_STATE = -1, E_ARG = -2, E_NULL = -3, E_DEVICE = -4, E_NOMEM = -5, E_RANGE = -6;',
             '    /** fspann_tick field order for the long[] passed to tickDev. */',
             '    public static final String[] TICK_FIELDS = {' + ", ".join('"%s"' % f for f in TICK_FIELDS) + '};', '']

@@ -1,9 +1,9 @@
-"""Dev tool: the refinement scan over FSPANN_F16 (and, with --rows f32,f16,bf16, FSPANN_BF16) rows beside the same scan over
+"""Dev tool: the refinement scan over FSPANN_F16 (and, with --rows f32,f16,bf16 / f32,f16,f8, FSPANN_BF16 / FSPANN_F8E4M3) rows beside the same scan over
 FSPANN_F32 rows, and fspann_search_store_dev end to end over an F16 (BF16) and an F32 store, at the shapes whose rows are float
 embeddings: BASELINE config #2, config #4's shard, config #3's shard and a RedCaps-like long list (the reference's
 REDCAPS_LAMBDA3 profile: B = 28 000 over 512-dimensional rows).
 
-  python tools/refine_f16_bench.py [--rows f32,f16[,bf16]] [--parts dense,gather,search] [--shapes ...] [--tag NAME]
+  python tools/refine_f16_bench.py [--rows f32,f16[,bf16][,f8]] [--parts dense,gather,search] [--shapes ...] [--tag NAME]
   AB_LIB=<path to another libfspann_hip.so> ... --rows f32        the same F32 readings with another build (the parent's)
 
 The method of tools/refine_u8_bench.py.  Per reading: device events around every launch on the context's stream, 8 warm-up + 40
@@ -13,9 +13,11 @@ a 2 M-row store), so neither dtype is served from the 256 MiB Infinity Cache; F3
 run over a 500 000-row store.  Each line: median us, algorithmic bytes (B d s + d 4 + k 8 per query, s = bytes per row element)
 over time, and the two lower bounds: bytes / 6.3 TB/s and the scan's fp64-pipe instructions per element (F32: two conversions,
 subtract, multiply, add = 5; F16: one more conversion for the row element = 6; BF16: one integer operation for the row element
-instead, which issues at the same rate = 6) / 39e12 lane-instructions per second.
-bf16 rows hold the halves' values rounded once more to bfloat16 (torch's rounding, the benchmark's own data: timings do not
-depend on the values); without bf16 in --rows every reading is taken exactly as before."""
+instead, which issues at the same rate = 6; F8E4M3: one v_cvt_pk_f32_fp8 per two row elements and a v_cvt_f64_f32 each = 5.5)
+/ 39e12 lane-instructions per second.
+bf16 / f8 rows hold the halves' values rounded once more to bfloat16 / fp8 e4m3fn (torch's rounding, the benchmark's own data:
+timings do not depend on the values, and a standard normal stays far below 448, so no fp8 row turns NaN); without bf16 / f8 in
+--rows every reading is taken exactly as before."""
 import argparse
 import os
 import sys
@@ -34,9 +36,9 @@ DEV = torch.device("cuda", 0)
 WARM, TIMED = 8, 40
 ROTATE_BYTES = 600 << 20
 HBM, FP64_RATE = 6.3e12, 39e12
-FP64_PER_ELEM = {"f32": 5, "f16": 6, "bf16": 6}
-ES = {"f32": 4, "f16": 2, "bf16": 2}
-TDT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+FP64_PER_ELEM = {"f32": 5, "f16": 6, "bf16": 6, "f8": 5.5}
+ES = {"f32": 4, "f16": 2, "bf16": 2, "f8": 1}
+TDT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "f8": torch.float8_e4m3fn}
 
 SHAPES = {   # name: (nq, B, d, k)
     "config2": (1024, 256, 128, 10),
@@ -53,7 +55,7 @@ PROFILES = {  # for the end-to-end readings: T, D, m, lambda, probes, hard_cap
 
 
 def cdt(rows):
-    return N.F16 if rows == "f16" else N.BF16 if rows == "bf16" else N.F32
+    return N.F16 if rows == "f16" else N.BF16 if rows == "bf16" else N.F8E4M3 if rows == "f8" else N.F32
 
 
 def timed(ctx, launches):
@@ -174,6 +176,8 @@ def bench_search(tag, rows_list, shapes):
                 c.store_set(X16, dtype=np.float16)
             elif rows == "bf16":
                 c.store_set(torch.from_numpy(X).to(torch.bfloat16), dtype=pkg.bfloat16)
+            elif rows == "f8":
+                c.store_set(torch.from_numpy(X).to(torch.float8_e4m3fn), dtype=pkg.float8_e4m3fn)
             else:
                 c.store_set(X)
             ctxs[rows] = c

@@ -23,6 +23,7 @@ U8 = 2     # rows only: unsigned bytes, value = the integer 0..255 (FSPANN_U8)
 F16 = 3    # rows only: IEEE binary16, value = the half widened exactly (FSPANN_F16)
 BF16 = 4   # rows only: bfloat16 bit patterns, value = the fp32 with the bits b << 16 (FSPANN_BF16)
 F8E4M3 = 5  # rows only: OCP fp8 e4m3fn bit patterns (S EEEE MMM, bias 7, no infinity, 0x7F / 0xFF NaN) (FSPANN_F8E4M3)
+I8 = 6     # rows only: signed bytes, value = the two's-complement integer -128..127 (FSPANN_I8)
 INT32_MAX = 2**31 - 1
 
 

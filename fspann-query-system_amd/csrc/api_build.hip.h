@@ -24,9 +24,9 @@ int build_begin_impl(fspann_ctx* c, int64_t n) {
 int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype) {
     const int d = c->cfg.dim, TD = c->TD, W = c->W;
     const size_t esz = dtype_size(dtype);
-    // byte rows, half rows, bfloat16 rows and fp8 rows go up as they are and are widened to fp32 on the device, exactly: the codes are those of the F32 build
+    // byte rows (unsigned and signed), half rows, bfloat16 rows and fp8 rows go up as they are and are widened to fp32 on the device, exactly: the codes are those of the F32 build
     const bool bytes_in = dtype == FSPANN_U8, halves_in = dtype == FSPANN_F16, bf16_in = dtype == FSPANN_BF16, f8_in = dtype == FSPANN_F8E4M3;
-    const bool widen = bytes_in || halves_in || bf16_in || f8_in;
+    const bool i8_in = dtype == FSPANN_I8, widen = bytes_in || halves_in || bf16_in || f8_in || i8_in;
     const int64_t chunk = 1 << 18;
     int rc;
     if (c->bld_done + nrows > c->bld_n) {       // more rows than the hint: grow the code buffer, keep what is coded
@@ -70,6 +70,11 @@ int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype)
             const int64_t ne = cn * d;
             hipLaunchKernelGGL(build_widen_f8_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
                                static_cast<const fsp_f8e4m3*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
+            FSP_HIP(hipGetLastError());
+        } else if (i8_in) {
+            const int64_t ne = cn * d;
+            hipLaunchKernelGGL(build_widen_i8_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
+                               static_cast<const int8_t*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
             FSP_HIP(hipGetLastError());
         }
         rc = fspann_encode_dev(c, cn, widen ? c->ws_io[1].p : c->ws_io[0].p, widen ? FSPANN_F32 : dtype, cdst, nullptr, static_cast<int32_t*>(c->ws_io[2].p));

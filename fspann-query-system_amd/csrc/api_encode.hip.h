@@ -114,6 +114,7 @@ int fspann_encode_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int dtype, u
     if (dtype == FSPANN_F16) return refuse_f16("dtype");
     if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
     if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
+    if (dtype == FSPANN_I8) return refuse_i8("dtype");
     return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
 }
 
@@ -126,6 +127,7 @@ int fspann_encode(fspann_ctx* c, int64_t nq, const void* q, int dtype, uint64_t*
     if (dtype == FSPANN_F16) return refuse_f16("dtype");
     if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
     if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
+    if (dtype == FSPANN_I8) return refuse_i8("dtype");
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     const size_t esz = dtype == FSPANN_F64 ? 8 : 4;
     const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * esz;

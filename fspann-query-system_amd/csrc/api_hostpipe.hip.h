@@ -60,6 +60,7 @@ int fspann_pointstore_encrypt(fspann_pointstore* ps, int64_t h0, int64_t cnt, co
     if (dtype == FSPANN_F16) return refuse_f16("dtype");
     if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
     if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
+    if (dtype == FSPANN_I8) return refuse_i8("dtype");
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     if (!ps->have_master) return fail(FSPANN_E_STATE, "Master key is not initialized");
     return guarded([&]() -> int {
@@ -100,6 +101,7 @@ int fspann_pointstore_open_batch(fspann_pointstore* ps, int64_t nq, int64_t B, c
     if (dst_dtype == FSPANN_F16) return refuse_f16("dst_dtype");
     if (dst_dtype == FSPANN_BF16) return refuse_bf16("dst_dtype");
     if (dst_dtype == FSPANN_F8E4M3) return refuse_f8("dst_dtype");
+    if (dst_dtype == FSPANN_I8) return refuse_i8("dst_dtype");
     if (dst_dtype != FSPANN_F32 && dst_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dst_dtype);
     return guarded([&]() -> int {
         if (dst_dtype == FSPANN_F32) pointstore_open_batch<float>(ps, nq, B, ids, count, static_cast<float*>(dst), out_ids, out_count, threads);

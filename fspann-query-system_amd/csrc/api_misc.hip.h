@@ -44,7 +44,7 @@ int fspann_eval_metrics_dev(fspann_ctx* c, int64_t n, const float* base_dev, int
 
 }  // extern "C"
 namespace {
-const char* gt_dtype_name(int dt) { return dt == FSPANN_F32 ? "FSPANN_F32" : dt == FSPANN_F64 ? "FSPANN_F64" : dt == FSPANN_U8 ? "FSPANN_U8" : dt == FSPANN_F16 ? "FSPANN_F16" : dt == FSPANN_BF16 ? "FSPANN_BF16" : dt == FSPANN_F8E4M3 ? "FSPANN_F8E4M3" : "unknown dtype"; }
+const char* gt_dtype_name(int dt) { return dt == FSPANN_F32 ? "FSPANN_F32" : dt == FSPANN_F64 ? "FSPANN_F64" : dt == FSPANN_U8 ? "FSPANN_U8" : dt == FSPANN_F16 ? "FSPANN_F16" : dt == FSPANN_BF16 ? "FSPANN_BF16" : dt == FSPANN_F8E4M3 ? "FSPANN_F8E4M3" : dt == FSPANN_I8 ? "FSPANN_I8" : "unknown dtype"; }
 int gt8_digits(uint64_t v) {      // 8-bit digits that hold v
     int nd = 1;
     while (nd < 4 && (v >> (8 * nd)) != 0) nd++;
@@ -53,7 +53,7 @@ int gt8_digits(uint64_t v) {      // 8-bit digits that hold v
 }  // namespace
 extern "C" {
 
-// Ground truth over typed rows.  (U8, U8): integer distances on the int8 matrix cores (groundtruth_u8.hip.h).
+// Ground truth over typed rows.  (U8, U8) and (I8, I8): integer distances on the int8 matrix cores (groundtruth_u8.hip.h).
 int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev, int q_dtype, int dim, int k,
                                  int32_t* out_ids_dev, double* out_d2_dev) {
     CHECK_CTX(c);
@@ -67,16 +67,19 @@ int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev,
     if (base_dtype == FSPANN_F8E4M3 || q_dtype == FSPANN_F8E4M3)   // likewise: and a query is never an fp8
         return fail(FSPANN_E_ARG, "no ground truth over FSPANN_F8E4M3 (base and query are both FSPANN_F32 or both FSPANN_U8): base %s, query %s",
                     gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    if (base_dtype != q_dtype || (base_dtype != FSPANN_F32 && base_dtype != FSPANN_U8))
+    // (FSPANN_I8 pairs with FSPANN_I8 only: signed with unsigned bytes, or with floats, is a pair that does not match)
+    if (base_dtype != q_dtype || (base_dtype != FSPANN_F32 && base_dtype != FSPANN_U8 && base_dtype != FSPANN_I8))
         return fail(FSPANN_E_ARG, "Base and query types must match (both fvecs or both bvecs): base %s, query %s", gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
     if (base_dtype == FSPANN_F32)
         return fspann_groundtruth_dev(c, n, static_cast<const float*>(base_dev), nq, static_cast<const float*>(q_dev), dim, k, out_ids_dev, out_d2_dev);
     if (n <= 0 || n >= (1LL << 31) || nq < 0 || dim <= 0) return fail(FSPANN_E_ARG, "Empty or malformed vector files (zero records).");
-    if (dim > kGt8MaxDim) return fail(FSPANN_E_ARG, "dim %d > %d: FSPANN_U8 distances would not fit 32 bits", dim, kGt8MaxDim);
+    if (dim > kGt8MaxDim) return fail(FSPANN_E_ARG, "dim %d > %d: %s distances would not fit 32 bits", dim, kGt8MaxDim, gt_dtype_name(base_dtype));
     if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
+    const bool sgn = base_dtype == FSPANN_I8;     // signed bytes: the gt8s_* kernels (no flip); everything else is shared
     const uint8_t* base = static_cast<const uint8_t*>(base_dev);
     const uint8_t* q = static_cast<const uint8_t*>(q_dev);
+    const int8_t* sbase = static_cast<const int8_t*>(base_dev);
     // scratch: |x'|^2 [n], |q'|^2 [chunk], then the [chunk x ld] uint32 distances, every part 256-byte aligned, rows 16-byte aligned
     const int64_t ld = (n + 3) & ~int64_t(3);
     const int64_t nbt = (n + kGt8Rows - 1) / kGt8Rows;
@@ -93,7 +96,9 @@ int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev,
     const bool aligned = (dim % 16 == 0) && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(q)) & 15) == 0;
     const int ndd = gt8_digits(static_cast<uint64_t>(dim) * 255 * 255), ndi = gt8_digits(static_cast<uint64_t>(n - 1));
     const dim3 ngrid(static_cast<unsigned>((n + 255) / 256));
-    if (aligned) hipLaunchKernelGGL(gt8_norm_kernel<true>, ngrid, dim3(256), 0, c->stream, base, n, dim, xn);
+    if (sgn && aligned) hipLaunchKernelGGL(gt8s_norm_kernel<true>, ngrid, dim3(256), 0, c->stream, sbase, n, dim, xn);
+    else if (sgn) hipLaunchKernelGGL(gt8s_norm_kernel<false>, ngrid, dim3(256), 0, c->stream, sbase, n, dim, xn);
+    else if (aligned) hipLaunchKernelGGL(gt8_norm_kernel<true>, ngrid, dim3(256), 0, c->stream, base, n, dim, xn);
     else hipLaunchKernelGGL(gt8_norm_kernel<false>, ngrid, dim3(256), 0, c->stream, base, n, dim, xn);
     FSP_HIP(hipGetLastError());
     for (int64_t s = 0; s < nq; s += chunk) {
@@ -102,7 +107,14 @@ int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev,
         const bool qal = aligned && (reinterpret_cast<uintptr_t>(qs) & 15) == 0;      // (dim % 16 == 0: every chunk starts aligned)
         const int nqb = static_cast<int>((cq + kGt8Q - 1) / kGt8Q);
         const dim3 qgrid(static_cast<unsigned>((cq + 255) / 256)), dgrid(static_cast<unsigned>(nbt * nqb));
-        if (qal) {
+        const int8_t* sqs = reinterpret_cast<const int8_t*>(qs);
+        if (sgn && qal) {
+            hipLaunchKernelGGL(gt8s_norm_kernel<true>, qgrid, dim3(256), 0, c->stream, sqs, cq, dim, qn);
+            hipLaunchKernelGGL(gt8s_dist_kernel<true>, dgrid, dim3(256), 0, c->stream, sbase, n, sqs, cq, dim, xn, qn, dist, ld, nqb);
+        } else if (sgn) {
+            hipLaunchKernelGGL(gt8s_norm_kernel<false>, qgrid, dim3(256), 0, c->stream, sqs, cq, dim, qn);
+            hipLaunchKernelGGL(gt8s_dist_kernel<false>, dgrid, dim3(256), 0, c->stream, sbase, n, sqs, cq, dim, xn, qn, dist, ld, nqb);
+        } else if (qal) {
             hipLaunchKernelGGL(gt8_norm_kernel<true>, qgrid, dim3(256), 0, c->stream, qs, cq, dim, qn);
             hipLaunchKernelGGL(gt8_dist_kernel<true>, dgrid, dim3(256), 0, c->stream, base, n, qs, cq, dim, xn, qn, dist, ld, nqb);
         } else {
@@ -136,7 +148,11 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
     if (!f8 && (base_dtype == FSPANN_F8E4M3 || q_dtype == FSPANN_F8E4M3))
         return fail(FSPANN_E_ARG, "metrics take FSPANN_F8E4M3 rows with FSPANN_F32 queries only (a query is never FSPANN_F8E4M3): base %s, query %s",
                     gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    if (!f32 && !u8 && !f16 && !bf16 && !f8)
+    const bool i8 = base_dtype == FSPANN_I8 && (q_dtype == FSPANN_I8 || q_dtype == FSPANN_F32);
+    if (!i8 && (base_dtype == FSPANN_I8 || q_dtype == FSPANN_I8))
+        return fail(FSPANN_E_ARG, "metrics take FSPANN_I8 rows with FSPANN_I8 / FSPANN_F32 queries only (a signed byte pairs with nothing else): base %s, query %s",
+                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
+    if (!f32 && !u8 && !f16 && !bf16 && !f8 && !i8)
         return fail(FSPANN_E_ARG, "metrics take FSPANN_F32 rows with FSPANN_F32 queries, or FSPANN_U8 rows with FSPANN_U8 / FSPANN_F32 queries: base %s, query %s",
                     gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
     if (f32)
@@ -153,6 +169,12 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
                            static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     else if (f8)      // a resident fp8 store, likewise
         hipLaunchKernelGGL((gt_metrics_typed_kernel<fsp_f8e4m3, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const fsp_f8e4m3*>(base_dev), n,
+                           static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+    else if (i8 && q_dtype == FSPANN_I8)    // signed bytes, against signed byte queries or the fp32 queries searches are made with
+        hipLaunchKernelGGL((gt_metrics_typed_kernel<int8_t, int8_t>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const int8_t*>(base_dev), n,
+                           static_cast<const int8_t*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+    else if (i8)
+        hipLaunchKernelGGL((gt_metrics_typed_kernel<int8_t, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const int8_t*>(base_dev), n,
                            static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     else if (q_dtype == FSPANN_U8)
         hipLaunchKernelGGL((gt_metrics_typed_kernel<uint8_t, uint8_t>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base, n, static_cast<const uint8_t*>(q_dev), dim, k,

@@ -118,14 +118,15 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
                 c->refine_fix_used = true;
             }
         }
-        if constexpr ((std::is_same<TC, uint8_t>::value || std::is_same<TC, _Float16>::value || std::is_same<TC, fsp_bf16>::value || std::is_same<TC, fsp_f8e4m3>::value) &&
-                      std::is_same<TQ, float>::value && DC * sizeof(TC) == 128) {
+        if constexpr ((std::is_same<TC, uint8_t>::value || std::is_same<TC, _Float16>::value || std::is_same<TC, fsp_bf16>::value || std::is_same<TC, fsp_f8e4m3>::value ||
+                       std::is_same<TC, int8_t>::value) && std::is_same<TQ, float>::value && DC * sizeof(TC) == 128) {
             if (c->refine_fix_dev && nchunks == 1) {
-                // FSPANN_U8 / FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 rows: the same hand-over, the kernel with the row type as a template parameter
+                // FSPANN_U8 / FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 / FSPANN_I8 rows: the same hand-over, the kernel with the row type as a template parameter
                 auto fk = refine_stream_fix_kernel<TC, GATHER>;
                 const size_t flds = std::max(lds, c->refine_fix_lds);
-                const unsigned abit = std::is_same<TC, fsp_f8e4m3>::value ? (GATHER ? (1u << 30) : (1u << 31))      // (a bit pair per row type: one kernel each)
-                                      : (sizeof(TC) == 1) ? (GATHER ? (1u << 24) : (1u << 25))
+                const uint64_t abit = std::is_same<TC, int8_t>::value ? (GATHER ? (uint64_t(1) << 32) : (uint64_t(1) << 33))   // (a bit pair per row type: one kernel each)
+                                      : std::is_same<TC, fsp_f8e4m3>::value ? (GATHER ? (1u << 30) : (1u << 31))
+                                      : std::is_same<TC, uint8_t>::value ? (GATHER ? (1u << 24) : (1u << 25))
                                       : std::is_same<TC, fsp_bf16>::value ? (GATHER ? (1u << 28) : (1u << 29)) : (GATHER ? (1u << 26) : (1u << 27));
                 if (!(c->attr_mask & abit)) {
                     FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
@@ -188,9 +189,9 @@ int launch_refine_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int6
     const int dc_env = c->knob_refine_dc;
     int rc;
     // FSPANN_U8 rows: a tile is 128 bytes = 128 dims; FSPANN_REFINE_DC (32 / 64 / 128 dims) is an fp32 notion and is ignored
-    // FSPANN_F16 and FSPANN_BF16 rows likewise: a tile is 128 bytes = 64 dims; FSPANN_F8E4M3 rows have the byte geometry of FSPANN_U8
+    // FSPANN_F16 and FSPANN_BF16 rows likewise: a tile is 128 bytes = 64 dims; FSPANN_F8E4M3 and FSPANN_I8 rows have the byte geometry of FSPANN_U8
     if constexpr (std::is_same<TC, _Float16>::value || std::is_same<TC, fsp_bf16>::value) rc = launch_refine_dc<TC, TQ, 64, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    else if constexpr (std::is_same<TC, uint8_t>::value || std::is_same<TC, fsp_f8e4m3>::value) rc = launch_refine_dc<TC, TQ, 128, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    else if constexpr (std::is_same<TC, uint8_t>::value || std::is_same<TC, fsp_f8e4m3>::value || std::is_same<TC, int8_t>::value) rc = launch_refine_dc<TC, TQ, 128, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
     else if (dc_env == DC0 * 2) rc = launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
     else if (dc_env == DC0 * 4) rc = launch_refine_dc<TC, TQ, DC0 * 4, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
     else rc = launch_refine_dc<TC, TQ, DC0, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
@@ -218,10 +219,13 @@ int refine_store_list(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
     if (c->store_dtype == FSPANN_BF16 && q_dtype == FSPANN_F64) FSP_REF(fsp_bf16, double);
     if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32) FSP_REF(fsp_f8e4m3, float);
     if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F64) FSP_REF(fsp_f8e4m3, double);
+    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F32) FSP_REF(int8_t, float);
+    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F64) FSP_REF(int8_t, double);
 #undef FSP_REF
     if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
     if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
     if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
+    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
     if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     return fail(FSPANN_E_ARG, "unknown dtype");
 }
@@ -257,10 +261,13 @@ int fspann_refine_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
     if (cand_dtype == FSPANN_BF16 && q_dtype == FSPANN_F64) FSP_REF(fsp_bf16, double);
     if (cand_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32) FSP_REF(fsp_f8e4m3, float);
     if (cand_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F64) FSP_REF(fsp_f8e4m3, double);
+    if (cand_dtype == FSPANN_I8 && q_dtype == FSPANN_F32) FSP_REF(int8_t, float);
+    if (cand_dtype == FSPANN_I8 && q_dtype == FSPANN_F64) FSP_REF(int8_t, double);
 #undef FSP_REF
     if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
     if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
     if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
+    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
     if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     return fail(FSPANN_E_ARG, "unknown dtype");
 }
@@ -277,6 +284,7 @@ int fspann_refine(fspann_ctx* c, int64_t nq, const void* q, const void* cand, in
     if (dtype == FSPANN_F16) return fail(FSPANN_E_ARG, "dtype FSPANN_F16: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (half rows: fspann_refine_dev)");
     if (dtype == FSPANN_BF16) return fail(FSPANN_E_ARG, "dtype FSPANN_BF16: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (bfloat16 rows: fspann_refine_dev)");
     if (dtype == FSPANN_F8E4M3) return fail(FSPANN_E_ARG, "dtype FSPANN_F8E4M3: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (fp8 rows: fspann_refine_dev)");
+    if (dtype == FSPANN_I8) return fail(FSPANN_E_ARG, "dtype FSPANN_I8: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (signed byte rows: fspann_refine_dev)");
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     const size_t esz = dtype == FSPANN_F64 ? 8 : 4;
     const int d = c->cfg.dim;
@@ -434,10 +442,13 @@ int fspann_refine_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     if (c->store_dtype == FSPANN_BF16 && q_dtype == FSPANN_F64) FSP_REF(fsp_bf16, double);
     if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32) FSP_REF(fsp_f8e4m3, float);
     if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F64) FSP_REF(fsp_f8e4m3, double);
+    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F32) FSP_REF(int8_t, float);
+    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F64) FSP_REF(int8_t, double);
 #undef FSP_REF
     if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
     if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
     if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
+    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
     if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     return fail(FSPANN_E_ARG, "unknown dtype");
 }
@@ -454,6 +465,7 @@ int fspann_refine_store(fspann_ctx* c, int64_t nq, const void* q, int q_dtype, i
     if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
     if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
     if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
+    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
     if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * (q_dtype == FSPANN_F64 ? 8 : 4);
     const size_t ib = static_cast<size_t>(nq) * B * 4, nb = static_cast<size_t>(nq) * 4;
@@ -536,6 +548,10 @@ int fspann_store_gather_dev(fspann_ctx* c, int64_t nq, const int32_t* sel_ids_de
         const int vec_ok = (d % 16 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
         hipLaunchKernelGGL(store_gather_kernel<fsp_f8e4m3>, dim3(grid), dim3(256), 0, c->stream, static_cast<const fsp_f8e4m3*>(c->d_store), d,
                            sel_ids_dev, sel_count_dev, B, nq, static_cast<fsp_f8e4m3*>(cand_dev), vec_ok);
+    } else if (c->store_dtype == FSPANN_I8) {
+        const int vec_ok = (d % 16 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
+        hipLaunchKernelGGL(store_gather_kernel<int8_t>, dim3(grid), dim3(256), 0, c->stream, static_cast<const int8_t*>(c->d_store), d,
+                           sel_ids_dev, sel_count_dev, B, nq, static_cast<int8_t*>(cand_dev), vec_ok);
     } else if (c->store_dtype == FSPANN_U8) {
         const int vec_ok = (d % 16 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
         hipLaunchKernelGGL(store_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, c->stream, static_cast<const uint8_t*>(c->d_store), d,

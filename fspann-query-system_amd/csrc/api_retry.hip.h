@@ -234,6 +234,7 @@ int fspann_search_retry_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev,
     if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");     // (whether or not a query is left to finish)
     if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");     // (whether or not a query is left to finish)
     if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");     // (whether or not a query is left to finish)
+    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");        // (whether or not a query is left to finish)
     int rc = check_retry_args(c, nq, q_dev, B, k, out_ids_dev, out_dist_dev, out_count_dev);
     if (rc || nq == 0) return rc;
     SearchArea sa;

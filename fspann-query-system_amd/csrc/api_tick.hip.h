@@ -129,8 +129,8 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         // (the same conditions launch_refine_dc takes its refine_stream_fix_kernel under — incl. the default tile width: with
         // FSPANN_REFINE_DC = 64 / 128 the plain scan would run first and read PENDING as "no rows")
         // (FSPANN_U8 rows: the U8 refine_stream_fix_kernel, 16 dims per 16-byte slot, always at its one tile width)
-        // (FSPANN_F16 / FSPANN_BF16 rows: the same overload, 8 dims per slot; FSPANN_F8E4M3 rows: 16 dims per slot, like U8)
-        const bool rows_ok = (rows_dtype == FSPANN_U8 || rows_dtype == FSPANN_F8E4M3) ? (d % 16 == 0) : (rows_dtype == FSPANN_F16 || rows_dtype == FSPANN_BF16) ? (d % 8 == 0)
+        // (FSPANN_F16 / FSPANN_BF16 rows: the same overload, 8 dims per slot; FSPANN_F8E4M3 and FSPANN_I8 rows: 16 dims per slot, like U8)
+        const bool rows_ok = (rows_dtype == FSPANN_U8 || rows_dtype == FSPANN_F8E4M3 || rows_dtype == FSPANN_I8) ? (d % 16 == 0) : (rows_dtype == FSPANN_F16 || rows_dtype == FSPANN_BF16) ? (d % 8 == 0)
                                                      : (rows_dtype == FSPANN_F32 && (d % 4 == 0) && (c->knob_refine_dc == 0 || c->knob_refine_dc == 32));
         const bool stream_ok = rows_ok &&
                                t->ref_q_dtype == FSPANN_F32 && nchunks == 1 &&

@@ -39,7 +39,7 @@ int touch_store_ok(fspann_ctx* c) {
     if (rc) return rc;
     const int d = c->cfg.dim;
     const unsigned grid = static_cast<unsigned>((c->store_n + kTouchThreads / 64 - 1) / (kTouchThreads / 64));
-    if (c->store_dtype == FSPANN_U8)      // a byte is always finite: every row is valid
+    if (c->store_dtype == FSPANN_U8 || c->store_dtype == FSPANN_I8)   // a byte, unsigned or signed, is always finite: every row is valid
         FSP_HIP(hipMemsetAsync(c->store_ok.p, 1, static_cast<size_t>(c->store_n), c->stream));
     else if (c->store_dtype == FSPANN_F16)  // a half can be +-inf or NaN, like a float
         hipLaunchKernelGGL(touch_store_valid_kernel<_Float16>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const _Float16*>(c->d_store),

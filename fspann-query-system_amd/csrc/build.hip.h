@@ -34,6 +34,19 @@ __global__ __launch_bounds__(256) void build_widen_u8_kernel(const uint8_t* __re
     }
 }
 
+// Setup input as signed bytes (FSPANN_I8: the integers -128..127): widened to fp32 on the device, exactly (a sign-extending bit-field
+// extract and v_cvt_f32_i32 per element), four elements per thread; the encode kernels then see what an F32 build would have uploaded.
+__global__ __launch_bounds__(256) void build_widen_i8_kernel(const int8_t* __restrict__ in, int64_t n, float* __restrict__ out) {
+    const int64_t i = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+    if (i + 4 <= n) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(in + i);
+        *reinterpret_cast<float4*>(out + i) = make_float4(static_cast<float>(static_cast<int32_t>(w << 24) >> 24), static_cast<float>(static_cast<int32_t>(w << 16) >> 24),
+                                                          static_cast<float>(static_cast<int32_t>(w << 8) >> 24), static_cast<float>(static_cast<int32_t>(w) >> 24));
+    } else {
+        for (int64_t j = i; j < n; j++) out[j] = static_cast<float>(in[j]);
+    }
+}
+
 // Setup input as halves (FSPANN_F16): widened to fp32 on the device, exactly (every half, subnormals, infinities and NaN
 // included, is an fp32 value), four elements per thread; a non-finite element is then refused by the encode as in an F32 build.
 __global__ __launch_bounds__(256) void build_widen_f16_kernel(const _Float16* __restrict__ in, int64_t n, float* __restrict__ out) {

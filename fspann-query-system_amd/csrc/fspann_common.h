@@ -45,11 +45,12 @@ inline int fail(int code, const char* fmt, ...) {
 
 // bytes per element of a dtype of include/fspann.h (the callers have checked which dtypes they take)
 inline size_t dtype_size(int dtype) {
-    return dtype == FSPANN_F64 ? 8 : ((dtype == FSPANN_U8 || dtype == FSPANN_F8E4M3) ? 1 : ((dtype == FSPANN_F16 || dtype == FSPANN_BF16) ? 2 : 4));
+    return dtype == FSPANN_F64 ? 8 : ((dtype == FSPANN_U8 || dtype == FSPANN_F8E4M3 || dtype == FSPANN_I8) ? 1 : ((dtype == FSPANN_F16 || dtype == FSPANN_BF16) ? 2 : 4));
 }
 // the row dtypes: what fspann_store_set / _attach_dev, fspann_build_index / _append and the rows of a refinement take
 inline bool is_row_dtype(int dtype) {
-    return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16 || dtype == FSPANN_BF16 || dtype == FSPANN_F8E4M3;
+    return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16 || dtype == FSPANN_BF16 || dtype == FSPANN_F8E4M3 ||
+           dtype == FSPANN_I8;
 }
 // FSPANN_F16 given where no half can stand (a query, the point store, the ground truth): refused by name
 inline int refuse_f16(const char* what) {
@@ -62,6 +63,10 @@ inline int refuse_bf16(const char* what) {
 // FSPANN_F8E4M3 likewise
 inline int refuse_f8(const char* what) {
     return fail(FSPANN_E_ARG, "%s FSPANN_F8E4M3: fp8 e4m3fn is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
+}
+// FSPANN_I8 likewise (an int8 row element is a plain int8_t: the integer it holds, always finite)
+inline int refuse_i8(const char* what) {
+    return fail(FSPANN_E_ARG, "%s FSPANN_I8: signed int8 is a row dtype only (store, refine rows, Setup input, metrics and ground truth over int8 pairs); this one is FSPANN_F32 or FSPANN_F64", what);
 }
 
 // One FSPANN_BF16 row element: 16 bits b, value = the fp32 whose bit pattern is b << 16 (every bfloat16, subnormals, +-0, +-inf and
@@ -211,7 +216,7 @@ struct fspann_ctx {
     bool rt_on = false;
     fspann::DevBuf ws_search;        // codes / F_q ids / counts of fspann_search_store_dev
     fspann::DevBuf ws_retry;         // pick list, its count, retried / scored of fspann_search_retry_dev (api_retry.hip.h)
-    unsigned attr_mask = 0;          // kernels whose dynamic-LDS ceiling has been raised on this context's device
+    uint64_t attr_mask = 0;          // kernels whose dynamic-LDS ceiling has been raised on this context's device (one bit per kernel; bits 32-33: the FSPANN_I8 hand-over pair)
     int ovf_flip = 0;                // which of the two overflow counters the last bounded select used
     unsigned ovf_gen_seen = 0;       // ws_ovf.gen whose counters have been zeroed (0 = never)
     int last_route_lazy = 0;         // 1 if the last fspann_route[_dev] ran the bounded select

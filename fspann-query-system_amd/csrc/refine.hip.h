@@ -49,6 +49,13 @@ typedef uint32_t fsp_u32x4 __attribute__((ext_vector_type(4)));
 template <> struct VecOf<uint8_t> { using type = fsp_u32x4; static constexpr int N = 16; };
 template <typename T> struct RowIsBytes { static constexpr bool value = false; };
 template <> struct RowIsBytes<uint8_t> { static constexpr bool value = true; };
+// FSPANN_I8 rows: the same byte geometry, a row element is the two's-complement integer -128..127, always finite like a byte.  The
+// slot is held as two SIGNED qwords: a native vector like the others, and a type of its own, so that no overload takes it for an
+// unsigned byte slot (unsigned dwords), a bf16 slot (signed dwords) or an fp8 slot (unsigned qwords).
+typedef int64_t fsp_i8x16 __attribute__((ext_vector_type(2)));
+typedef int32_t fsp_i32x4 __attribute__((ext_vector_type(4)));
+template <> struct VecOf<int8_t> { using type = fsp_i8x16; static constexpr int N = 16; };
+template <> struct RowIsBytes<int8_t> { static constexpr bool value = true; };
 // FSPANN_F16 rows: a 16-byte slot is 8 IEEE binary16 elements (four dwords, two halves each); an element is the half widened
 // exactly (half -> float -> double: every finite half, subnormals included, is a double), and unlike a byte it can be +-inf or NaN.
 typedef _Float16 fsp_f16x8 __attribute__((ext_vector_type(8)));
@@ -90,6 +97,13 @@ __device__ __forceinline__ double vcomp(fsp_f64x2 v, int e) { return v[e]; }
 // and against keeping the query's tile as fp64 in LDS instead of converting it per element: within 5 % of each other
 //  — every vector instruction of this loop issues at the same rate, so the plain expression stays.
 __device__ __forceinline__ double vcomp(fsp_u32x4 v, int e) { return static_cast<double>((v[e >> 2] >> (8 * (e & 3))) & 0xFFu); }
+// Exact widening of signed byte e of a slot (e is a constant after unrolling): the byte's sign is extended by a left shift to the
+// top of its dword and an arithmetic shift back (one v_bfe_i32; for the top byte the arithmetic shift alone), then v_cvt_f64_i32
+// — the instruction count of the unsigned byte above.
+__device__ __forceinline__ double vcomp(fsp_i8x16 v, int e) {
+    const int32_t w = __builtin_bit_cast(fsp_i32x4, v)[e >> 2];
+    return static_cast<double>(static_cast<int32_t>(static_cast<uint32_t>(w) << (24 - 8 * (e & 3))) >> 24);
+}
 // Exact widening of half e of a slot: v_cvt_f32_f16 (the high half of a dword through SDWA src0_sel:WORD_1, no shift), then
 // v_cvt_f64_f32.  Kernels keep fp16 denormals (float_denorm_mode_16_64 = 3), so a subnormal half arrives as its value.
 __device__ __forceinline__ double vcomp(fsp_f16x8 v, int e) { return static_cast<double>(static_cast<float>(v[e])); }
@@ -677,7 +691,7 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     // fp32 rows against an fp32 query: |q - x| < 2^129, so the fp64 sum of squares cannot overflow, and a NaN or an infinity
     // in the row always reaches the sum — "every element finite" (QSI.isValid, QSI:407-413) is "the sum is finite", one test
     // per row instead of one per element (a sixth of the scan's vector instructions).
-    // Byte rows (FSPANN_U8) are always finite, so no row element is ever tested; against an fp32 query the sum tells about the
+    // Byte rows (FSPANN_U8, FSPANN_I8) are always finite, so no row element is ever tested; against an fp32 query the sum tells about the
     // QUERY in the same way (|q - x| < 2^129 again).  Against an fp64 query it does not (1e200 squared overflows with every element
     // finite): there the per-query check stays, and such a row is scored with distance +inf as the reference scores it.
     // Half rows (FSPANN_F16) can hold +-inf and NaN like fp32 rows, and |x| <= 65504: against an fp32 query the sum tells again

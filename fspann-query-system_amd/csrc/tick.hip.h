@@ -17,7 +17,7 @@
 // batch) is redone with the full select by the workgroup that refines it one tick later — before it scans.  That removes
 // the hand-back launch of fspann_route_dev (an empty dependent kernel costs ~4.5 us on this runtime).
 //
-// tick_kernel is fp32-only (queries and rows).  A tick over FSPANN_U8, FSPANN_F16, FSPANN_BF16 or FSPANN_F8E4M3 rows that would have fused runs the stand-alone kernels in
+// tick_kernel is fp32-only (queries and rows).  A tick over FSPANN_U8, FSPANN_I8, FSPANN_F16, FSPANN_BF16 or FSPANN_F8E4M3 rows that would have fused runs the stand-alone kernels in
 // stream order instead (fspann_last_tick_fused says 0; results identical); a refine-only tick with a hand-over buffer keeps its
 // one launch through the typed refine_stream_fix_kernel overload below.
 #pragma once
@@ -159,8 +159,8 @@ __global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_fix_
                                                                 RefineRouteFix{fix_dev, smem});
 }
 
-// The same kernel over FSPANN_U8 / FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 rows (one 128-byte tile per 128 / 64 / 64 / 128 dims; an overload with the row type as a template parameter, so
-// that the fp32 kernel above keeps its symbol and its code): a U8, F16, BF16 or F8E4M3 batch keeps the front pipeline.
+// The same kernel over FSPANN_U8 / FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 / FSPANN_I8 rows (one 128-byte tile per 128 / 64 / 64 / 128 / 128 dims; an overload with the row type as a template parameter, so
+// that the fp32 kernel above keeps its symbol and its code): a U8, F16, BF16, F8E4M3 or I8 batch keeps the front pipeline.
 template <typename TC, bool GATHER>
 __global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_fix_kernel(const RefineArgs<TC, float> a, const int64_t nq,
                                                                                        const RouteParams* __restrict__ fix_dev) {

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kTouchThreads) void touch_mark_rows_kernel(const TQ
         if (id < 0 || id >= n_set) continue;          // (wave-uniform) not a handle of this index: nothing to mark
         const TC* r = rows + (qi * B + j) * d;
         bool bad = false;
-        if constexpr (!std::is_same<TC, uint8_t>::value)  // (FSPANN_U8 rows: a byte is always finite; F16 / BF16 / F8E4M3 rows are tested like floats)
+        if constexpr (!std::is_same<TC, uint8_t>::value && !std::is_same<TC, int8_t>::value)  // (FSPANN_U8 / FSPANN_I8 rows: a byte is always finite; F16 / BF16 / F8E4M3 rows are tested like floats)
             for (int i = lane; i < d; i += 64) bad = bad || !touch_finite(r[i]);
         const bool any_bad = __any(bad);
         if (lane == 0 && !any_bad) set[id] = 1;

@@ -131,6 +131,19 @@ def _f8_bits(x, what):
     return bits
 
 
+def _i8_rows(x, what):
+    """Rows handed over as signed bytes (FSPANN_I8): an int8 array as it is, any other array only if every value is an integer in
+    -128..127 (NaN and +-inf are not).  No scale and no zero point: the library never quantises for the caller."""
+    v = np.ascontiguousarray(x)
+    if v.dtype == np.int8:
+        return v
+    with np.errstate(invalid="ignore"):
+        exact = v.dtype.kind in "biuf" and bool(np.all((v >= -128) & (v <= 127) & (v == np.floor(v))))
+    if not exact:
+        raise N.FspannArgumentError(f"{what}(dtype=int8): every value must be an integer in -128..127")
+    return v.astype(np.int8)
+
+
 def _dt(a):
     if a.dtype == np.float32:
         return N.F32
@@ -141,6 +154,14 @@ def _dt(a):
     if a.dtype == np.float16:   # rows only (FSPANN_F16): refused likewise
         return N.F16
     raise N.FspannArgumentError(f"unsupported dtype {a.dtype}")
+
+
+def _row_dt(a):
+    """_dt for ROWS (store, Setup input, ground-truth pairs): an int8 array is FSPANN_I8 there.  _dt itself, which types queries
+    too, keeps refusing signed bytes."""
+    if a.dtype == np.int8:
+        return N.I8
+    return _dt(a)
 
 
 class FspannContext:
@@ -234,7 +255,7 @@ class FspannContext:
 
     def build_index(self, vectors, order=None, dtype=None):
         """A uint8 array goes to the library as bytes (FSPANN_U8: widened on the device; same tables, a quarter of the traffic),
-        a float16 array as halves (FSPANN_F16: same tables, half the traffic).  dtype=bfloat16 (the package's marker): the rows
+        an int8 array as signed bytes (FSPANN_I8: likewise), a float16 array as halves (FSPANN_F16: same tables, half the traffic).  dtype=bfloat16 (the package's marker): the rows
         go up as bfloat16 bit patterns (FSPANN_BF16; a torch.bfloat16 tensor, uint16 patterns, or floats that already are
         bfloat16 values, as in store_set): same tables, half the traffic.  dtype=float8_e4m3fn likewise (FSPANN_F8E4M3; a
         torch.float8_e4m3fn tensor, uint8 patterns, or floats that already are e4m3 values): same tables, a quarter of the traffic."""
@@ -251,11 +272,11 @@ class FspannContext:
         if dtype is not None:
             raise N.FspannArgumentError("build_index(dtype=): only the bfloat16 and float8_e4m3fn markers are given by name; other rows are typed by their array")
         v = np.ascontiguousarray(vectors)
-        if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
+        if v.dtype not in (np.float32, np.float64, np.uint8, np.int8, np.float16):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
         o = None if order is None else _c(order, np.int32)
-        N.check(self.L.fspann_build_index(self._h, v.shape[0], _p(v), _dt(v), _p(o)))
+        N.check(self.L.fspann_build_index(self._h, v.shape[0], _p(v), _row_dt(v), _p(o)))
 
     def build_begin(self, n_total: int):
         """Incremental Setup: begin(n) -> append(rows of the next handles) ... -> finish(order) (fspann_build_begin / _append / _finish)."""
@@ -273,10 +294,10 @@ class FspannContext:
         if dtype is not None:
             raise N.FspannArgumentError("build_append(dtype=): only the bfloat16 and float8_e4m3fn markers are given by name; other rows are typed by their array")
         v = np.ascontiguousarray(rows)
-        if v.dtype not in (np.float32, np.float64, np.uint8, np.float16):
+        if v.dtype not in (np.float32, np.float64, np.uint8, np.int8, np.float16):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
-        N.check(self.L.fspann_build_append(self._h, v.shape[0], _p(v), _dt(v)))
+        N.check(self.L.fspann_build_append(self._h, v.shape[0], _p(v), _row_dt(v)))
 
     def build_finish(self, order=None):
         o = None if order is None else _c(order, np.int32)
@@ -493,6 +514,9 @@ class FspannContext:
         """dtype=np.uint8 keeps the rows as bytes (FSPANN_U8): only for data whose values are the integers 0..255 (a uint8
         array, or an array holding nothing else), where a byte is exactly what the reference's double[] holds.  Without it a
         uint8 array is widened to float64 like every other non-float array.
+        dtype=np.int8 keeps the rows as signed bytes (FSPANN_I8): an int8 array as it is, any other array only if every value is an
+        integer in -128..127 (no scale, no zero point: the library never quantises for the caller).  Without it an int8 array
+        is widened to float64 as well.
         dtype=np.float16 keeps the rows as halves (FSPANN_F16): a float16 array as it is, any other array only if every value
         already is a half (it survives astype(float16) and back unchanged, NaN counting as NaN) — the library never rounds for
         the caller.  Without it a float16 array is widened to float64 as well.
@@ -520,6 +544,8 @@ class FspannContext:
                 if not exact:
                     raise N.FspannArgumentError("store_set(dtype=uint8): every value must be an integer in 0..255")
                 v = v.astype(np.uint8)
+        elif dtype is not None and np.dtype(dtype) == np.int8:
+            v = _i8_rows(v, "store_set")                                        # (raises before the store is touched)
         elif dtype is not None and np.dtype(dtype) == np.float16:
             if v.dtype != np.float16:
                 with np.errstate(over="ignore", invalid="ignore"):
@@ -537,11 +563,11 @@ class FspannContext:
         elif v.dtype not in (np.float32, np.float64):
             v = v.astype(np.float64)
         v = v.reshape(-1, self.cfg.dim)
-        N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), _dt(v)))
+        N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), _row_dt(v)))
         self.store_dtype = v.dtype
 
     def store_attach_dev(self, n, ptr, dtype):
-        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8, N.F16, N.BF16 or N.F8E4M3."""
+        """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8, N.F16, N.BF16, N.F8E4M3 or N.I8."""
         N.check(self.L.fspann_store_attach_dev(self._h, int(n), ptr, dtype))
 
     def hbm_read_peak(self, nbytes=1 << 32, reps=5) -> float:
@@ -617,24 +643,25 @@ class FspannContext:
                                                recall_ptr, ratio_ptr))
 
     def groundtruth_typed_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, out_ids_ptr, out_d2_ptr=0):
-        """Exact k-NN of device-resident rows: (N.F32, N.F32) as groundtruth_dev, (N.U8, N.U8) over bytes on the int8 matrix
-        cores, ids and squared distances bit-identical to the reference's."""
+        """Exact k-NN of device-resident rows: (N.F32, N.F32) as groundtruth_dev, (N.U8, N.U8) over bytes and (N.I8, N.I8) over signed bytes
+        on the int8 matrix cores, ids and squared distances bit-identical to the reference's."""
         N.check(self.L.fspann_groundtruth_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, out_ids_ptr, out_d2_ptr or None))
 
     def eval_metrics_typed_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride, ann_count_ptr, gt_ptr, gt_stride,
                                recall_ptr, ratio_ptr):
-        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries, or N.F16 / N.BF16 /
-        N.F8E4M3 rows with N.F32 queries (recall and ratio against a resident half, bfloat16 or fp8 store without an fp32 copy)."""
+        """eval_metrics_dev over typed rows: N.F32 rows with N.F32 queries, or N.U8 rows with N.U8 / N.F32 queries, or N.I8 rows with
+        N.I8 / N.F32 queries, or N.F16 / N.BF16 / N.F8E4M3 rows with N.F32 queries (recall and ratio against a resident half, bfloat16 or fp8 store without an fp32 copy)."""
         N.check(self.L.fspann_eval_metrics_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride,
                                                      ann_count_ptr or None, gt_ptr, gt_stride, recall_ptr, ratio_ptr))
 
     def groundtruth(self, base, q, k):
-        """Exact k-NN of host arrays: uint8 arrays stay bytes on the device, anything else goes as fp32 (base and q alike).
+        """Exact k-NN of host arrays: uint8 arrays stay bytes on the device, int8 arrays signed bytes, anything else goes as fp32
+        (base and q alike; bytes with anything but bytes of the same signedness do not match).
         Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n)."""
         base, q = np.asarray(base), np.asarray(q)
-        if (base.dtype == np.uint8) != (q.dtype == np.uint8):
+        if (base.dtype == np.uint8) != (q.dtype == np.uint8) or (base.dtype == np.int8) != (q.dtype == np.int8):
             raise N.FspannArgumentError("Base and query types must match (both fvecs or both bvecs)")
-        dt = np.uint8 if base.dtype == np.uint8 else np.float32
+        dt = base.dtype if base.dtype in (np.uint8, np.int8) else np.float32
         b, qq = _c(base, dt), _c(q, dt)
         if b.ndim != 2 or qq.ndim != 2 or b.shape[1] != qq.shape[1]:
             raise N.FspannArgumentError("base [n][dim] and q [nq][dim] must share dim")
@@ -649,7 +676,7 @@ class FspannContext:
             bd, qd, idd, d2d = ptrs
             N.check(self.L.fspann_h2d(self._h, bd, _p(b), b.nbytes))
             N.check(self.L.fspann_h2d(self._h, qd, _p(qq), qq.nbytes))
-            self.groundtruth_typed_dev(n, bd, _dt(b), nq, qd, _dt(qq), dim, k, idd, d2d)
+            self.groundtruth_typed_dev(n, bd, _row_dt(b), nq, qd, _row_dt(qq), dim, k, idd, d2d)
             N.check(self.L.fspann_d2h(self._h, _p(ids), idd, ids.nbytes))
             N.check(self.L.fspann_d2h(self._h, _p(d2), d2d, d2.nbytes))
         finally:

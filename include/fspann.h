@@ -93,6 +93,18 @@ extern "C" {
  * (QSI.isValid).  A three-role tick over F8E4M3 rows runs the stand-alone kernels in stream order (fspann_last_tick_fused says
  * 0), results identical.                                                                                                    */
 #define FSPANN_F8E4M3 5
+/* Signed bytes, value = the two's-complement integer -128..127 (int8-quantised embeddings as most services and vector databases
+ * hand them out): every value is exactly a half, a float and a double, so distances over signed bytes widened on the fly are
+ * bit-identical to those over the same values held as FSPANN_F32 / FSPANN_F64, at a quarter / an eighth of the bytes.  The
+ * library never shifts, rounds or scales: a quantisation scale or zero point stays with the caller.  A ROW dtype only, with the
+ * standing of FSPANN_U8: accepted by fspann_store_set / _attach_dev (and everything that reads the store), by the cand_dtype of
+ * fspann_refine_dev, the ref_cand_dtype of fspann_tick_dev, the dtype of fspann_build_index / _append, as the base of
+ * fspann_eval_metrics_typed_dev with FSPANN_I8 or FSPANN_F32 queries, and by fspann_groundtruth_typed_dev as the pair
+ * (FSPANN_I8, FSPANN_I8); refused with FSPANN_E_ARG and a message naming FSPANN_I8 wherever a QUERY dtype is given, by
+ * fspann_pointstore_encrypt / _open_batch, by ground truth over any other pair (signed with unsigned included) and by metrics
+ * with any other query type.  A signed byte is always finite.  A three-role tick over I8 rows runs the stand-alone kernels in
+ * stream order (fspann_last_tick_fused says 0), results identical.                                                          */
+#define FSPANN_I8 6
 
 typedef struct fspann_ctx fspann_ctx;
 
@@ -431,10 +443,13 @@ int fspann_eval_metrics_dev(fspann_ctx* ctx, int64_t n, const float* base_dev, i
  * and q [nq][dim] packed bytes in device memory, any alignment, dim in 1..32768; sums of squares of byte differences are
  * integers, exact in fp64 in any order, so they are computed as 32-bit integers on the int8 matrix cores and out_ids / out_d2
  * equal the reference's bit for bit (out_d2: the integers as fp64).  fspann_store_dev_ptr of a U8 store is a valid base_dev.
+ * (FSPANN_I8, FSPANN_I8): the same over signed bytes (values -128..127), on the same matrix cores without the sign flip; a
+ * signed base with unsigned queries, or the reverse, is a pair that does not match.
  * Any other pair, FSPANN_F64, dim > 32768 with bytes, k outside 1..1024: FSPANN_E_ARG ("Base and query types must match
  * (both fvecs or both bvecs)", :226-228).
  * fspann_eval_metrics_typed_dev: FSPANN_F32 rows with FSPANN_F32 queries (= fspann_eval_metrics_dev), or FSPANN_U8 rows
- * with FSPANN_U8 or FSPANN_F32 queries (searches are made with fp32 queries), or FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 rows
+ * with FSPANN_U8 or FSPANN_F32 queries (searches are made with fp32 queries), or FSPANN_I8 rows with FSPANN_I8 or FSPANN_F32
+ * queries, or FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 rows
  * with FSPANN_F32 queries (a resident half, bfloat16 or fp8 store as it is); the same fp64 arithmetic and ordered fold.
  * The [query chunk x n] distance matrix of either ground-truth call (fp64, or uint32 over bytes) lives in library scratch of at
  * most FSPANN_GT_SCRATCH_MB MiB (environment, read at fspann_ctx_create; default 8192); more queries run in chunks.         */

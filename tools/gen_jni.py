@@ -129,6 +129,8 @@ def main():
             '    public static final int BF16 = 4;',
             '    /** Rows only (FSPANN_F8E4M3): OCP fp8 e4m3fn bit patterns (S EEEE MMM, bias 7, no infinity, 0x7F / 0xFF NaN); refused wherever a query dtype is given. */',
             '    public static final int F8E4M3 = 5;',
+            "    /** Rows only (FSPANN_I8): signed bytes, value = the two's-complement integer -128..127; refused wherever a query dtype is given. */",
+            '    public static final int I8 = 6;',
             '    public static final int OK = 0, E_STATE = -1, E_ARG = -2, E_NULL = -3, E_DEVICE = -4, E_NOMEM = -5, E_RANGE = -6;',
             '    /** fspann_tick field order for the long[] passed to tickDev. */',
             '    public static final String[] TICK_FIELDS = {' + ", ".join('"%s"' % f for f in TICK_FIELDS) + '};', '']

@@ -10,7 +10,11 @@ calls, each between two device events on the context's stream (a whole call: nor
 chunk); the readings alternate a / b / c over the rounds.  After the rounds: median and range (min .. max) of every reading's
 timed calls, the outputs of (a) (or (b)) and (c) compared array for array, and the two verdicts — (b) inside the range of (a),
 (c) faster than (a) by more than the width of (a)'s range.  `--readings c --rounds 1 --warm 0 --timed 1` is one (c) call, for
-a kernel trace."""
+a kernel trace.
+The signed leg: reading (d) is this build's typed call over the same scene shifted by -128 and held as SIGNED bytes (FSPANN_I8
+base and queries: the same distances, so its outputs must equal (c)'s array for array), and reading (e) is AB_LIB's typed
+(FSPANN_U8, FSPANN_U8) call, the parent's byte ground truth.  `--readings e,c,d` with AB_LIB set alternates the three; the verdict
+is whether (d)'s median lies inside the range of (e) (without AB_LIB: of (c)) or below it — the signed path does strictly less work."""
 import argparse
 import ctypes as C
 import os
@@ -47,6 +51,7 @@ class OtherLib:
         L.fspann_sync.argtypes, L.fspann_sync.restype = [vp], i
         L.fspann_last_error.restype = C.c_char_p
         L.fspann_groundtruth_dev.argtypes, L.fspann_groundtruth_dev.restype = [vp, i64, vp, i64, vp, i, i, vp, vp], i
+        L.fspann_groundtruth_typed_dev.argtypes, L.fspann_groundtruth_typed_dev.restype = [vp, i64, vp, i, i64, vp, i, i, i, vp, vp], i
         self.h = vp()
         cc = pkg.PaperRuntimeConfig(tables=1, divisions=1, m=4, lambda_=2, dim=D).to_c()
         self.ck(L.fspann_ctx_create(0, C.byref(cc), C.byref(self.h)))
@@ -58,6 +63,9 @@ class OtherLib:
 
     def groundtruth_dev(self, n, b, nq, q, d, k, ids, d2):
         self.ck(self.L.fspann_groundtruth_dev(self.h, n, b, nq, q, d, k, ids, d2))
+
+    def groundtruth_typed_dev(self, n, b, bdt, nq, q, qdt, d, k, ids, d2):
+        self.ck(self.L.fspann_groundtruth_typed_dev(self.h, n, b, bdt, nq, q, qdt, d, k, ids, d2))
 
     def sync(self):
         self.ck(self.L.fspann_sync(self.h))
@@ -91,9 +99,10 @@ def main():
     a = ap.parse_args()
     readings = a.readings.split(",")
     ab = os.environ.get("AB_LIB")
-    if "a" in readings and not ab:
-        print("# AB_LIB is not set: reading (a) is left out", flush=True)
-        readings.remove("a")
+    for r in ("a", "e"):
+        if r in readings and not ab:
+            print(f"# AB_LIB is not set: reading ({r}) is left out", flush=True)
+            readings.remove(r)
     rng = np.random.default_rng(1)
     draw = siftlike(rng, N_BASE, D)
     X8 = draw(N_BASE).astype(np.uint8)
@@ -101,11 +110,13 @@ def main():
     Q8 = draw(max(nqs)).astype(np.uint8)
     x8 = torch.from_numpy(X8).to(DEV)
     q8 = torch.from_numpy(Q8).to(DEV)
+    xs8 = (x8.to(torch.int16) - 128).to(torch.int8) if "d" in readings else None      # the same scene as signed bytes
+    qs8 = (q8.to(torch.int16) - 128).to(torch.int8) if "d" in readings else None
     x32 = x8.to(torch.float32) if ("a" in readings or "b" in readings) else None
     q32 = q8.to(torch.float32) if x32 is not None else None
     torch.cuda.synchronize()
     ctx = pkg.FspannContext(pkg.PaperRuntimeConfig(tables=1, divisions=1, m=4, lambda_=2, dim=D), 0)
-    other = OtherLib(ab) if "a" in readings else None
+    other = OtherLib(ab) if ("a" in readings or "e" in readings) else None
     print(f"# {a.tag}: n {N_BASE} d {D} k {K}  lib {os.path.relpath(N._SO)}  AB_LIB {ab}  {a.rounds} rounds x ({a.warm} warm-up + {a.timed} timed calls)",
           flush=True)
     for nq in nqs:
@@ -115,6 +126,10 @@ def main():
             "b": (ctx, lambda: ctx.groundtruth_dev(N_BASE, x32.data_ptr(), nq, q32.data_ptr(), D, K, out["b"][0].data_ptr(), out["b"][1].data_ptr())),
             "c": (ctx, lambda: ctx.groundtruth_typed_dev(N_BASE, x8.data_ptr(), N.U8, nq, q8.data_ptr(), N.U8, D, K, out["c"][0].data_ptr(),
                                                          out["c"][1].data_ptr())),
+            "d": (ctx, lambda: ctx.groundtruth_typed_dev(N_BASE, xs8.data_ptr(), N.I8, nq, qs8.data_ptr(), N.I8, D, K, out["d"][0].data_ptr(),
+                                                         out["d"][1].data_ptr())),
+            "e": (other, lambda: other.groundtruth_typed_dev(N_BASE, x8.data_ptr(), N.U8, nq, q8.data_ptr(), N.U8, D, K, out["e"][0].data_ptr(),
+                                                             out["e"][1].data_ptr())),
         }
         ts = {r: [] for r in readings}
         for rnd in range(a.rounds):
@@ -137,6 +152,12 @@ def main():
             width = st["a"][2] - st["a"][1]
             print(f"{a.tag} nq={nq}: (c) faster than (a) by {st['a'][0] - st['c'][0]:.3f} ms = {st['a'][0] / st['c'][0]:.2f}x; the range of (a) is "
                   f"{width:.3f} ms wide: {st['a'][0] - st['c'][0] > width}", flush=True)
+        if "d" in readings and ("c" in readings or "e" in readings):
+            u = "e" if "e" in readings else "c"
+            same = bool(torch.equal(out[u][0], out["d"][0]) and torch.equal(out[u][1], out["d"][1]))
+            print(f"{a.tag} nq={nq}: ids and squared distances of ({u}) and (d) equal: {same}", flush=True)
+            print(f"{a.tag} nq={nq}: (d) median {st['d'][0]:.3f} ms against ({u}) {st[u][0]:.3f} ms (range {st[u][1]:.3f} .. {st[u][2]:.3f}): inside the "
+                  f"range or below it: {st['d'][0] <= st[u][2]}", flush=True)
         del out
     ctx.close()
     if other:

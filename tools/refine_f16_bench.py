@@ -3,7 +3,7 @@ FSPANN_F32 rows, and fspann_search_store_dev end to end over an F16 (BF16) and a
 embeddings: BASELINE config #2, config #4's shard, config #3's shard and a RedCaps-like long list (the reference's
 REDCAPS_LAMBDA3 profile: B = 28 000 over 512-dimensional rows).
 
-  python tools/refine_f16_bench.py [--rows f32,f16[,bf16][,f8]] [--parts dense,gather,search] [--shapes ...] [--tag NAME]
+  python tools/refine_f16_bench.py [--rows f32,f16[,bf16][,f8] | f32,u8,i8] [--parts dense,gather,search] [--shapes ...] [--tag NAME]
   AB_LIB=<path to another libfspann_hip.so> ... --rows f32        the same F32 readings with another build (the parent's)
 
 The method of tools/refine_u8_bench.py.  Per reading: device events around every launch on the context's stream, 8 warm-up + 40
@@ -17,7 +17,10 @@ instead, which issues at the same rate = 6; F8E4M3: one v_cvt_pk_f32_fp8 per two
 / 39e12 lane-instructions per second.
 bf16 / f8 rows hold the halves' values rounded once more to bfloat16 / fp8 e4m3fn (torch's rounding, the benchmark's own data:
 timings do not depend on the values, and a standard normal stays far below 448, so no fp8 row turns NaN); without bf16 / f8 in
---rows every reading is taken exactly as before."""
+--rows every reading is taken exactly as before.
+u8 / i8 rows (FSPANN_U8 / FSPANN_I8: a bit-field extract and an integer conversion per row element = 6, like F16) hold
+round(40 x) clipped to -128..127 (u8: + 128); when --rows names either, the end-to-end part builds every index and store, F32
+included, from those quantised values (u8: its own shifted copy, queries shifted too), so that every store routes the same lists."""
 import argparse
 import os
 import sys
@@ -36,9 +39,10 @@ DEV = torch.device("cuda", 0)
 WARM, TIMED = 8, 40
 ROTATE_BYTES = 600 << 20
 HBM, FP64_RATE = 6.3e12, 39e12
-FP64_PER_ELEM = {"f32": 5, "f16": 6, "bf16": 6, "f8": 5.5}
-ES = {"f32": 4, "f16": 2, "bf16": 2, "f8": 1}
-TDT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "f8": torch.float8_e4m3fn}
+FP64_PER_ELEM = {"f32": 5, "f16": 6, "bf16": 6, "f8": 5.5, "u8": 6, "i8": 6}
+ES = {"f32": 4, "f16": 2, "bf16": 2, "f8": 1, "u8": 1, "i8": 1}
+TDT = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16, "f8": torch.float8_e4m3fn, "u8": torch.uint8, "i8": torch.int8}
+BYTE_SCALE = 40.0
 
 SHAPES = {   # name: (nq, B, d, k)
     "config2": (1024, 256, 128, 10),
@@ -55,7 +59,15 @@ PROFILES = {  # for the end-to-end readings: T, D, m, lambda, probes, hard_cap
 
 
 def cdt(rows):
-    return N.F16 if rows == "f16" else N.BF16 if rows == "bf16" else N.F8E4M3 if rows == "f8" else N.F32
+    return N.F16 if rows == "f16" else N.BF16 if rows == "bf16" else N.F8E4M3 if rows == "f8" else N.U8 if rows == "u8" else N.I8 if rows == "i8" else N.F32
+
+
+def as_rows(t, rows):
+    """a device tensor of halves as rows of the given type (byte types: quantised, see the module text)"""
+    if rows in ("u8", "i8"):
+        v = (t.to(torch.float32) * BYTE_SCALE).round().clamp(-128, 127)
+        return (v + 128).to(torch.uint8) if rows == "u8" else v.to(torch.int8)
+    return t.to(TDT[rows])
 
 
 def timed(ctx, launches):
@@ -104,7 +116,7 @@ def bench_dense(tag, rows_list, shapes):
         bufs = {}
         for rows in rows_list:
             nb = max(2, -(-ROTATE_BYTES // (nq * B * d * ES[rows])) + 1)
-            bufs[rows] = [halves((nq, B, d)).to(TDT[rows]) for _ in range(nb)]
+            bufs[rows] = [as_rows(halves((nq, B, d)), rows) for _ in range(nb)]
         torch.cuda.synchronize()
         for rnd in range(2):
             for rows in rows_list:
@@ -122,7 +134,7 @@ def bench_gather(tag, rows_list, shapes):
     for shape in shapes:
         nq, B, d, k = SHAPES[shape]
         base = halves((n, d))
-        stores = {r: base.to(TDT[r]) for r in rows_list}
+        stores = {r: as_rows(base, r) for r in rows_list}
         del base
         ctxs = {}
         for rows in rows_list:
@@ -164,15 +176,24 @@ def bench_search(tag, rows_list, shapes):
         draw = embedlike(rng, d)
         X16 = draw(n).astype(np.float16)           # the one rounding; both stores hold these values
         X = X16.astype(np.float32)
+        bytes_run = any(r in ("u8", "i8") for r in rows_list)
+        if bytes_run:                                # every store holds the quantised values (u8: shifted by 128, queries too)
+            X = np.clip(np.rint(X * np.float32(BYTE_SCALE)), -128, 127).astype(np.float32)
+            X16 = X.astype(np.float16)
         cfg = pkg.PaperRuntimeConfig(tables=pr["T"], divisions=pr["D"], m=pr["m"], lambda_=pr["lam"], dim=d, refinement_limit=B,
                                      max_global_candidates=pr["hard_cap"], probe_override=pr["probes"])
         ctxs = {}
         for rows in rows_list:
             c = pkg.FspannContext(cfg, 0)
-            c.registry_initialize(X[:1000].astype(np.float64))
+            Xr = X + np.float32(128) if rows == "u8" else X
+            c.registry_initialize(Xr[:1000].astype(np.float64))
             c.set_id_meta(n)
-            c.build_index(X)
-            if rows == "f16":
+            c.build_index(Xr)
+            if rows == "u8":
+                c.store_set(Xr.astype(np.uint8), dtype=np.uint8)
+            elif rows == "i8":
+                c.store_set(X.astype(np.int8), dtype=np.int8)
+            elif rows == "f16":
                 c.store_set(X16, dtype=np.float16)
             elif rows == "bf16":
                 c.store_set(torch.from_numpy(X).to(torch.bfloat16), dtype=pkg.bfloat16)
@@ -181,7 +202,8 @@ def bench_search(tag, rows_list, shapes):
             else:
                 c.store_set(X)
             ctxs[rows] = c
-        qs = [torch.from_numpy(draw(nq)).to(DEV) for _ in range(6)]
+        qs = [torch.from_numpy(draw(nq) * np.float32(BYTE_SCALE if bytes_run else 1.0)).to(DEV) for _ in range(6)]
+        qs_u8 = [qq + 128 for qq in qs] if "u8" in rows_list else None
         oi, od, oc, sc = outs(nq, k)
         sel = torch.full((nq, B), -1, dtype=torch.int32, device=DEV)
         selc = torch.zeros(nq, dtype=torch.int32, device=DEV)
@@ -189,7 +211,8 @@ def bench_search(tag, rows_list, shapes):
         for rnd in range(2):
             for rows in rows_list:
                 c = ctxs[rows]
-                launches = [(lambda qq=qs[i % len(qs)], c=c: c.search_store_dev(nq, qq.data_ptr(), N.F32, -1, B, k, oi.data_ptr(), od.data_ptr(), oc.data_ptr(),
+                qr = qs_u8 if rows == "u8" else qs
+                launches = [(lambda qq=qr[i % len(qr)], c=c: c.search_store_dev(nq, qq.data_ptr(), N.F32, -1, B, k, oi.data_ptr(), od.data_ptr(), oc.data_ptr(),
                                                                                 sc.data_ptr(), sel.data_ptr(), selc.data_ptr())) for i in range(WARM + TIMED)]
                 ts = timed(c, launches)
                 scored = float(sc.to(torch.float64).mean().item())

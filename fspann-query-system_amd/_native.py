@@ -1,4 +1,4 @@
-"""ctypes binding of libfspann_hip.so (include/fspann.h).
+"""ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -86,8 +86,8 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = os.path.join(_HERE, "..", "include", "fspann.h")
-    return any(os.path.getmtime(p) > t for p in sources() + [inc])
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h")]
+    return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -202,6 +202,12 @@ _SIGS = {
     "fspann_d2h": (_i, [_vp, _vp, _vp, _sz]),
 }
 
+# include/fspann_groundtruth_rows.h: the companion header's calls (exported_symbols() stays the set of fspann.h)
+_SIGS_ROWS = {
+    "fspann_groundtruth_rows_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _vp, _vp]),
+    "fspann_groundtruth_store_dev": (_i, [_vp, _i64, _vp, _i, _vp, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
@@ -212,7 +218,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -229,3 +235,8 @@ def check(rc: int):
 
 def exported_symbols():
     return sorted(_SIGS)
+
+
+def rows_symbols():
+    """the entry points of include/fspann_groundtruth_rows.h"""
+    return sorted(_SIGS_ROWS)

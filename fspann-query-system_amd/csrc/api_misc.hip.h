@@ -1,6 +1,7 @@
 // api_misc.hip.h — ground truth + metrics, the multi-GPU top-k merge, HBM read-peak probes, device memory helpers
 // Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
+#include "../../include/fspann_groundtruth_rows.h"     // the two ground-truth calls over typed rows (not part of fspann.h's counted set)
 
 extern "C" {
 
@@ -184,6 +185,64 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
                            ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
+}
+
+}  // extern "C"
+namespace {
+// fspann_groundtruth_dev's loop with gt_rows_dist_kernel<TB, .> in the place of gt_dist_kernel (arguments checked by the caller)
+template <typename TB>
+int gt_rows_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const float* q, int dim, int k, int32_t* out_ids, double* out_d2) {
+    // the same [chunk x n] fp64 matrix in the same scratch, and a grid whose y dimension stays within 65535 query tiles
+    int64_t chunk = std::max<int64_t>(kGtQT, std::min<int64_t>(nq, (c->gt_scratch_bytes / (n * 8)) / kGtQT * kGtQT));
+    chunk = std::min<int64_t>(chunk, int64_t(65535) * kGtQT);
+    int rc = ensure(c, c->ws_gt, static_cast<size_t>(chunk) * n * 8);
+    if (rc) return rc;
+    double* dist = static_cast<double*>(c->ws_gt.p);
+    // a lane reads its row 16 bytes at a time when every row starts on a 16-byte boundary and ends on one
+    const bool vec = (static_cast<int64_t>(dim) * static_cast<int64_t>(sizeof(TB))) % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
+    for (int64_t s = 0; s < nq; s += chunk) {
+        const int64_t cq = std::min(chunk, nq - s);
+        dim3 grid(static_cast<unsigned>((n + kGtRows - 1) / kGtRows), static_cast<unsigned>((cq + kGtQT - 1) / kGtQT));
+        if (vec) hipLaunchKernelGGL((gt_rows_dist_kernel<TB, true>), grid, dim3(kGtRows), 0, c->stream, base, n, q + s * dim, cq, dim, dist);
+        else hipLaunchKernelGGL((gt_rows_dist_kernel<TB, false>), grid, dim3(kGtRows), 0, c->stream, base, n, q + s * dim, cq, dim, dist);
+        FSP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(gt_select_kernel, dim3(static_cast<unsigned>(cq)), dim3(kGtSelThreads), 0, c->stream, dist, n, k, out_ids + s * k,
+                           out_d2 ? out_d2 + s * k : nullptr);
+        FSP_HIP(hipGetLastError());
+    }
+    return FSPANN_OK;
+}
+}  // namespace
+extern "C" {
+
+// Ground truth of fp32 queries over typed rows: the element widened exactly, then fspann_groundtruth_dev's arithmetic and select.
+int fspann_groundtruth_rows_dev(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const float* q_dev, int dim, int k,
+                                int32_t* out_ids_dev, double* out_d2_dev) {
+    CHECK_CTX(c);
+    if (!base_dev || !q_dev || !out_ids_dev) return fail(FSPANN_E_NULL, "ground truth buffer is null");
+    if (base_dtype == FSPANN_F32) return fspann_groundtruth_dev(c, n, static_cast<const float*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
+    if (base_dtype != FSPANN_U8 && base_dtype != FSPANN_I8 && base_dtype != FSPANN_F16 && base_dtype != FSPANN_BF16 && base_dtype != FSPANN_F8E4M3)
+        return fail(FSPANN_E_ARG, "ground truth rows are FSPANN_F32, FSPANN_U8, FSPANN_I8, FSPANN_F16, FSPANN_BF16 or FSPANN_F8E4M3 (the reference's ground truth reads floats): base %s (%d)",
+                    gt_dtype_name(base_dtype), base_dtype);
+    if (n <= 0 || n >= (1LL << 31) || nq < 0 || dim <= 0) return fail(FSPANN_E_ARG, "Empty or malformed vector files (zero records).");
+    if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
+    if (nq == 0) return FSPANN_OK;
+    switch (base_dtype) {
+    case FSPANN_U8: return gt_rows_run(c, n, static_cast<const uint8_t*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
+    case FSPANN_I8: return gt_rows_run(c, n, static_cast<const int8_t*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
+    case FSPANN_F16: return gt_rows_run(c, n, static_cast<const _Float16*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
+    case FSPANN_BF16: return gt_rows_run(c, n, static_cast<const fsp_bf16*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
+    default: return gt_rows_run(c, n, static_cast<const fsp_f8e4m3*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
+    }
+}
+
+// The same with the context's resident store as the base (fspann_store_set or fspann_store_attach_dev; its n, dtype and cfg.dim).
+int fspann_groundtruth_store_dev(fspann_ctx* c, int64_t nq, const float* q_dev, int k, int32_t* out_ids_dev, double* out_d2_dev) {
+    CHECK_CTX(c);
+    if (!q_dev || !out_ids_dev) return fail(FSPANN_E_NULL, "ground truth buffer is null");
+    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (c->store_dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no ground truth over an FSPANN_F64 store: the reference's ground truth reads floats");
+    return fspann_groundtruth_rows_dev(c, c->store_n, c->d_store, c->store_dtype, nq, q_dev, c->cfg.dim, k, out_ids_dev, out_d2_dev);
 }
 
 // ---- multi-GPU merge: one RCCL all-gather of the packed per-rank top-k -------------------------------

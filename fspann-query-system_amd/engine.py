@@ -164,6 +164,42 @@ def _row_dt(a):
     return _dt(a)
 
 
+def _typed_rows(vectors, dtype, what):
+    """Rows as store_set takes them (its docstring says what each dtype= accepts; `what` names the caller in the messages): the
+    contiguous array to hand over, its FSPANN_* code, and what store_dtype reports for it."""
+    if dtype is float8_e4m3fn:
+        return _f8_bits(vectors, what), N.F8E4M3, float8_e4m3fn
+    if dtype is bfloat16:
+        return _bf16_bits(vectors, what), N.BF16, bfloat16
+    v = np.ascontiguousarray(vectors)
+    if dtype is not None and np.dtype(dtype) == np.uint8:
+        if v.dtype != np.uint8:
+            with np.errstate(invalid="ignore"):
+                exact = bool(np.all((v >= 0) & (v <= 255) & (v == np.floor(v))))
+            if not exact:
+                raise N.FspannArgumentError(f"{what}(dtype=uint8): every value must be an integer in 0..255")
+            v = v.astype(np.uint8)
+    elif dtype is not None and np.dtype(dtype) == np.int8:
+        v = _i8_rows(v, what)
+    elif dtype is not None and np.dtype(dtype) == np.float16:
+        if v.dtype != np.float16:
+            with np.errstate(over="ignore", invalid="ignore"):
+                h = v.astype(np.float16)
+                back = h.astype(v.dtype)
+                exact = bool(np.all((back == v) | ((back != back) & (v != v))))
+            if not exact:
+                raise N.FspannArgumentError(f"{what}(dtype=float16): every value must be exactly representable as an IEEE half "
+                                            "(round the data yourself: the library never does)")
+            v = h
+    elif dtype is not None:
+        v = v.astype(np.dtype(dtype))
+        if v.dtype not in (np.float32, np.float64):
+            raise N.FspannArgumentError(f"unsupported dtype {v.dtype}")
+    elif v.dtype not in (np.float32, np.float64):
+        v = v.astype(np.float64)
+    return v, _row_dt(v), v.dtype
+
+
 class FspannContext:
     def __init__(self, cfg: PaperRuntimeConfig, device: int = 0):
         self.cfg = cfg
@@ -526,45 +562,10 @@ class FspannContext:
         dtype=float8_e4m3fn (the package's marker) keeps the rows as OCP fp8 e4m3fn (FSPANN_F8E4M3): a CPU torch.float8_e4m3fn
         tensor as it is, a uint8 array as bit patterns, a float array only if every value already is an e4m3 value (NaN becomes
         0x7F; +-inf is refused, the format has none).  store_dtype then reports the marker."""
-        if dtype is float8_e4m3fn:
-            v = _f8_bits(vectors, "store_set").reshape(-1, self.cfg.dim)        # (raises before the store is touched)
-            N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), N.F8E4M3))
-            self.store_dtype = float8_e4m3fn
-            return
-        if dtype is bfloat16:
-            v = _bf16_bits(vectors, "store_set").reshape(-1, self.cfg.dim)      # (raises before the store is touched)
-            N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), N.BF16))
-            self.store_dtype = bfloat16
-            return
-        v = np.ascontiguousarray(vectors)
-        if dtype is not None and np.dtype(dtype) == np.uint8:
-            if v.dtype != np.uint8:
-                with np.errstate(invalid="ignore"):
-                    exact = bool(np.all((v >= 0) & (v <= 255) & (v == np.floor(v))))
-                if not exact:
-                    raise N.FspannArgumentError("store_set(dtype=uint8): every value must be an integer in 0..255")
-                v = v.astype(np.uint8)
-        elif dtype is not None and np.dtype(dtype) == np.int8:
-            v = _i8_rows(v, "store_set")                                        # (raises before the store is touched)
-        elif dtype is not None and np.dtype(dtype) == np.float16:
-            if v.dtype != np.float16:
-                with np.errstate(over="ignore", invalid="ignore"):
-                    h = v.astype(np.float16)
-                    back = h.astype(v.dtype)
-                    exact = bool(np.all((back == v) | ((back != back) & (v != v))))
-                if not exact:
-                    raise N.FspannArgumentError("store_set(dtype=float16): every value must be exactly representable as an IEEE half "
-                                                "(round the data yourself: the library never does)")
-                v = h
-        elif dtype is not None:
-            v = v.astype(np.dtype(dtype))
-            if v.dtype not in (np.float32, np.float64):
-                raise N.FspannArgumentError(f"unsupported dtype {v.dtype}")
-        elif v.dtype not in (np.float32, np.float64):
-            v = v.astype(np.float64)
+        v, code, kept = _typed_rows(vectors, dtype, "store_set")                # (raises before the store is touched)
         v = v.reshape(-1, self.cfg.dim)
-        N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), _row_dt(v)))
-        self.store_dtype = v.dtype
+        N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), code))
+        self.store_dtype = kept
 
     def store_attach_dev(self, n, ptr, dtype):
         """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8, N.F16, N.BF16, N.F8E4M3 or N.I8."""
@@ -654,15 +655,32 @@ class FspannContext:
         N.check(self.L.fspann_eval_metrics_typed_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, k, ann_ptr, ann_stride,
                                                      ann_count_ptr or None, gt_ptr, gt_stride, recall_ptr, ratio_ptr))
 
-    def groundtruth(self, base, q, k):
-        """Exact k-NN of host arrays: uint8 arrays stay bytes on the device, int8 arrays signed bytes, anything else goes as fp32
-        (base and q alike; bytes with anything but bytes of the same signedness do not match).
-        Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n)."""
-        base, q = np.asarray(base), np.asarray(q)
-        if (base.dtype == np.uint8) != (q.dtype == np.uint8) or (base.dtype == np.int8) != (q.dtype == np.int8):
-            raise N.FspannArgumentError("Base and query types must match (both fvecs or both bvecs)")
-        dt = base.dtype if base.dtype in (np.uint8, np.int8) else np.float32
-        b, qq = _c(base, dt), _c(q, dt)
+    def groundtruth_rows_dev(self, n, base_ptr, base_dtype, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr=0):
+        """Exact k-NN of device-resident fp32 queries over typed rows as they are (N.U8, N.I8, N.F16, N.BF16, N.F8E4M3; N.F32 is
+        groundtruth_dev): every element widened exactly, ids and squared distances bit-identical to groundtruth_dev over the same
+        values held as fp32."""
+        N.check(self.L.fspann_groundtruth_rows_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr or None))
+
+    def groundtruth_store_dev(self, nq, q_ptr, k, out_ids_ptr, out_d2_ptr=0):
+        """groundtruth_rows_dev with the resident store (store_set or store_attach_dev) as the base: the ids eval_metrics_typed_dev
+        needs for recall against that store, with no fp32 copy of it."""
+        N.check(self.L.fspann_groundtruth_store_dev(self._h, nq, q_ptr, k, out_ids_ptr, out_d2_ptr or None))
+
+    def groundtruth_rows(self, base, q, k, dtype=None):
+        """Exact k-NN of fp32 queries over host rows kept in their type on the device.  base [n][dim] and dtype= are what store_set
+        takes (np.uint8 / np.int8 / np.float16 arrays or values, the bfloat16 / float8_e4m3fn markers with tensors, bit patterns or
+        exact floats); without dtype= a uint8, int8 or float16 array keeps its own type (nothing here widens rows).  q [nq][dim] goes
+        as fp32.  float64 rows are refused (the reference's ground truth reads floats: pass dtype=np.float32 to have them cast).
+        Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n), what groundtruth() returns
+        for the same values held as float32."""
+        if dtype is None and getattr(base, "dtype", None) in (np.uint8, np.int8, np.float16):
+            dtype = base.dtype
+        b, code, _ = _typed_rows(base, dtype, "groundtruth_rows")
+        return self._groundtruth_host(b, _c(q, np.float32), k,
+                                      lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_rows_dev(n, bd, code, nq, qd, dim, k, idd, d2d))
+
+    def _groundtruth_host(self, b, qq, k, run):
+        """base b and queries qq (host arrays as they go to the device) -> ids, d2 of the device call `run`"""
         if b.ndim != 2 or qq.ndim != 2 or b.shape[1] != qq.shape[1]:
             raise N.FspannArgumentError("base [n][dim] and q [nq][dim] must share dim")
         (n, dim), nq = b.shape, qq.shape[0]
@@ -676,13 +694,25 @@ class FspannContext:
             bd, qd, idd, d2d = ptrs
             N.check(self.L.fspann_h2d(self._h, bd, _p(b), b.nbytes))
             N.check(self.L.fspann_h2d(self._h, qd, _p(qq), qq.nbytes))
-            self.groundtruth_typed_dev(n, bd, _row_dt(b), nq, qd, _row_dt(qq), dim, k, idd, d2d)
+            run(n, bd, nq, qd, dim, idd, d2d)
             N.check(self.L.fspann_d2h(self._h, _p(ids), idd, ids.nbytes))
             N.check(self.L.fspann_d2h(self._h, _p(d2), d2d, d2.nbytes))
         finally:
             for p in ptrs:
                 self.L.fspann_dev_free(self._h, p)
         return ids, d2
+
+    def groundtruth(self, base, q, k):
+        """Exact k-NN of host arrays: uint8 arrays stay bytes on the device, int8 arrays signed bytes, anything else goes as fp32
+        (base and q alike; bytes with anything but bytes of the same signedness do not match).
+        Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n)."""
+        base, q = np.asarray(base), np.asarray(q)
+        if (base.dtype == np.uint8) != (q.dtype == np.uint8) or (base.dtype == np.int8) != (q.dtype == np.int8):
+            raise N.FspannArgumentError("Base and query types must match (both fvecs or both bvecs)")
+        dt = base.dtype if base.dtype in (np.uint8, np.int8) else np.float32
+        b, qq = _c(base, dt), _c(q, dt)
+        return self._groundtruth_host(b, qq, k, lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_typed_dev(n, bd, _row_dt(b), nq, qd, _row_dt(qq), dim, k,
+                                                                                                        idd, d2d))
 
     def route_handover_bytes(self, nq, probe_override=-1) -> int:
         return int(self.L.fspann_route_handover_bytes(self._h, nq, probe_override))

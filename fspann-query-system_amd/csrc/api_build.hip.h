@@ -24,9 +24,8 @@ int build_begin_impl(fspann_ctx* c, int64_t n) {
 int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype) {
     const int d = c->cfg.dim, TD = c->TD, W = c->W;
     const size_t esz = dtype_size(dtype);
-    // byte rows (unsigned and signed), half rows, bfloat16 rows and fp8 rows go up as they are and are widened to fp32 on the device, exactly: the codes are those of the F32 build
-    const bool bytes_in = dtype == FSPANN_U8, halves_in = dtype == FSPANN_F16, bf16_in = dtype == FSPANN_BF16, f8_in = dtype == FSPANN_F8E4M3;
-    const bool i8_in = dtype == FSPANN_I8, widen = bytes_in || halves_in || bf16_in || f8_in || i8_in;
+    // every row type that is no query type (bytes unsigned and signed, halves, bfloat16, fp8) goes up as it is and is widened to fp32 on the device, exactly: the codes are those of the F32 build
+    const bool widen = !is_query_dtype(dtype);
     const int64_t chunk = 1 << 18;
     int rc;
     if (c->bld_done + nrows > c->bld_n) {       // more rows than the hint: grow the code buffer, keep what is coded
@@ -51,32 +50,15 @@ int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype)
         FSP_HIP(hipMemcpyAsync(c->ws_io[0].p, static_cast<const char*>(rows) + static_cast<size_t>(s) * d * esz,
                                static_cast<size_t>(cn) * d * esz, hipMemcpyHostToDevice, c->stream));
         uint64_t* cdst = codes_all + static_cast<size_t>(c->bld_done + s) * TD * W;
-        if (bytes_in) {
-            const int64_t ne = cn * d;
-            hipLaunchKernelGGL(build_widen_u8_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
-                               static_cast<const uint8_t*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
-            FSP_HIP(hipGetLastError());
-        } else if (halves_in) {
-            const int64_t ne = cn * d;
-            hipLaunchKernelGGL(build_widen_f16_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
-                               static_cast<const _Float16*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
-            FSP_HIP(hipGetLastError());
-        } else if (bf16_in) {
-            const int64_t ne = cn * d;
-            hipLaunchKernelGGL(build_widen_bf16_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
-                               static_cast<const fsp_bf16*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
-            FSP_HIP(hipGetLastError());
-        } else if (f8_in) {
-            const int64_t ne = cn * d;
-            hipLaunchKernelGGL(build_widen_f8_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
-                               static_cast<const fsp_f8e4m3*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
-            FSP_HIP(hipGetLastError());
-        } else if (i8_in) {
-            const int64_t ne = cn * d;
-            hipLaunchKernelGGL(build_widen_i8_kernel, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
-                               static_cast<const int8_t*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
-            FSP_HIP(hipGetLastError());
-        }
+        with_row_type(dtype, [&](auto tr) {
+            using T = typename decltype(tr)::type;
+            if constexpr (!DtypeOf<T>::query) {
+                const int64_t ne = cn * d;
+                hipLaunchKernelGGL(build_widen_kernel(static_cast<const T*>(nullptr)), dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
+                                   static_cast<const T*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
+            }
+        });
+        if (widen) FSP_HIP(hipGetLastError());
         rc = fspann_encode_dev(c, cn, widen ? c->ws_io[1].p : c->ws_io[0].p, widen ? FSPANN_F32 : dtype, cdst, nullptr, static_cast<int32_t*>(c->ws_io[2].p));
         if (rc) return rc;
         FSP_HIP(hipMemcpyAsync(bad.data(), c->ws_io[2].p, static_cast<size_t>(cn) * 4, hipMemcpyDeviceToHost, c->stream));

@@ -111,10 +111,7 @@ int fspann_encode_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int dtype, u
     if (!q_dev || !codes_dev) return fail(FSPANN_E_NULL, "query vector is null");
     if (dtype == FSPANN_F64) return launch_encode<double>(c, nq, static_cast<const double*>(q_dev), codes_dev, hashes_dev, bad_dev);
     if (dtype == FSPANN_F32) return launch_encode<float>(c, nq, static_cast<const float*>(q_dev), codes_dev, hashes_dev, bad_dev);
-    if (dtype == FSPANN_F16) return refuse_f16("dtype");
-    if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
-    if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
-    if (dtype == FSPANN_I8) return refuse_i8("dtype");
+    if (int rc = refuse_row_only(dtype, "dtype")) return rc;
     return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
 }
 
@@ -124,10 +121,7 @@ int fspann_encode(fspann_ctx* c, int64_t nq, const void* q, int dtype, uint64_t*
     if (nq < 0) return fail(FSPANN_E_ARG, "nq < 0");
     if (nq == 0) return FSPANN_OK;
     if (!q || !codes) return fail(FSPANN_E_NULL, "query vector is null");
-    if (dtype == FSPANN_F16) return refuse_f16("dtype");
-    if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
-    if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
-    if (dtype == FSPANN_I8) return refuse_i8("dtype");
+    if (int rc = refuse_row_only(dtype, "dtype")) return rc;
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     const size_t esz = dtype == FSPANN_F64 ? 8 : 4;
     const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * esz;

@@ -122,10 +122,7 @@ int fspann_search_store_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev,
                                    int32_t* sel_ids_dev, int32_t* sel_count_dev, int64_t* resolved) {
     CHECK_CTX(c);
     if (resolved) *resolved = 0;
-    if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");     // (whether or not a query is left to finish)
-    if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");     // (whether or not a query is left to finish)
-    if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");     // (whether or not a query is left to finish)
-    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");        // (whether or not a query is left to finish)
+    if (int rc = refuse_row_only(q_dtype, "q_dtype")) return rc;     // (whether or not a query is left to finish)
     if (!c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
     if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
     if (nq < 0 || B <= 0 || B > INT32_MAX) return fail(FSPANN_E_ARG, "nq < 0 or B out of range");

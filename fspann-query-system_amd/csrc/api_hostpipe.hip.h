@@ -57,10 +57,7 @@ int fspann_pointstore_retire(fspann_pointstore* ps, int version) {
 int fspann_pointstore_encrypt(fspann_pointstore* ps, int64_t h0, int64_t cnt, const void* vectors, int dtype, int threads) {
     if (!ps || !vectors) return fail(FSPANN_E_NULL, "point store / vectors is null");
     if (h0 < 0 || cnt < 0 || h0 + cnt > ps->n) return fail(FSPANN_E_ARG, "handles [%lld, %lld) outside the store", (long long)h0, (long long)(h0 + cnt));
-    if (dtype == FSPANN_F16) return refuse_f16("dtype");
-    if (dtype == FSPANN_BF16) return refuse_bf16("dtype");
-    if (dtype == FSPANN_F8E4M3) return refuse_f8("dtype");
-    if (dtype == FSPANN_I8) return refuse_i8("dtype");
+    if (int rc = refuse_row_only(dtype, "dtype")) return rc;
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     if (!ps->have_master) return fail(FSPANN_E_STATE, "Master key is not initialized");
     return guarded([&]() -> int {
@@ -98,10 +95,7 @@ int fspann_pointstore_open_batch(fspann_pointstore* ps, int64_t nq, int64_t B, c
                                  int32_t* out_ids, int32_t* out_count, int threads) {
     if (!ps || !ids || !count || !dst || !out_ids || !out_count) return fail(FSPANN_E_NULL, "point store / buffer is null");
     if (nq < 0 || B <= 0) return fail(FSPANN_E_ARG, "nq < 0 or B <= 0");
-    if (dst_dtype == FSPANN_F16) return refuse_f16("dst_dtype");
-    if (dst_dtype == FSPANN_BF16) return refuse_bf16("dst_dtype");
-    if (dst_dtype == FSPANN_F8E4M3) return refuse_f8("dst_dtype");
-    if (dst_dtype == FSPANN_I8) return refuse_i8("dst_dtype");
+    if (int rc = refuse_row_only(dst_dtype, "dst_dtype")) return rc;
     if (dst_dtype != FSPANN_F32 && dst_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dst_dtype);
     return guarded([&]() -> int {
         if (dst_dtype == FSPANN_F32) pointstore_open_batch<float>(ps, nq, B, ids, count, static_cast<float*>(dst), out_ids, out_count, threads);

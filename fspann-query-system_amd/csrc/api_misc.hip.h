@@ -45,7 +45,6 @@ int fspann_eval_metrics_dev(fspann_ctx* c, int64_t n, const float* base_dev, int
 
 }  // extern "C"
 namespace {
-const char* gt_dtype_name(int dt) { return dt == FSPANN_F32 ? "FSPANN_F32" : dt == FSPANN_F64 ? "FSPANN_F64" : dt == FSPANN_U8 ? "FSPANN_U8" : dt == FSPANN_F16 ? "FSPANN_F16" : dt == FSPANN_BF16 ? "FSPANN_BF16" : dt == FSPANN_F8E4M3 ? "FSPANN_F8E4M3" : dt == FSPANN_I8 ? "FSPANN_I8" : "unknown dtype"; }
 int gt8_digits(uint64_t v) {      // 8-bit digits that hold v
     int nd = 1;
     while (nd < 4 && (v >> (8 * nd)) != 0) nd++;
@@ -59,22 +58,17 @@ int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev,
                                  int32_t* out_ids_dev, double* out_d2_dev) {
     CHECK_CTX(c);
     if (!base_dev || !q_dev || !out_ids_dev) return fail(FSPANN_E_NULL, "ground truth buffer is null");
-    if (base_dtype == FSPANN_F16 || q_dtype == FSPANN_F16)   // the reference reads base and query from files of one type, and a query is never a half
-        return fail(FSPANN_E_ARG, "no ground truth over FSPANN_F16 (base and query are both FSPANN_F32 or both FSPANN_U8): base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    if (base_dtype == FSPANN_BF16 || q_dtype == FSPANN_BF16)   // likewise: and a query is never a bfloat16
-        return fail(FSPANN_E_ARG, "no ground truth over FSPANN_BF16 (base and query are both FSPANN_F32 or both FSPANN_U8): base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    if (base_dtype == FSPANN_F8E4M3 || q_dtype == FSPANN_F8E4M3)   // likewise: and a query is never an fp8
-        return fail(FSPANN_E_ARG, "no ground truth over FSPANN_F8E4M3 (base and query are both FSPANN_F32 or both FSPANN_U8): base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
+    for (const DtypeInfo& r : kDtypes)     // the reference reads base and query from files of one type, floats or bytes: and a query is never a half, a bfloat16 or an fp8
+        if (!r.query && !r.finite && (base_dtype == r.id || q_dtype == r.id))
+            return fail(FSPANN_E_ARG, "no ground truth over %s (base and query are both FSPANN_F32 or both FSPANN_U8): base %s, query %s", r.name, dtype_name(base_dtype),
+                        dtype_name(q_dtype));
     // (FSPANN_I8 pairs with FSPANN_I8 only: signed with unsigned bytes, or with floats, is a pair that does not match)
     if (base_dtype != q_dtype || (base_dtype != FSPANN_F32 && base_dtype != FSPANN_U8 && base_dtype != FSPANN_I8))
-        return fail(FSPANN_E_ARG, "Base and query types must match (both fvecs or both bvecs): base %s, query %s", gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
+        return fail(FSPANN_E_ARG, "Base and query types must match (both fvecs or both bvecs): base %s, query %s", dtype_name(base_dtype), dtype_name(q_dtype));
     if (base_dtype == FSPANN_F32)
         return fspann_groundtruth_dev(c, n, static_cast<const float*>(base_dev), nq, static_cast<const float*>(q_dev), dim, k, out_ids_dev, out_d2_dev);
     if (n <= 0 || n >= (1LL << 31) || nq < 0 || dim <= 0) return fail(FSPANN_E_ARG, "Empty or malformed vector files (zero records).");
-    if (dim > kGt8MaxDim) return fail(FSPANN_E_ARG, "dim %d > %d: %s distances would not fit 32 bits", dim, kGt8MaxDim, gt_dtype_name(base_dtype));
+    if (dim > kGt8MaxDim) return fail(FSPANN_E_ARG, "dim %d > %d: %s distances would not fit 32 bits", dim, kGt8MaxDim, dtype_name(base_dtype));
     if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
     const bool sgn = base_dtype == FSPANN_I8;     // signed bytes: the gt8s_* kernels (no flip); everything else is shared
@@ -135,54 +129,37 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
                                   int64_t gt_stride, double* recall_dev, double* ratio_dev) {
     CHECK_CTX(c);
     if (!base_dev || !q_dev || !ann_ids_dev || !gt_ids_dev || !recall_dev || !ratio_dev) return fail(FSPANN_E_NULL, "metrics buffer is null");
-    const bool f32 = base_dtype == FSPANN_F32 && q_dtype == FSPANN_F32;
-    const bool u8 = base_dtype == FSPANN_U8 && (q_dtype == FSPANN_U8 || q_dtype == FSPANN_F32);
-    const bool f16 = base_dtype == FSPANN_F16 && q_dtype == FSPANN_F32;
-    if (!f16 && (base_dtype == FSPANN_F16 || q_dtype == FSPANN_F16))
-        return fail(FSPANN_E_ARG, "metrics take FSPANN_F16 rows with FSPANN_F32 queries only (a query is never FSPANN_F16): base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    const bool bf16 = base_dtype == FSPANN_BF16 && q_dtype == FSPANN_F32;
-    if (!bf16 && (base_dtype == FSPANN_BF16 || q_dtype == FSPANN_BF16))
-        return fail(FSPANN_E_ARG, "metrics take FSPANN_BF16 rows with FSPANN_F32 queries only (a query is never FSPANN_BF16): base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    const bool f8 = base_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32;
-    if (!f8 && (base_dtype == FSPANN_F8E4M3 || q_dtype == FSPANN_F8E4M3))
-        return fail(FSPANN_E_ARG, "metrics take FSPANN_F8E4M3 rows with FSPANN_F32 queries only (a query is never FSPANN_F8E4M3): base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    const bool i8 = base_dtype == FSPANN_I8 && (q_dtype == FSPANN_I8 || q_dtype == FSPANN_F32);
-    if (!i8 && (base_dtype == FSPANN_I8 || q_dtype == FSPANN_I8))
-        return fail(FSPANN_E_ARG, "metrics take FSPANN_I8 rows with FSPANN_I8 / FSPANN_F32 queries only (a signed byte pairs with nothing else): base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    if (!f32 && !u8 && !f16 && !bf16 && !f8 && !i8)
+    // The pairs: fp32 queries (what searches are made with) over every row type but FSPANN_F64, and a byte type over itself.
+    const DtypeInfo* bi = dtype_info(base_dtype);
+    const bool same_bytes = bi && bi->finite && q_dtype == base_dtype;
+    if (!(same_bytes || (bi && q_dtype == FSPANN_F32 && base_dtype != FSPANN_F64))) {
+        for (const DtypeInfo& r : kDtypes) {       // the row-only types that are refused by name, in the table's order
+            if (!r.words || (base_dtype != r.id && q_dtype != r.id)) continue;
+            if (r.finite)
+                return fail(FSPANN_E_ARG, "metrics take %s rows with %s / FSPANN_F32 queries only (a signed byte pairs with nothing else): base %s, query %s", r.name, r.name,
+                            dtype_name(base_dtype), dtype_name(q_dtype));
+            return fail(FSPANN_E_ARG, "metrics take %s rows with FSPANN_F32 queries only (a query is never %s): base %s, query %s", r.name, r.name, dtype_name(base_dtype),
+                        dtype_name(q_dtype));
+        }
         return fail(FSPANN_E_ARG, "metrics take FSPANN_F32 rows with FSPANN_F32 queries, or FSPANN_U8 rows with FSPANN_U8 / FSPANN_F32 queries: base %s, query %s",
-                    gt_dtype_name(base_dtype), gt_dtype_name(q_dtype));
-    if (f32)
+                    dtype_name(base_dtype), dtype_name(q_dtype));
+    }
+    if (base_dtype == FSPANN_F32)
         return fspann_eval_metrics_dev(c, n, static_cast<const float*>(base_dev), nq, static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride,
                                        ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     if (n <= 0 || nq < 0 || dim <= 0 || k <= 0 || k > kGtMaxK || gt_stride < k || ann_stride <= 0) return fail(FSPANN_E_ARG, "k must be in [1, %d] and gt must hold >= k ids per query", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
-    const uint8_t* base = static_cast<const uint8_t*>(base_dev);
-    if (f16)      // a resident half store: recall and ratio without an fp32 copy (every half is exact in fp64)
-        hipLaunchKernelGGL((gt_metrics_typed_kernel<_Float16, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const _Float16*>(base_dev), n,
-                           static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
-    else if (bf16)    // a resident bfloat16 store, likewise
-        hipLaunchKernelGGL((gt_metrics_typed_kernel<fsp_bf16, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const fsp_bf16*>(base_dev), n,
-                           static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
-    else if (f8)      // a resident fp8 store, likewise
-        hipLaunchKernelGGL((gt_metrics_typed_kernel<fsp_f8e4m3, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const fsp_f8e4m3*>(base_dev), n,
-                           static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
-    else if (i8 && q_dtype == FSPANN_I8)    // signed bytes, against signed byte queries or the fp32 queries searches are made with
-        hipLaunchKernelGGL((gt_metrics_typed_kernel<int8_t, int8_t>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const int8_t*>(base_dev), n,
-                           static_cast<const int8_t*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
-    else if (i8)
-        hipLaunchKernelGGL((gt_metrics_typed_kernel<int8_t, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const int8_t*>(base_dev), n,
-                           static_cast<const float*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
-    else if (q_dtype == FSPANN_U8)
-        hipLaunchKernelGGL((gt_metrics_typed_kernel<uint8_t, uint8_t>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base, n, static_cast<const uint8_t*>(q_dev), dim, k,
-                           ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
-    else
-        hipLaunchKernelGGL((gt_metrics_typed_kernel<uint8_t, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base, n, static_cast<const float*>(q_dev), dim, k,
-                           ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+    // a resident typed store: recall and ratio without an fp32 copy (every element is exact in fp64)
+    with_row_type(base_dtype, [&](auto tb) {
+        using TB = typename decltype(tb)::type;
+        auto go = [&](auto tq) {
+            using TQ = typename decltype(tq)::type;
+            hipLaunchKernelGGL((gt_metrics_typed_kernel<TB, TQ>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const TB*>(base_dev), n,
+                               static_cast<const TQ*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
+        };
+        if constexpr (DtypeOf<TB>::finite) { if (same_bytes) go(tb); else go(DtypeTag<float>{}); }
+        else if constexpr (!DtypeOf<TB>::query) go(DtypeTag<float>{});
+    });
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
 }
@@ -221,19 +198,18 @@ int fspann_groundtruth_rows_dev(fspann_ctx* c, int64_t n, const void* base_dev, 
     CHECK_CTX(c);
     if (!base_dev || !q_dev || !out_ids_dev) return fail(FSPANN_E_NULL, "ground truth buffer is null");
     if (base_dtype == FSPANN_F32) return fspann_groundtruth_dev(c, n, static_cast<const float*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
-    if (base_dtype != FSPANN_U8 && base_dtype != FSPANN_I8 && base_dtype != FSPANN_F16 && base_dtype != FSPANN_BF16 && base_dtype != FSPANN_F8E4M3)
+    if (!is_row_dtype(base_dtype) || is_query_dtype(base_dtype))      // (FSPANN_F64, or no dtype at all)
         return fail(FSPANN_E_ARG, "ground truth rows are FSPANN_F32, FSPANN_U8, FSPANN_I8, FSPANN_F16, FSPANN_BF16 or FSPANN_F8E4M3 (the reference's ground truth reads floats): base %s (%d)",
-                    gt_dtype_name(base_dtype), base_dtype);
+                    dtype_name(base_dtype), base_dtype);
     if (n <= 0 || n >= (1LL << 31) || nq < 0 || dim <= 0) return fail(FSPANN_E_ARG, "Empty or malformed vector files (zero records).");
     if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
-    switch (base_dtype) {
-    case FSPANN_U8: return gt_rows_run(c, n, static_cast<const uint8_t*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
-    case FSPANN_I8: return gt_rows_run(c, n, static_cast<const int8_t*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
-    case FSPANN_F16: return gt_rows_run(c, n, static_cast<const _Float16*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
-    case FSPANN_BF16: return gt_rows_run(c, n, static_cast<const fsp_bf16*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
-    default: return gt_rows_run(c, n, static_cast<const fsp_f8e4m3*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
-    }
+    int rc = FSPANN_OK;
+    with_row_type(base_dtype, [&](auto tb) {
+        using TB = typename decltype(tb)::type;
+        if constexpr (!DtypeOf<TB>::query) rc = gt_rows_run(c, n, static_cast<const TB*>(base_dev), nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
+    });
+    return rc;
 }
 
 // The same with the context's resident store as the base (fspann_store_set or fspann_store_attach_dev; its n, dtype and cfg.dim).

@@ -51,7 +51,7 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
     const unsigned grid = static_cast<unsigned>(nq * nchunks);
     const RefineArgs<TC, TQ> ra{q, cand, GATHER ? c->store_n : 0, B, d, cand_ids, cand_count, k, nchunks, out_ids, out_dist, out_count, scored, partial, pcnt, npieces, cpp, c->dbg_route};
     auto launch = [&](auto kern) -> int {
-        if (lds > 64 * 1024) FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+        if (lds > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, lds)) return rc;
         if (c->rt_on && (c->rt_seen++ % c->rt_every) == 0 && c->rt_used + 2 <= c->rt_events.size()) {   // start/stop events attached to this very dispatch
             hipExtLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, c->rt_events[c->rt_used], c->rt_events[c->rt_used + 1], 0, ra);
             c->rt_used += 2;
@@ -72,7 +72,7 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
         }
         if (!done) {
             auto kern = vec ? refine_scan_list_kernel<TC, TQ, DC, true, GATHER> : refine_scan_list_kernel<TC, TQ, DC, false, GATHER>;
-            if (lds > 64 * 1024) FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+            if (lds > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, lds)) return rc;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
         }
         FSP_HIP(hipGetLastError());
@@ -80,7 +80,7 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
             const size_t mlds = static_cast<size_t>(nchunks) * k * 8 + static_cast<size_t>(nchunks) * 4 + 16;
             if (mlds <= 72 * 1024) {
                 auto mk = refine_merge_list_kernel<true>;
-                if (mlds > 64 * 1024) FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mk), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
+                if (mlds > 64 * 1024) if (int rc = raise_lds_ceiling(c, mk, 72 * 1024)) return rc;
                 hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>(nq)), dim3(256), mlds, c->stream, partial, pcnt, nchunks, k, out_ids, out_dist, out_count, scored, qlist, qcount);
             } else {
                 hipLaunchKernelGGL(refine_merge_list_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(256), static_cast<size_t>(nchunks) * 4 + 16, c->stream, partial, pcnt,
@@ -102,38 +102,21 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
         hipEvent_t ev0 = timed ? c->rt_events[c->rt_used] : nullptr, ev1 = timed ? c->rt_events[c->rt_used + 1] : nullptr;
         if (timed) c->rt_used += 2;
         bool fixed = false;
-        if constexpr (std::is_same<TC, float>::value && std::is_same<TQ, float>::value && DC == 32) {
+        // fp32 queries over rows of at most four bytes at the default tile width (128 bytes; no hand-over kernel reads FSPANN_F64 rows)
+        if constexpr (std::is_same<TQ, float>::value && sizeof(TC) <= 4 && DC * sizeof(TC) == 128) {
             if (c->refine_fix_dev && nchunks == 1) {
                 // the batch's Route ran with a hand-over buffer: the scan's workgroups finish its PENDING queries first (tick.hip.h)
-                auto fk = refine_stream_fix_kernel<GATHER>;
-                const size_t flds = std::max(lds, c->refine_fix_lds);
-                const unsigned abit = GATHER ? 4096u : 8192u;
-                if (!(c->attr_mask & abit)) {
-                    FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                    c->attr_mask |= abit;
-                }
-                if (timed) hipExtLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ev0, ev1, 0, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
-                else hipLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
-                fixed = true;
-                c->refine_fix_used = true;
-            }
-        }
-        if constexpr ((std::is_same<TC, uint8_t>::value || std::is_same<TC, _Float16>::value || std::is_same<TC, fsp_bf16>::value || std::is_same<TC, fsp_f8e4m3>::value ||
-                       std::is_same<TC, int8_t>::value) && std::is_same<TQ, float>::value && DC * sizeof(TC) == 128) {
-            if (c->refine_fix_dev && nchunks == 1) {
-                // FSPANN_U8 / FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 / FSPANN_I8 rows: the same hand-over, the kernel with the row type as a template parameter
-                auto fk = refine_stream_fix_kernel<TC, GATHER>;
-                const size_t flds = std::max(lds, c->refine_fix_lds);
-                const uint64_t abit = std::is_same<TC, int8_t>::value ? (GATHER ? (uint64_t(1) << 32) : (uint64_t(1) << 33))   // (a bit pair per row type: one kernel each)
-                                      : std::is_same<TC, fsp_f8e4m3>::value ? (GATHER ? (1u << 30) : (1u << 31))
-                                      : std::is_same<TC, uint8_t>::value ? (GATHER ? (1u << 24) : (1u << 25))
-                                      : std::is_same<TC, fsp_bf16>::value ? (GATHER ? (1u << 28) : (1u << 29)) : (GATHER ? (1u << 26) : (1u << 27));
-                if (!(c->attr_mask & abit)) {
-                    FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                    c->attr_mask |= abit;
-                }
-                if (timed) hipExtLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ev0, ev1, 0, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
-                else hipLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
+                auto hand_over = [&](auto fk) -> int {
+                    const size_t flds = std::max(lds, c->refine_fix_lds);
+                    if (int rc = raise_lds_ceiling(c, fk, 159 * 1024)) return rc;
+                    if (timed) hipExtLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ev0, ev1, 0, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
+                    else hipLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
+                    return FSPANN_OK;
+                };
+                // fp32 rows have the kernel of their own; every narrower row type the one with the row type as a template parameter
+                if constexpr (std::is_same<TC, float>::value) { auto fk = refine_stream_fix_kernel<GATHER>; lrc = hand_over(fk); }
+                else { auto fk = refine_stream_fix_kernel<TC, GATHER>; lrc = hand_over(fk); }
+                if (lrc) return lrc;
                 fixed = true;
                 c->refine_fix_used = true;
             }
@@ -166,10 +149,7 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
         const size_t mlds = static_cast<size_t>(nchunks) * k * 8 + static_cast<size_t>(nchunks) * 4 + 16;
         if (mlds <= 72 * 1024) {
             auto mk = refine_merge_kernel<true>;
-            if (mlds > 64 * 1024 && !(c->attr_mask & 16384u)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mk), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024));
-                c->attr_mask |= 16384u;
-            }
+            if (mlds > 64 * 1024) if (int rc = raise_lds_ceiling(c, mk, 72 * 1024)) return rc;
             hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>(nq)), dim3(256), mlds, c->stream, partial, pcnt,
                                nchunks, k, out_ids, out_dist, out_count, scored);
         } else {
@@ -185,51 +165,51 @@ template <typename TC, typename TQ, bool GATHER>
 int launch_refine_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids,
                     const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
                     int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
-    constexpr int DC0 = (sizeof(TC) == 4) ? 32 : 16;
+    auto run = [&](auto dc) {
+        return launch_refine_dc<TC, TQ, decltype(dc)::value, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    };
+    // dims per tile.  One- and two-byte rows: a tile is 128 bytes (128 / 64 dims), FSPANN_REFINE_DC is an fp32 / fp64 notion and is
+    // ignored; FSPANN_F32 / FSPANN_F64 rows: 128 bytes unless FSPANN_REFINE_DC asks for twice or four times that
+    constexpr int DC0 = 128 / static_cast<int>(sizeof(TC));
     const int dc_env = c->knob_refine_dc;
     int rc;
-    // FSPANN_U8 rows: a tile is 128 bytes = 128 dims; FSPANN_REFINE_DC (32 / 64 / 128 dims) is an fp32 notion and is ignored
-    // FSPANN_F16 and FSPANN_BF16 rows likewise: a tile is 128 bytes = 64 dims; FSPANN_F8E4M3 and FSPANN_I8 rows have the byte geometry of FSPANN_U8
-    if constexpr (std::is_same<TC, _Float16>::value || std::is_same<TC, fsp_bf16>::value) rc = launch_refine_dc<TC, TQ, 64, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    else if constexpr (std::is_same<TC, uint8_t>::value || std::is_same<TC, fsp_f8e4m3>::value || std::is_same<TC, int8_t>::value) rc = launch_refine_dc<TC, TQ, 128, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    else if (dc_env == DC0 * 2) rc = launch_refine_dc<TC, TQ, DC0 * 2, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    else if (dc_env == DC0 * 4) rc = launch_refine_dc<TC, TQ, DC0 * 4, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    else rc = launch_refine_dc<TC, TQ, DC0, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+    if constexpr (sizeof(TC) < 4) rc = run(std::integral_constant<int, DC0>{});
+    else if (dc_env == DC0 * 2) rc = run(std::integral_constant<int, DC0 * 2>{});
+    else if (dc_env == DC0 * 4) rc = run(std::integral_constant<int, DC0 * 4>{});
+    else rc = run(std::integral_constant<int, DC0>{});
     if (rc) return rc;
     // the touched-record set (api_touch.hip.h): the rows this launch scores, marked behind it (nothing while tracking is off)
     return touch_mark<TC, TQ, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, qlist, qcount);
 }
 
-// fspann_refine_store_dev over the queries qlist[0 .. *qcount) only (device list; the retry pass and its host finish).
-int refine_store_list(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype, int64_t B, const int32_t* cand_ids_dev, const int32_t* cand_count_dev,
-                      int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev, const int32_t* qlist, const int32_t* qcount) {
-#define FSP_REF(TC, TQ)                                                                                            \
-    return launch_refine_t<TC, TQ, true>(c, nq, static_cast<const TQ*>(q_dev), static_cast<const TC*>(c->d_store), B, \
-                                         cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, \
-                                         scored_dev, qlist, qcount)
-    if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F32) FSP_REF(float, float);
-    if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F64) FSP_REF(float, double);
-    if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F32) FSP_REF(double, float);
-    if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F64) FSP_REF(double, double);
-    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F32) FSP_REF(uint8_t, float);
-    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F64) FSP_REF(uint8_t, double);
-    if (c->store_dtype == FSPANN_F16 && q_dtype == FSPANN_F32) FSP_REF(_Float16, float);
-    if (c->store_dtype == FSPANN_F16 && q_dtype == FSPANN_F64) FSP_REF(_Float16, double);
-    if (c->store_dtype == FSPANN_BF16 && q_dtype == FSPANN_F32) FSP_REF(fsp_bf16, float);
-    if (c->store_dtype == FSPANN_BF16 && q_dtype == FSPANN_F64) FSP_REF(fsp_bf16, double);
-    if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32) FSP_REF(fsp_f8e4m3, float);
-    if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F64) FSP_REF(fsp_f8e4m3, double);
-    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F32) FSP_REF(int8_t, float);
-    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F64) FSP_REF(int8_t, double);
-#undef FSP_REF
-    if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
-    if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
-    if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
-    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
-    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
+// The one way from (row dtype, query dtype) to the scan: rows at `rows` (dense blocks, or GATHER: the resident store), over every
+// query or (qlist / qcount, device; the retry pass and its host finish) over the queries qlist[0 .. *qcount) only.
+template <bool GATHER>
+int refine_typed(fspann_ctx* c, int row_dtype, int q_dtype, int64_t nq, const void* q_dev, const void* rows, int64_t B, const int32_t* cand_ids_dev,
+                 const int32_t* cand_count_dev, int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev,
+                 const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
+    int rc = FSPANN_OK;
+    bool launched = false;
+    with_query_type(q_dtype, [&](auto tq) {
+        launched = with_row_type(row_dtype, [&](auto tc) {
+            using TQ = typename decltype(tq)::type;
+            using TC = typename decltype(tc)::type;
+            rc = launch_refine_t<TC, TQ, GATHER>(c, nq, static_cast<const TQ*>(q_dev), static_cast<const TC*>(rows), B, cand_ids_dev, cand_count_dev, k, out_ids_dev,
+                                                 out_dist_dev, out_count_dev, scored_dev, qlist, qcount);
+        });
+    });
+    if (launched) return rc;
+    if ((rc = refuse_row_only(q_dtype, "q_dtype"))) return rc;
+    if (!is_query_dtype(q_dtype)) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
     return fail(FSPANN_E_ARG, "unknown dtype");
 }
 
+// fspann_refine_store_dev over the queries qlist[0 .. *qcount) only (device list; the retry pass and its host finish).
+int refine_store_list(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype, int64_t B, const int32_t* cand_ids_dev, const int32_t* cand_count_dev,
+                      int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev, const int32_t* qlist, const int32_t* qcount) {
+    return refine_typed<true>(c, c->store_dtype, q_dtype, nq, q_dev, c->d_store, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev,
+                              qlist, qcount);
+}
 
 }  // namespace
 
@@ -245,31 +225,7 @@ int fspann_refine_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
     if (nq == 0) return FSPANN_OK;
     if (!q_dev || !cand_dev || !cand_ids_dev || !cand_count_dev || !out_ids_dev || !out_dist_dev || !out_count_dev)
         return fail(FSPANN_E_NULL, "refine buffer is null");
-#define FSP_REF(TC, TQ)                                                                                          \
-    return launch_refine_t<TC, TQ, false>(c, nq, static_cast<const TQ*>(q_dev), static_cast<const TC*>(cand_dev), B, \
-                                   cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev,    \
-                                   scored_dev)
-    if (cand_dtype == FSPANN_F32 && q_dtype == FSPANN_F32) FSP_REF(float, float);
-    if (cand_dtype == FSPANN_F32 && q_dtype == FSPANN_F64) FSP_REF(float, double);
-    if (cand_dtype == FSPANN_F64 && q_dtype == FSPANN_F32) FSP_REF(double, float);
-    if (cand_dtype == FSPANN_F64 && q_dtype == FSPANN_F64) FSP_REF(double, double);
-    if (cand_dtype == FSPANN_U8 && q_dtype == FSPANN_F32) FSP_REF(uint8_t, float);
-    if (cand_dtype == FSPANN_U8 && q_dtype == FSPANN_F64) FSP_REF(uint8_t, double);
-    if (cand_dtype == FSPANN_F16 && q_dtype == FSPANN_F32) FSP_REF(_Float16, float);
-    if (cand_dtype == FSPANN_F16 && q_dtype == FSPANN_F64) FSP_REF(_Float16, double);
-    if (cand_dtype == FSPANN_BF16 && q_dtype == FSPANN_F32) FSP_REF(fsp_bf16, float);
-    if (cand_dtype == FSPANN_BF16 && q_dtype == FSPANN_F64) FSP_REF(fsp_bf16, double);
-    if (cand_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32) FSP_REF(fsp_f8e4m3, float);
-    if (cand_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F64) FSP_REF(fsp_f8e4m3, double);
-    if (cand_dtype == FSPANN_I8 && q_dtype == FSPANN_F32) FSP_REF(int8_t, float);
-    if (cand_dtype == FSPANN_I8 && q_dtype == FSPANN_F64) FSP_REF(int8_t, double);
-#undef FSP_REF
-    if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
-    if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
-    if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
-    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
-    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
-    return fail(FSPANN_E_ARG, "unknown dtype");
+    return refine_typed<false>(c, cand_dtype, q_dtype, nq, q_dev, cand_dev, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev);
 }
 
 int fspann_refine(fspann_ctx* c, int64_t nq, const void* q, const void* cand, int dtype, int64_t B,
@@ -280,13 +236,10 @@ int fspann_refine(fspann_ctx* c, int64_t nq, const void* q, const void* cand, in
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
     if (!q || !cand || !cand_ids || !cand_count || !out_ids || !out_dist || !out_count) return fail(FSPANN_E_NULL, "refine buffer is null");
-    if (dtype == FSPANN_U8) return fail(FSPANN_E_ARG, "dtype FSPANN_U8: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (byte rows: fspann_refine_dev)");
-    if (dtype == FSPANN_F16) return fail(FSPANN_E_ARG, "dtype FSPANN_F16: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (half rows: fspann_refine_dev)");
-    if (dtype == FSPANN_BF16) return fail(FSPANN_E_ARG, "dtype FSPANN_BF16: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (bfloat16 rows: fspann_refine_dev)");
-    if (dtype == FSPANN_F8E4M3) return fail(FSPANN_E_ARG, "dtype FSPANN_F8E4M3: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (fp8 rows: fspann_refine_dev)");
-    if (dtype == FSPANN_I8) return fail(FSPANN_E_ARG, "dtype FSPANN_I8: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (signed byte rows: fspann_refine_dev)");
-    if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
-    const size_t esz = dtype == FSPANN_F64 ? 8 : 4;
+    if (const DtypeInfo* di = dtype_info(dtype); di && di->rows_noun)
+        return fail(FSPANN_E_ARG, "dtype %s: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (%s: fspann_refine_dev)", di->name, di->rows_noun);
+    if (!is_query_dtype(dtype)) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
+    const size_t esz = dtype_size(dtype);
     const int d = c->cfg.dim;
     const size_t qb = static_cast<size_t>(nq) * d * esz, cb = static_cast<size_t>(nq) * B * d * esz;
     const size_t ib = static_cast<size_t>(nq) * B * 4, nb = static_cast<size_t>(nq) * 4;
@@ -426,31 +379,7 @@ int fspann_refine_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     if (nq == 0) return FSPANN_OK;
     if (!q_dev || !cand_ids_dev || !cand_count_dev || !out_ids_dev || !out_dist_dev || !out_count_dev)
         return fail(FSPANN_E_NULL, "refine buffer is null");
-#define FSP_REF(TC, TQ)                                                                                            \
-    return launch_refine_t<TC, TQ, true>(c, nq, static_cast<const TQ*>(q_dev), static_cast<const TC*>(c->d_store), B, \
-                                         cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, \
-                                         scored_dev)
-    if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F32) FSP_REF(float, float);
-    if (c->store_dtype == FSPANN_F32 && q_dtype == FSPANN_F64) FSP_REF(float, double);
-    if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F32) FSP_REF(double, float);
-    if (c->store_dtype == FSPANN_F64 && q_dtype == FSPANN_F64) FSP_REF(double, double);
-    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F32) FSP_REF(uint8_t, float);
-    if (c->store_dtype == FSPANN_U8 && q_dtype == FSPANN_F64) FSP_REF(uint8_t, double);
-    if (c->store_dtype == FSPANN_F16 && q_dtype == FSPANN_F32) FSP_REF(_Float16, float);
-    if (c->store_dtype == FSPANN_F16 && q_dtype == FSPANN_F64) FSP_REF(_Float16, double);
-    if (c->store_dtype == FSPANN_BF16 && q_dtype == FSPANN_F32) FSP_REF(fsp_bf16, float);
-    if (c->store_dtype == FSPANN_BF16 && q_dtype == FSPANN_F64) FSP_REF(fsp_bf16, double);
-    if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F32) FSP_REF(fsp_f8e4m3, float);
-    if (c->store_dtype == FSPANN_F8E4M3 && q_dtype == FSPANN_F64) FSP_REF(fsp_f8e4m3, double);
-    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F32) FSP_REF(int8_t, float);
-    if (c->store_dtype == FSPANN_I8 && q_dtype == FSPANN_F64) FSP_REF(int8_t, double);
-#undef FSP_REF
-    if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
-    if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
-    if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
-    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
-    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
-    return fail(FSPANN_E_ARG, "unknown dtype");
+    return refine_typed<true>(c, c->store_dtype, q_dtype, nq, q_dev, c->d_store, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev);
 }
 
 int fspann_refine_store(fspann_ctx* c, int64_t nq, const void* q, int q_dtype, int64_t B, const int32_t* cand_ids,
@@ -462,12 +391,9 @@ int fspann_refine_store(fspann_ctx* c, int64_t nq, const void* q, int q_dtype, i
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
     if (!q || !cand_ids || !cand_count || !out_ids || !out_dist || !out_count) return fail(FSPANN_E_NULL, "refine buffer is null");
-    if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");
-    if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");
-    if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");
-    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");
-    if (q_dtype != FSPANN_F32 && q_dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
-    const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * (q_dtype == FSPANN_F64 ? 8 : 4);
+    if (int rc = refuse_row_only(q_dtype, "q_dtype")) return rc;
+    if (!is_query_dtype(q_dtype)) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
+    const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * dtype_size(q_dtype);
     const size_t ib = static_cast<size_t>(nq) * B * 4, nb = static_cast<size_t>(nq) * 4;
     const size_t ob_i = static_cast<size_t>(nq) * k * 4, ob_d = static_cast<size_t>(nq) * k * 8;
     int rc;
@@ -532,35 +458,12 @@ int fspann_store_gather_dev(fspann_ctx* c, int64_t nq, const int32_t* sel_ids_de
     const int d = c->cfg.dim;
     const int64_t rows = nq * B;
     const unsigned grid = static_cast<unsigned>((rows + 7) / 8);
-    if (c->store_dtype == FSPANN_F32) {
-        const int vec_ok = (d % 4 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<float>, dim3(grid), dim3(256), 0, c->stream, static_cast<const float*>(c->d_store), d,
-                           sel_ids_dev, sel_count_dev, B, nq, static_cast<float*>(cand_dev), vec_ok);
-    } else if (c->store_dtype == FSPANN_F16) {
-        const int vec_ok = (d % 8 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<_Float16>, dim3(grid), dim3(256), 0, c->stream, static_cast<const _Float16*>(c->d_store), d,
-                           sel_ids_dev, sel_count_dev, B, nq, static_cast<_Float16*>(cand_dev), vec_ok);
-    } else if (c->store_dtype == FSPANN_BF16) {
-        const int vec_ok = (d % 8 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<fsp_bf16>, dim3(grid), dim3(256), 0, c->stream, static_cast<const fsp_bf16*>(c->d_store), d,
-                           sel_ids_dev, sel_count_dev, B, nq, static_cast<fsp_bf16*>(cand_dev), vec_ok);
-    } else if (c->store_dtype == FSPANN_F8E4M3) {
-        const int vec_ok = (d % 16 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<fsp_f8e4m3>, dim3(grid), dim3(256), 0, c->stream, static_cast<const fsp_f8e4m3*>(c->d_store), d,
-                           sel_ids_dev, sel_count_dev, B, nq, static_cast<fsp_f8e4m3*>(cand_dev), vec_ok);
-    } else if (c->store_dtype == FSPANN_I8) {
-        const int vec_ok = (d % 16 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<int8_t>, dim3(grid), dim3(256), 0, c->stream, static_cast<const int8_t*>(c->d_store), d,
-                           sel_ids_dev, sel_count_dev, B, nq, static_cast<int8_t*>(cand_dev), vec_ok);
-    } else if (c->store_dtype == FSPANN_U8) {
-        const int vec_ok = (d % 16 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, c->stream, static_cast<const uint8_t*>(c->d_store), d,
-                           sel_ids_dev, sel_count_dev, B, nq, static_cast<uint8_t*>(cand_dev), vec_ok);
-    } else {
-        const int vec_ok = (d % 2 == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<double>, dim3(grid), dim3(256), 0, c->stream, static_cast<const double*>(c->d_store), d,
-                           sel_ids_dev, sel_count_dev, B, nq, static_cast<double*>(cand_dev), vec_ok);
-    }
+    with_row_type(c->store_dtype, [&](auto tc) {      // (a store has a row dtype: fspann_store_set / _attach_dev)
+        using T = typename decltype(tc)::type;
+        const int vec_ok = (d % VecOf<T>::N == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
+        hipLaunchKernelGGL(store_gather_kernel<T>, dim3(grid), dim3(256), 0, c->stream, static_cast<const T*>(c->d_store), d, sel_ids_dev, sel_count_dev, B, nq,
+                           static_cast<T*>(cand_dev), vec_ok);
+    });
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
 }

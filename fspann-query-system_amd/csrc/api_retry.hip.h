@@ -75,18 +75,15 @@ int route_list_dev(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int pro
     }
     c->last_route_lazy = pl.lazy;
     if (pl.lazy) {
-        auto go = [&](auto lk, unsigned abit) -> int {
-            if (abit && !(c->attr_mask & abit)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                c->attr_mask |= abit;
-            }
+        auto go = [&](auto lk, bool big) -> int {      // big: the size class plans with more than the default 64 KB of LDS
+            if (big) if (int r = raise_lds_ceiling(c, lk, 159 * 1024)) return r;
             hipLaunchKernelGGL(lk, dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
             FSP_HIP(hipGetLastError());
             return FSPANN_OK;
         };
-        if (pl.lz_entries == 512) rc = go(route_select_lazy_list_kernel<kLzThreads, 512, false>, 0u);
-        else if (pl.lz_entries == 2048) rc = go(route_select_lazy_list_kernel<kLzThreads, 2048, true>, 1u << 20);
-        else rc = go(route_select_lazy_list_kernel<kLzThreads, kLzEntriesMax, true>, 1u << 21);
+        if (pl.lz_entries == 512) rc = go(route_select_lazy_list_kernel<kLzThreads, 512, false>, false);
+        else if (pl.lz_entries == 2048) rc = go(route_select_lazy_list_kernel<kLzThreads, 2048, true>, true);
+        else rc = go(route_select_lazy_list_kernel<kLzThreads, kLzEntriesMax, true>, true);
         if (rc) return rc;
         // the queries the bounded select handed over (none, normally): the full select over its overflow list, as fspann_route_dev
         p.qcount = p.ovf_count; p.qlist = p.ovf_list;
@@ -231,10 +228,7 @@ int fspann_search_retry_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev,
                                    int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, int32_t* retried_dev, int64_t* resolved) {
     CHECK_CTX(c);
     if (resolved) *resolved = 0;
-    if (q_dtype == FSPANN_F16) return refuse_f16("q_dtype");     // (whether or not a query is left to finish)
-    if (q_dtype == FSPANN_BF16) return refuse_bf16("q_dtype");     // (whether or not a query is left to finish)
-    if (q_dtype == FSPANN_F8E4M3) return refuse_f8("q_dtype");     // (whether or not a query is left to finish)
-    if (q_dtype == FSPANN_I8) return refuse_i8("q_dtype");        // (whether or not a query is left to finish)
+    if (int rc = refuse_row_only(q_dtype, "q_dtype")) return rc;     // (whether or not a query is left to finish)
     int rc = check_retry_args(c, nq, q_dev, B, k, out_ids_dev, out_dist_dev, out_count_dev);
     if (rc || nq == 0) return rc;
     SearchArea sa;

@@ -239,12 +239,7 @@ int launch_full_select(fspann_ctx* c, const RoutePlan& pl, const RouteParams& p)
 #define FSP_LAUNCH_SEL(LDS, THR)                                                                                         \
     do {                                                                                                                 \
         auto kern = route_select_kernel<LDS, THR>;                                                                       \
-        const unsigned abit = 1u << ((LDS ? 0 : 2) + (THR == 1024 ? 1 : 0));                                             \
-        if (!(c->attr_mask & abit)) {   /* once per context: the attribute is the ceiling, not the launch size */        \
-            FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        159 * 1024));                                                                    \
-            c->attr_mask |= abit;                                                                                        \
-        }                                                                                                                \
+        if (int rc = raise_lds_ceiling(c, kern, 159 * 1024)) return rc;   /* the ceiling, not the launch size */          \
         hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(THR), pl.lds_bytes, c->stream, p, p.probe_g, p.nprobe_g);           \
     } while (0)
     if (pl.lds_mode) { if (pl.threads == 1024) FSP_LAUNCH_SEL(true, 1024); else FSP_LAUNCH_SEL(true, 512); }
@@ -280,17 +275,11 @@ int route_dev_impl(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int pro
                 hipLaunchKernelGGL((route_select_lazy_kernel<kLzThreads, 512, false>), dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
         } else if (pl.lz_entries == 2048) {
             auto lk = route_select_lazy_kernel<kLzThreads, 2048, true>;
-            if (!(c->attr_mask & 1024u)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                c->attr_mask |= 1024u;
-            }
+            if ((rc = raise_lds_ceiling(c, lk, 159 * 1024))) return rc;
             hipLaunchKernelGGL(lk, dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
         } else {
             auto lk = route_select_lazy_kernel<kLzThreads, kLzEntriesMax, true>;
-            if (!(c->attr_mask & 16u)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                c->attr_mask |= 16u;
-            }
+            if ((rc = raise_lds_ceiling(c, lk, 159 * 1024))) return rc;
             hipLaunchKernelGGL(lk, dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
         }
         FSP_HIP(hipGetLastError());

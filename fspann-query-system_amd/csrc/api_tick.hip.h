@@ -130,8 +130,9 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         // FSPANN_REFINE_DC = 64 / 128 the plain scan would run first and read PENDING as "no rows")
         // (FSPANN_U8 rows: the U8 refine_stream_fix_kernel, 16 dims per 16-byte slot, always at its one tile width)
         // (FSPANN_F16 / FSPANN_BF16 rows: the same overload, 8 dims per slot; FSPANN_F8E4M3 and FSPANN_I8 rows: 16 dims per slot, like U8)
-        const bool rows_ok = (rows_dtype == FSPANN_U8 || rows_dtype == FSPANN_F8E4M3 || rows_dtype == FSPANN_I8) ? (d % 16 == 0) : (rows_dtype == FSPANN_F16 || rows_dtype == FSPANN_BF16) ? (d % 8 == 0)
-                                                     : (rows_dtype == FSPANN_F32 && (d % 4 == 0) && (c->knob_refine_dc == 0 || c->knob_refine_dc == 32));
+        // (whole 16-byte slots of 16 / element size dims, refine.hip.h's VecOf<TC>::N; no hand-over kernel reads FSPANN_F64 rows)
+        const bool rows_ok = is_row_dtype(rows_dtype) && rows_dtype != FSPANN_F64 && d % static_cast<int>(16 / dtype_size(rows_dtype)) == 0 &&
+                             (rows_dtype != FSPANN_F32 || c->knob_refine_dc == 0 || c->knob_refine_dc == 32);
         const bool stream_ok = rows_ok &&
                                t->ref_q_dtype == FSPANN_F32 && nchunks == 1 &&
                                ((reinterpret_cast<uintptr_t>(rows) & 15) == 0) && c->knob_refine_stream != 0 && c->knob_tick_fuse != 0;
@@ -141,10 +142,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
             if ((rc = upload_fix(pX, &fdev))) return rc;
         } else if (fix) {
             auto fk = tick_fix_kernel;
-            if (!(c->attr_mask & 64u)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                c->attr_mask |= 64u;
-            }
+            if ((rc = raise_lds_ceiling(c, fk, 159 * 1024))) return rc;
             hipLaunchKernelGGL(fk, dim3(static_cast<unsigned>(t->nq_refine)), dim3(kTickThreads), plX.small_bytes, c->stream, pX);
             FSP_HIP(hipGetLastError());
         }
@@ -170,10 +168,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         if (R && plR.lazy) c->ovf_flip ^= 1;
         if (fix) {
             auto fk = tick_fix_kernel;
-            if (!(c->attr_mask & 64u)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                c->attr_mask |= 64u;
-            }
+            if ((rc = raise_lds_ceiling(c, fk, 159 * 1024))) return rc;
             hipLaunchKernelGGL(fk, dim3(static_cast<unsigned>(t->nq_refine)), dim3(kTickThreads), plX.small_bytes, c->stream, pX);
             FSP_HIP(hipGetLastError());
         }
@@ -243,11 +238,8 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
     fixT.dbg = nullptr;
     const int64_t total = static_cast<int64_t>(p.n_enc) + p.n_route + p.n_refine;
     if (total > INT32_MAX) return fail(FSPANN_E_RANGE, "too many workgroups in one tick");
-    auto launch = [&](auto kern, unsigned abit) -> int {
-        if (!(c->attr_mask & abit)) {
-            FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-            c->attr_mask |= abit;
-        }
+    auto launch = [&](auto kern) -> int {
+        if (int r = raise_lds_ceiling(c, kern, 159 * 1024)) return r;
         hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(total)), dim3(kTickThreads), lds, c->stream, p, eaT, routeT, fix_dev, raT);
         FSP_HIP(hipGetLastError());
         return FSPANN_OK;
@@ -260,15 +252,12 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
                 hipLaunchKernelGGL((front_kernel<512, false>), dim3(static_cast<unsigned>(total)), dim3(kTickThreads), lds, c->stream, p, eaT, routeT);
         } else {
             auto fk = front_kernel<kLzEntriesMax, true>;
-            if (!(c->attr_mask & 2048u)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fk), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                c->attr_mask |= 2048u;
-            }
+            if ((rc = raise_lds_ceiling(c, fk, 159 * 1024))) return rc;
             hipLaunchKernelGGL(fk, dim3(static_cast<unsigned>(total)), dim3(kTickThreads), lds, c->stream, p, eaT, routeT);
         }
         FSP_HIP(hipGetLastError());
     } else {
-        if ((rc = gather ? launch(tick_kernel<true>, 128u) : launch(tick_kernel<false>, 256u))) return rc;
+        if ((rc = gather ? launch(tick_kernel<true>) : launch(tick_kernel<false>))) return rc;
         // the refine role's rows, from F_q as the tick leaves it (PENDING queries finished); the stand-alone paths above mark
         // inside their refine calls
         if (F && (rc = gather ? touch_mark<float, float, true>(c, t->nq_refine, static_cast<const float*>(t->ref_q_dev), static_cast<const float*>(rows),
@@ -283,10 +272,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         const int g2 = std::min(plR.grid, 32);
         auto kern = route_select_kernel<true, 512>;
         if (plR.lds_mode && plR.threads == 512) {
-            if (!(c->attr_mask & 1u)) {
-                FSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-                c->attr_mask |= 1u;
-            }
+            if ((rc = raise_lds_ceiling(c, kern, 159 * 1024))) return rc;
             hipLaunchKernelGGL(kern, dim3(g2), dim3(512), plR.lds_bytes, c->stream, q2, q2.probe_g, q2.nprobe_g);
             FSP_HIP(hipGetLastError());
         } else {

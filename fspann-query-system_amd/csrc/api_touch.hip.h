@@ -39,23 +39,16 @@ int touch_store_ok(fspann_ctx* c) {
     if (rc) return rc;
     const int d = c->cfg.dim;
     const unsigned grid = static_cast<unsigned>((c->store_n + kTouchThreads / 64 - 1) / (kTouchThreads / 64));
-    if (c->store_dtype == FSPANN_U8 || c->store_dtype == FSPANN_I8)   // a byte, unsigned or signed, is always finite: every row is valid
-        FSP_HIP(hipMemsetAsync(c->store_ok.p, 1, static_cast<size_t>(c->store_n), c->stream));
-    else if (c->store_dtype == FSPANN_F16)  // a half can be +-inf or NaN, like a float
-        hipLaunchKernelGGL(touch_store_valid_kernel<_Float16>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const _Float16*>(c->d_store),
-                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
-    else if (c->store_dtype == FSPANN_BF16) // so can a bfloat16
-        hipLaunchKernelGGL(touch_store_valid_kernel<fsp_bf16>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const fsp_bf16*>(c->d_store),
-                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
-    else if (c->store_dtype == FSPANN_F8E4M3)   // an fp8 has no infinity but two NaN patterns
-        hipLaunchKernelGGL(touch_store_valid_kernel<fsp_f8e4m3>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const fsp_f8e4m3*>(c->d_store),
-                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
-    else if (c->store_dtype == FSPANN_F64)
-        hipLaunchKernelGGL(touch_store_valid_kernel<double>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const double*>(c->d_store),
-                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
-    else
-        hipLaunchKernelGGL(touch_store_valid_kernel<float>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const float*>(c->d_store),
-                           c->store_n, d, static_cast<uint8_t*>(c->store_ok.p));
+    hipError_t set = hipSuccess;
+    with_row_type(c->store_dtype, [&](auto tr) {
+        using T = typename decltype(tr)::type;
+        if constexpr (DtypeOf<T>::finite)     // a byte, unsigned or signed, is always finite: every row is valid
+            set = hipMemsetAsync(c->store_ok.p, 1, static_cast<size_t>(c->store_n), c->stream);
+        else                                  // a float, a double, a half and a bfloat16 can be +-inf or NaN; an fp8 has no infinity but two NaN patterns
+            hipLaunchKernelGGL(touch_store_valid_kernel<T>, dim3(grid), dim3(kTouchThreads), 0, c->stream, static_cast<const T*>(c->d_store), c->store_n, d,
+                               static_cast<uint8_t*>(c->store_ok.p));
+    });
+    FSP_HIP(set);
     FSP_HIP(hipGetLastError());
     c->store_ok_gen = c->store_gen;
     return FSPANN_OK;

@@ -89,6 +89,13 @@ __global__ __launch_bounds__(256) void build_widen_f8_kernel(const fsp_f8e4m3* _
     }
 }
 
+// row type -> its widen kernel (host side: api_build.hip.h launches build_widen_kernel of the row pointer's type)
+inline auto build_widen_kernel(const uint8_t*) { return build_widen_u8_kernel; }
+inline auto build_widen_kernel(const int8_t*) { return build_widen_i8_kernel; }
+inline auto build_widen_kernel(const _Float16*) { return build_widen_f16_kernel; }
+inline auto build_widen_kernel(const fsp_bf16*) { return build_widen_bf16_kernel; }
+inline auto build_widen_kernel(const fsp_f8e4m3*) { return build_widen_f8_kernel; }
+
 __global__ __launch_bounds__(kRsThreads) void rs_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
                                                              int nblocks, uint32_t* __restrict__ tot) {
     __shared__ uint32_t h[256];

@@ -43,32 +43,6 @@ inline int fail(int code, const char* fmt, ...) {
                                   __LINE__);                                                       \
     } while (0)
 
-// bytes per element of a dtype of include/fspann.h (the callers have checked which dtypes they take)
-inline size_t dtype_size(int dtype) {
-    return dtype == FSPANN_F64 ? 8 : ((dtype == FSPANN_U8 || dtype == FSPANN_F8E4M3 || dtype == FSPANN_I8) ? 1 : ((dtype == FSPANN_F16 || dtype == FSPANN_BF16) ? 2 : 4));
-}
-// the row dtypes: what fspann_store_set / _attach_dev, fspann_build_index / _append and the rows of a refinement take
-inline bool is_row_dtype(int dtype) {
-    return dtype == FSPANN_F32 || dtype == FSPANN_F64 || dtype == FSPANN_U8 || dtype == FSPANN_F16 || dtype == FSPANN_BF16 || dtype == FSPANN_F8E4M3 ||
-           dtype == FSPANN_I8;
-}
-// FSPANN_F16 given where no half can stand (a query, the point store, the ground truth): refused by name
-inline int refuse_f16(const char* what) {
-    return fail(FSPANN_E_ARG, "%s FSPANN_F16: half precision is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
-}
-// FSPANN_BF16 likewise
-inline int refuse_bf16(const char* what) {
-    return fail(FSPANN_E_ARG, "%s FSPANN_BF16: bfloat16 is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
-}
-// FSPANN_F8E4M3 likewise
-inline int refuse_f8(const char* what) {
-    return fail(FSPANN_E_ARG, "%s FSPANN_F8E4M3: fp8 e4m3fn is a row dtype only (store, refine rows, Setup input, metrics base); this one is FSPANN_F32 or FSPANN_F64", what);
-}
-// FSPANN_I8 likewise (an int8 row element is a plain int8_t: the integer it holds, always finite)
-inline int refuse_i8(const char* what) {
-    return fail(FSPANN_E_ARG, "%s FSPANN_I8: signed int8 is a row dtype only (store, refine rows, Setup input, metrics and ground truth over int8 pairs); this one is FSPANN_F32 or FSPANN_F64", what);
-}
-
 // One FSPANN_BF16 row element: 16 bits b, value = the fp32 whose bit pattern is b << 16 (every bfloat16, subnormals, +-0, +-inf and
 // NaN included).  A type of its own, so that a bf16 row is never taken for a half or for a uint16_t id.  Widening is a shift: exact,
 // no conversion instruction that could round or flush.
@@ -102,6 +76,10 @@ struct fsp_f8e4m3 {
 static_assert(sizeof(fsp_f8e4m3) == 1 && alignof(fsp_f8e4m3) == 1, "an fp8 row element is one byte");
 // an element is NaN iff all seven bits under the sign are set (the format has no infinity)
 __host__ __device__ __forceinline__ bool f8e4m3_finite(fsp_f8e4m3 x) { return (x.b & 0x7fu) != 0x7fu; }
+
+}  // namespace fspann
+#include "dtypes.h"     // the table of the dtypes, their dispatchers and the refusal by name
+namespace fspann {
 
 // ---- order-key bit budget (DESIGN.md "Java order key") ----------------------------
 // key = score(10) | bucket(20) | seq(22); seq = (td*P + step)*S + pos is unique per tuple.
@@ -216,7 +194,10 @@ struct fspann_ctx {
     bool rt_on = false;
     fspann::DevBuf ws_search;        // codes / F_q ids / counts of fspann_search_store_dev
     fspann::DevBuf ws_retry;         // pick list, its count, retried / scored of fspann_search_retry_dev (api_retry.hip.h)
-    uint64_t attr_mask = 0;          // kernels whose dynamic-LDS ceiling has been raised on this context's device (one bit per kernel; bits 32-33: the FSPANN_I8 hand-over pair)
+    struct LdsCeiling { const void* kernel; size_t bytes; };
+    static constexpr int kLdsCeilings = 64;
+    LdsCeiling lds_ceilings[kLdsCeilings] = {};   // kernels whose dynamic-LDS ceiling this context has raised on its device, and to what (raise_lds_ceiling)
+    int n_lds_ceilings = 0;
     int ovf_flip = 0;                // which of the two overflow counters the last bounded select used
     unsigned ovf_gen_seen = 0;       // ws_ovf.gen whose counters have been zeroed (0 = never)
     int last_route_lazy = 0;         // 1 if the last fspann_route[_dev] ran the bounded select
@@ -301,6 +282,25 @@ inline int ensure(fspann_ctx* c, DevBuf& b, size_t bytes) {
     FSP_HIP(hipMalloc(&b.p, want));
     b.bytes = want;
     b.gen++;
+    return FSPANN_OK;
+}
+
+// Launches that need more than the default 64 KB of dynamic LDS: hipFuncAttributeMaxDynamicSharedMemorySize of `kernel` is raised to
+// `bytes` unless this context has already raised it that far (the attribute is a ceiling, not the launch size; a clone keeps its
+// own record).  A few dozen kernels at most: a flat array scanned linearly, nothing allocated on the launch path.
+template <class K> int raise_lds_ceiling(fspann_ctx* c, K kernel, size_t bytes) {
+    const void* key = reinterpret_cast<const void*>(kernel);
+    fspann_ctx::LdsCeiling* e = c->lds_ceilings;
+    fspann_ctx::LdsCeiling* const end = e + c->n_lds_ceilings;
+    while (e != end && e->kernel != key) e++;
+    if (e != end && e->bytes >= bytes) return FSPANN_OK;
+    FSP_HIP(hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+    if (e == end) {
+        if (c->n_lds_ceilings == fspann_ctx::kLdsCeilings) return FSPANN_OK;     // (a full record: this kernel is raised at every launch)
+        c->n_lds_ceilings++;
+        e->kernel = key;
+    }
+    e->bytes = bytes;
     return FSPANN_OK;
 }
 

@@ -77,6 +77,10 @@ template <> struct RowIsBf16<fsp_bf16> { static constexpr bool value = true; };
 // OCP e4m3fn value and, unlike a byte, can be NaN (0x7F / 0xFF; the format has no infinity).
 typedef uint64_t fsp_f8x16 __attribute__((ext_vector_type(2)));
 template <> struct VecOf<fsp_f8e4m3> { using type = fsp_f8x16; static constexpr int N = 16; };
+// every row type fills a 16-byte slot: what the host computes as 16 / element size (api_tick.hip.h) is VecOf<TC>::N
+#define FSPANN_SLOT_CHECK(ID, T, QUERY, FINITE, WORDS, USES, NOUN) static_assert(VecOf<T>::N == 16 / sizeof(T), #ID ": elements per 16-byte slot");
+FSPANN_DTYPE_TABLE(FSPANN_SLOT_CHECK)
+#undef FSPANN_SLOT_CHECK
 template <typename T> struct RowIsF8 { static constexpr bool value = false; };
 template <> struct RowIsF8<fsp_f8e4m3> { static constexpr bool value = true; };
 // Which hardware conversion widens an fp8 slot (both exact; a switch so that the two can be A/B-ed): 0 = v_cvt_pk_f32_fp8, one

@@ -41,7 +41,7 @@ def kernel_isa(so):
         if cur is None or not line.startswith("\t"):
             continue
         ins = line.split("//")[0].strip()
-        if ins:
+        if ins and ins != "...":      # "...": objdump's elision of the zero padding behind a kernel (depends on what the linker placed next)
             cur.append(re.sub(r"\s+", " ", ins))
     return out
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h).
+"""ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -86,7 +86,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -208,6 +208,13 @@ _SIGS_ROWS = {
     "fspann_groundtruth_store_dev": (_i, [_vp, _i64, _vp, _i, _vp, _vp]),
 }
 
+# include/fspann_eval.h: runQueries' fallback search and its metrics at every k (a third table: the two sets above stay as they are)
+_SIGS_EVAL = {
+    "fspann_eval_kvariants_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, C.POINTER(_i32), _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "fspann_search_fallback_dev": (_i, [_vp, _i64, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fspann_search_fallback_finish_dev": (_i, [_vp, _i64, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
@@ -218,7 +225,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -240,3 +247,8 @@ def exported_symbols():
 def rows_symbols():
     """the entry points of include/fspann_groundtruth_rows.h"""
     return sorted(_SIGS_ROWS)
+
+
+def eval_symbols():
+    """the entry points of include/fspann_eval.h"""
+    return sorted(_SIGS_EVAL)

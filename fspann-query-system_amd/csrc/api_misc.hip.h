@@ -30,6 +30,8 @@ int fspann_groundtruth_dev(fspann_ctx* c, int64_t n, const float* base_dev, int6
     return FSPANN_OK;
 }
 
+// (Every check stands before the `nq == 0` return, and nq == 0 launches nothing: fspann_eval_kvariants_dev, api_eval.hip.h, runs
+// fspann_eval_metrics_typed_dev with nq = 0 as ITS argument check.  Keep that order here and there.)
 int fspann_eval_metrics_dev(fspann_ctx* c, int64_t n, const float* base_dev, int64_t nq, const float* q_dev, int dim, int k, const int32_t* ann_ids_dev,
                             int64_t ann_stride, const int32_t* ann_count_dev, const int32_t* gt_ids_dev, int64_t gt_stride, double* recall_dev,
                             double* ratio_dev) {
@@ -124,6 +126,11 @@ int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev,
     return FSPANN_OK;
 }
 
+// This function is also the argument check of fspann_eval_kvariants_dev (api_eval.hip.h), which calls it with nq = 0 and relies on
+// two things: every refusal below (null buffers, the dtype pair, n, dim, k, the strides) is decided BEFORE the `nq == 0` return,
+// on both branches (the FSPANN_F32 one forwards to fspann_eval_metrics_dev), and nq == 0 launches nothing.  A check added or
+// moved behind that return is a check the one-launch call loses; tests/test_gpu_eval_kvariants.py::test_refusals holds both
+// calls to the same refusals.
 int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev, int q_dtype, int dim, int k,
                                   const int32_t* ann_ids_dev, int64_t ann_stride, const int32_t* ann_count_dev, const int32_t* gt_ids_dev,
                                   int64_t gt_stride, double* recall_dev, double* ratio_dev) {

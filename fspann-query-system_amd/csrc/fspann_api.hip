@@ -15,6 +15,7 @@
 #include "build.hip.h"
 #include "encode.hip.h"
 #include "groundtruth.hip.h"
+#include "eval_sweep.hip.h"
 #include "groundtruth_u8.hip.h"
 #include "hostpipe.hip.h"
 #include "refine.hip.h"
@@ -38,3 +39,4 @@
 #include "api_build.hip.h"
 #include "api_ext.hip.h"
 #include "api_retry.hip.h"
+#include "api_eval.hip.h"

@@ -194,6 +194,7 @@ struct fspann_ctx {
     bool rt_on = false;
     fspann::DevBuf ws_search;        // codes / F_q ids / counts of fspann_search_store_dev
     fspann::DevBuf ws_retry;         // pick list, its count, retried / scored of fspann_search_retry_dev (api_retry.hip.h)
+    fspann::DevBuf ws_fallback;      // fallback list, its count, member / fellback flags of fspann_search_fallback_dev (api_eval.hip.h)
     struct LdsCeiling { const void* kernel; size_t bytes; };
     static constexpr int kLdsCeilings = 64;
     LdsCeiling lds_ceilings[kLdsCeilings] = {};   // kernels whose dynamic-LDS ceiling this context has raised on its device, and to what (raise_lds_ceiling)

@@ -213,6 +213,7 @@ class FspannContext:
         self.W = (self.bits + 63) // 64
         self.hard_cap = max(cfg.max_global_candidates, cfg.refinement_limit)
         self.device = device
+        self._store_n = 0            # rows of the resident store (store_set / store_attach_dev; a clone takes its parent's)
 
     # -- lifecycle -----------------------------------------------------------
     def clone(self) -> "FspannContext":
@@ -224,6 +225,11 @@ class FspannContext:
         N.check(self.L.fspann_ctx_clone(self._h, C.byref(h)))
         other._h = h
         other.TD, other.bits, other.W, other.hard_cap, other.device = self.TD, self.bits, self.W, self.hard_cap, self.device
+        # the clone reads this context's store in place: what this object knows about it goes along (the library refuses to change
+        # a store while clones are alive, so the two cannot drift)
+        other._store_n = self._store_n
+        if hasattr(self, "store_dtype"):
+            other.store_dtype = self.store_dtype
         return other
 
     def close(self):
@@ -566,10 +572,12 @@ class FspannContext:
         v = v.reshape(-1, self.cfg.dim)
         N.check(self.L.fspann_store_set(self._h, v.shape[0], _p(v), code))
         self.store_dtype = kept
+        self._store_n = v.shape[0]
 
     def store_attach_dev(self, n, ptr, dtype):
         """Use caller-owned device rows [n][dim] as the store (no copy; keep them alive).  dtype: N.F32, N.F64, N.U8, N.F16, N.BF16, N.F8E4M3 or N.I8."""
         N.check(self.L.fspann_store_attach_dev(self._h, int(n), ptr, dtype))
+        self._store_n = int(n)
 
     def hbm_read_peak(self, nbytes=1 << 32, reps=5) -> float:
         """GB/s of a pure-load kernel over `nbytes` of HBM on this device (bench.py roofline.peak_measured)."""
@@ -634,6 +642,35 @@ class FspannContext:
                                                       bad_ptr or None, retried_ptr or None, C.byref(done)))
         return int(done.value)
 
+    def search_fallback_dev(self, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr=0,
+                            sel_ids_ptr=0, sel_count_ptr=0, bad_ptr=0, retried_ptr=0, fellback_ptr=0):
+        """search_retry_dev plus ForwardSecureANNSystem.runQueries' empty-result fallback (FSA:667-678): the queries that returned
+        nothing are searched again on the device, a whole QSI.search at max(2 * base probes, 4) probes, in stream order and in
+        place; fellback [nq] (optional) says which were."""
+        N.check(self.L.fspann_search_fallback_dev(self._h, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr,
+                                                  out_count_ptr, scored_ptr or None, sel_ids_ptr or None, sel_count_ptr or None,
+                                                  bad_ptr or None, retried_ptr or None, fellback_ptr or None))
+
+    def search_fallback_finish_dev(self, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr=0,
+                                   sel_ids_ptr=0, sel_count_ptr=0, bad_ptr=0, retried_ptr=0, fellback_ptr=0) -> int:
+        """Completes the preceding search_fallback_dev call (same arguments): queries Route flagged in either search are finished on
+        the host and scored, those of search 1 take their fallback when empty.  Returns how many were finished on the host."""
+        done = C.c_int64(0)
+        N.check(self.L.fspann_search_fallback_finish_dev(self._h, nq, q_ptr, q_dtype, probe_override, B, k, out_ids_ptr, out_dist_ptr,
+                                                         out_count_ptr, scored_ptr or None, sel_ids_ptr or None, sel_count_ptr or None,
+                                                         bad_ptr or None, retried_ptr or None, fellback_ptr or None, C.byref(done)))
+        return int(done.value)
+
+    def eval_kvariants_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, ks, ann_ptr, ann_stride, ann_count_ptr, gt_ptr, gt_stride,
+                           unique_ptr, recall_ptr, ratio_ptr, cand_ratio_ptr=0):
+        """eval_metrics_typed_dev for every k of ks (a host sequence, at most 64) in one launch: recall / ratio [nk][nq], row j what
+        that call writes for k = ks[j], and cand_ratio [nk][nq] = unique / k (NaN where unique <= 0) when unique_ptr is given."""
+        kk = [int(x) for x in ks]
+        arr = (C.c_int32 * max(1, len(kk)))(*kk)
+        N.check(self.L.fspann_eval_kvariants_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, arr, len(kk), ann_ptr, ann_stride,
+                                                 ann_count_ptr or None, gt_ptr, gt_stride, unique_ptr or None, recall_ptr, ratio_ptr,
+                                                 cand_ratio_ptr or None))
+
     def groundtruth_dev(self, n, base_ptr, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr=0):
         """Exact k-NN (GroundtruthPrecompute semantics) of device-resident fp32 base / query rows."""
         N.check(self.L.fspann_groundtruth_dev(self._h, n, base_ptr, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr or None))
@@ -678,6 +715,110 @@ class FspannContext:
         b, code, _ = _typed_rows(base, dtype, "groundtruth_rows")
         return self._groundtruth_host(b, _c(q, np.float32), k,
                                       lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_rows_dev(n, bd, code, nq, qd, dim, k, idd, d2d))
+
+    class _Dev:
+        """device buffers of a numpy-level call: up(array) / new(shape, dtype) -> pointer, down(pointer) -> array; freed on exit"""
+
+        def __init__(self, ctx):
+            self.ctx, self.bufs = ctx, []
+
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *a):
+            for p, _, _ in self.bufs:
+                self.ctx.L.fspann_dev_free(self.ctx._h, p)
+
+        def new(self, shape, dtype):
+            p = C.c_void_p()
+            N.check(self.ctx.L.fspann_dev_alloc(self.ctx._h, int(np.prod(shape)) * np.dtype(dtype).itemsize, C.byref(p)))
+            self.bufs.append((p, tuple(np.atleast_1d(shape)), np.dtype(dtype)))
+            return p
+
+        def up(self, a):
+            p = self.new(a.shape, a.dtype)
+            if a.nbytes:
+                N.check(self.ctx.L.fspann_h2d(self.ctx._h, p, _p(a), a.nbytes))
+            return p
+
+        def down(self, p):
+            shape, dtype = next((sh, dt) for q, sh, dt in self.bufs if q is p)
+            out = np.empty(shape, dtype)
+            if out.nbytes:
+                N.check(self.ctx.L.fspann_d2h(self.ctx._h, _p(out), p, out.nbytes))
+            return out
+
+    def eval_kvariants(self, base, q, ks, ann, ann_count, gt, unique=None, dtype=None):
+        """recall@k, distance ratio@k and candidate ratio@k for every k of ks (ForwardSecureANNSystem.computeMetricsAtK over prefixes
+        of one result list, FSA:684-692) of host arrays.  base [n][dim] and dtype= are what groundtruth_rows takes; q [nq][dim] goes
+        as fp32, or as bytes when it has the byte type of the rows.  ann [nq][stride] result ids with ann_count per query (None: all),
+        gt [nq][>= max(ks)] ground-truth ids, unique [nq] = |F_q| of each query's last pass (None: no candidate ratio).
+        Returns dict(recall, ratio, cand_ratio) of float64 [nk][nq] (cand_ratio None without unique)."""
+        if dtype is None and getattr(base, "dtype", None) in (np.uint8, np.int8, np.float16):
+            dtype = base.dtype
+        b, code, _ = _typed_rows(base, dtype, "eval_kvariants")
+        qq = np.ascontiguousarray(q)
+        if not (qq.dtype == b.dtype and code in (N.U8, N.I8)):
+            qq = _c(q, np.float32)
+        if b.ndim != 2 or qq.ndim != 2 or b.shape[1] != qq.shape[1]:
+            raise N.FspannArgumentError("base [n][dim] and q [nq][dim] must share dim")
+        a, g = _c(ann, np.int32), _c(gt, np.int32)
+        (n, dim), nq, nk = b.shape, qq.shape[0], len(ks)
+        if a.ndim != 2 or g.ndim != 2 or a.shape[0] != nq or g.shape[0] != nq:
+            raise N.FspannArgumentError("ann [nq][stride] and gt [nq][>= max(ks)] must have one row per query")
+        with self._Dev(self) as dv:
+            bd, qd, ad, gd = dv.up(b), dv.up(qq), dv.up(a), dv.up(g)
+            cd = dv.up(_c(ann_count, np.int32).reshape(nq)) if ann_count is not None else 0
+            ud = dv.up(_c(unique, np.int32).reshape(nq)) if unique is not None else 0
+            rec, rat = dv.new((nk, nq), np.float64), dv.new((nk, nq), np.float64)
+            cr = dv.new((nk, nq), np.float64) if unique is not None else 0
+            self.eval_kvariants_dev(n, bd, code, nq, qd, _row_dt(qq), dim, ks, ad, a.shape[1], cd, gd, g.shape[1], ud, rec, rat, cr)
+            return dict(recall=dv.down(rec), ratio=dv.down(rat), cand_ratio=dv.down(cr) if cr else None)
+
+    def run_queries(self, q, k_variants, gt_ids=None, probe_override=-1, B=None):
+        """ForwardSecureANNSystem.runQueries (FSA:622-748) for a batch over the resident store: one search at K = max(k_variants) with
+        its adaptive retry and the empty-result fallback (search_fallback_dev + its finish call), the ground truth over the store
+        (groundtruth_store_dev) unless gt_ids [nq][>= K] is given, and recall / ratio / candidate ratio at every k of k_variants
+        from that one result list (eval_kvariants_dev with unique = sel_count).  q [nq][dim] goes as fp32.  B: candidates per query
+        (cfg.refinement_limit).  An FSPANN_F64 store is refused: the reference's ground truth reads floats.
+        Returns dict(ids, dist, count, scored, sel_count, bad, retried, fellback, resolved, gt_ids, recall, ratio, cand_ratio), the
+        last three float64 [nk][nq]."""
+        code = C.c_int(0)
+        store = self.L.fspann_store_dev_ptr(self._h, C.byref(code))
+        if not store:
+            raise N.FspannStateError("plaintext store not set")
+        if code.value == N.F64:
+            raise N.FspannArgumentError("run_queries over an FSPANN_F64 store: the reference's ground truth reads floats")
+        ks = [int(x) for x in k_variants]
+        if not ks:
+            raise N.FspannArgumentError("k_variants is empty")
+        K, nk = max(ks), len(ks)
+        B = int(self.cfg.refinement_limit if B is None else B)
+        qq = _c(q, np.float32).reshape(-1, self.cfg.dim)
+        nq = qq.shape[0]
+        g = None
+        if gt_ids is not None:
+            g = _c(gt_ids, np.int32)
+            if g.ndim != 2 or g.shape[0] != nq or g.shape[1] < K:
+                raise N.FspannArgumentError("gt_ids must be [nq][>= max(k_variants)]")
+        with self._Dev(self) as dv:
+            qd = dv.up(qq)
+            ids, dist = dv.new((nq, K), np.int32), dv.new((nq, K), np.float64)
+            cnt, sc, selc, bad, ret, fb = (dv.new((nq,), np.int32) for _ in range(6))
+            sel = dv.new((nq, B), np.int32)
+            args = (nq, qd, N.F32, probe_override, B, K, ids, dist, cnt, sc, sel, selc, bad, ret, fb)
+            self.search_fallback_dev(*args)
+            resolved = self.search_fallback_finish_dev(*args)
+            if g is None:
+                gd, gs = dv.new((nq, K), np.int32), K
+                self.groundtruth_store_dev(nq, qd, K, gd)
+            else:
+                gd, gs = dv.up(g), g.shape[1]
+            rec, rat, cr = (dv.new((nk, nq), np.float64) for _ in range(3))
+            self.eval_kvariants_dev(self._store_n, store, code.value, nq, qd, N.F32, self.cfg.dim, ks, ids, K, cnt, gd, gs, selc, rec, rat, cr)
+            return dict(ids=dv.down(ids), dist=dv.down(dist), count=dv.down(cnt), scored=dv.down(sc), sel_count=dv.down(selc), bad=dv.down(bad),
+                        retried=dv.down(ret), fellback=dv.down(fb), resolved=resolved, gt_ids=dv.down(gd), recall=dv.down(rec), ratio=dv.down(rat),
+                        cand_ratio=dv.down(cr))
 
     def _groundtruth_host(self, b, qq, k, run):
         """base b and queries qq (host arrays as they go to the device) -> ids, d2 of the device call `run`"""

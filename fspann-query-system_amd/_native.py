@@ -1,4 +1,5 @@
-"""ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h).
+"""ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
+include/fspann_gt_validate.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -86,7 +87,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -216,6 +217,23 @@ _SIGS_EVAL = {
 }
 
 
+class GtValidation(C.Structure):
+    """fspann_gt_validation of include/fspann_gt_validate.h"""
+    _fields_ = [("valid", C.c_int32), ("consistent", C.c_int32), ("sample_size", C.c_int64), ("mismatches", C.c_int64),
+                ("mismatch_rate", C.c_double), ("n_mismatched", C.c_int32), ("gt_min_id", C.c_int32), ("gt_max_id", C.c_int32),
+                ("reserved", C.c_int32), ("mismatched", C.c_int64 * 10)]
+
+
+# include/fspann_gt_validate.h: GroundtruthValidator's sample, exact top-1 and validate (a fourth table: the three above stay as they are)
+_SIGS_VALIDATE = {
+    "fspann_gt_validator_sample": (_i, [_i64, _i64, _vp, C.POINTER(_i64)]),
+    "fspann_nn1_exact_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp]),
+    "fspann_nn1_exact_store_dev": (_i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp]),
+    "fspann_gt_validate_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _vp, _i64, _i64, _i64, C.c_double, C.POINTER(GtValidation)]),
+    "fspann_gt_validate_store_dev": (_i, [_vp, _i64, _vp, _i, _vp, _i64, _i64, _i64, C.c_double, C.POINTER(GtValidation)]),
+}
+
+
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
     global _LIB
@@ -225,7 +243,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -252,3 +270,8 @@ def rows_symbols():
 def eval_symbols():
     """the entry points of include/fspann_eval.h"""
     return sorted(_SIGS_EVAL)
+
+
+def validate_symbols():
+    """the entry points of include/fspann_gt_validate.h"""
+    return sorted(_SIGS_VALIDATE)

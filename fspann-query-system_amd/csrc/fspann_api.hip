@@ -17,6 +17,7 @@
 #include "groundtruth.hip.h"
 #include "eval_sweep.hip.h"
 #include "groundtruth_u8.hip.h"
+#include "gt_validate.hip.h"
 #include "hostpipe.hip.h"
 #include "refine.hip.h"
 #include "route.hip.h"
@@ -40,3 +41,4 @@
 #include "api_ext.hip.h"
 #include "api_retry.hip.h"
 #include "api_eval.hip.h"
+#include "api_gt_validate.hip.h"

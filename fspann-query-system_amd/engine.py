@@ -716,6 +716,39 @@ class FspannContext:
         return self._groundtruth_host(b, _c(q, np.float32), k,
                                       lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_rows_dev(n, bd, code, nq, qd, dim, k, idd, d2d))
 
+    def gt_validator_sample(self, nq, sample_size=100) -> np.ndarray:
+        """GroundtruthValidator's sample (java.util.Random(42).nextInt(nq) into a HashSet<Integer> until it holds
+        min(sample_size, nq) values) in the set's iteration order, int64."""
+        out = np.empty(max(0, min(int(sample_size), int(nq))), np.int64)
+        cnt = C.c_int64(0)
+        N.check(self.L.fspann_gt_validator_sample(int(nq), int(sample_size), _p(out) if out.size else None, C.byref(cnt)))
+        return out[:cnt.value]
+
+    def nn1_exact_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, qsel_ptr, nsel, out_idx_ptr, out_d2_ptr=0):
+        """BaseVectorReader.bruteForceNN of device-resident rows (every row dtype but N.F64) for the queries qsel [nsel] (int64
+        device list; 0: the first nsel) of q [nq][dim] (N.F64 or N.F32): the subtraction in DOUBLE, a strict `<` minimum over
+        ascending rows, -1 / +inf when no sum is below +inf.  One fused kernel, no distance matrix; stream order."""
+        N.check(self.L.fspann_nn1_exact_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, qsel_ptr or None, nsel, out_idx_ptr,
+                                            out_d2_ptr or None))
+
+    def nn1_exact_store_dev(self, nq, q_ptr, q_dtype, qsel_ptr, nsel, out_idx_ptr, out_d2_ptr=0):
+        """nn1_exact_dev with the resident store as the base."""
+        N.check(self.L.fspann_nn1_exact_store_dev(self._h, nq, q_ptr, q_dtype, qsel_ptr or None, nsel, out_idx_ptr, out_d2_ptr or None))
+
+    def gt_validate_dev(self, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, gt_ptr, gt_rows, gt_stride, sample_size, tolerance) -> N.GtValidation:
+        """GroundtruthValidator.validate over device buffers (host-synchronous): the fspann_gt_validation it fills."""
+        v = N.GtValidation()
+        N.check(self.L.fspann_gt_validate_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, q_dtype, dim, gt_ptr or None, gt_rows, gt_stride,
+                                              sample_size, tolerance, C.byref(v)))
+        return v
+
+    def gt_validate_store_dev(self, nq, q_ptr, q_dtype, gt_ptr, gt_rows, gt_stride, sample_size, tolerance) -> N.GtValidation:
+        """gt_validate_dev against the resident store."""
+        v = N.GtValidation()
+        N.check(self.L.fspann_gt_validate_store_dev(self._h, nq, q_ptr, q_dtype, gt_ptr or None, gt_rows, gt_stride, sample_size, tolerance,
+                                                    C.byref(v)))
+        return v
+
     class _Dev:
         """device buffers of a numpy-level call: up(array) / new(shape, dtype) -> pointer, down(pointer) -> array; freed on exit"""
 
@@ -775,14 +808,100 @@ class FspannContext:
             self.eval_kvariants_dev(n, bd, code, nq, qd, _row_dt(qq), dim, ks, ad, a.shape[1], cd, gd, g.shape[1], ud, rec, rat, cr)
             return dict(recall=dv.down(rec), ratio=dv.down(rat), cand_ratio=dv.down(cr) if cr else None)
 
-    def run_queries(self, q, k_variants, gt_ids=None, probe_override=-1, B=None):
+    @staticmethod
+    def _validator_queries(q):
+        """queries as the validator calls take them: float64 stays float64 (the reference's double[]), anything else goes as fp32"""
+        qq = np.ascontiguousarray(q)
+        return (qq, N.F64) if qq.dtype == np.float64 else (_c(q, np.float32), N.F32)
+
+    @staticmethod
+    def _validation_dict(v, tolerance):
+        """fspann_gt_validation -> dict, with ValidationResult's message (GroundtruthValidator.java:94-100, 166-182)"""
+        rate = float(v.mismatch_rate)
+        if v.valid and v.sample_size == 0:
+            msg = "No queries to validate"
+        elif not v.valid and v.sample_size == 0:
+            msg = "Groundtruth is empty"
+        elif v.valid:
+            msg = "GT validation PASSED: %.2f%% match rate" % ((1 - rate) * 100)
+        else:
+            msg = ("GT validation FAILED: %.2f%% mismatch rate exceeds %.2f%% tolerance. "
+                   "Groundtruth may be corrupted or computed for a different dataset." % (rate * 100, tolerance * 100))
+        return dict(valid=bool(v.valid), sample_size=int(v.sample_size), mismatches=int(v.mismatches), mismatch_rate=rate, message=msg,
+                    mismatched=[int(x) for x in v.mismatched[:v.n_mismatched]], gt_min_id=int(v.gt_min_id), gt_max_id=int(v.gt_max_id),
+                    consistent=bool(v.consistent), tolerance=float(tolerance))
+
+    @staticmethod
+    def _validator_defaults(sample_size, tolerance):
+        """FSA:2151-2152: a sample size <= 0 becomes 100, a tolerance <= 0 becomes 0.05"""
+        return (int(sample_size) if sample_size > 0 else 100), (float(tolerance) if tolerance > 0 else 0.05)
+
+    def nn1_exact(self, base, q, dtype=None, sel=None):
+        """The validator's exact nearest row (BaseVectorReader.bruteForceNN: the subtraction in double) of host arrays.  base [n][dim]
+        and dtype= are what groundtruth_rows takes; q [nq][dim] goes as float64 if it is float64, otherwise as fp32; sel: the query
+        indices to run, in any order, repeats allowed (None: all).  Returns (idx int32, d2 float64), one entry per selected query:
+        -1 / +inf where no row's sum is below +inf."""
+        if dtype is None and getattr(base, "dtype", None) in (np.uint8, np.int8, np.float16):
+            dtype = base.dtype
+        b, code, _ = _typed_rows(base, dtype, "nn1_exact")
+        qq, qcode = self._validator_queries(q)
+        if b.ndim != 2 or qq.ndim != 2 or b.shape[1] != qq.shape[1]:
+            raise N.FspannArgumentError("base [n][dim] and q [nq][dim] must share dim")
+        (n, dim), nq = b.shape, qq.shape[0]
+        s = None if sel is None else _c(sel, np.int64).reshape(-1)
+        nsel = nq if s is None else s.size
+        with self._Dev(self) as dv:
+            bd, qd = dv.up(b), dv.up(qq)
+            sd = dv.up(s) if s is not None else 0
+            idx, d2 = dv.new((nsel,), np.int32), dv.new((nsel,), np.float64)
+            self.nn1_exact_dev(n, bd, code, nq, qd, qcode, dim, sd, nsel, idx, d2)
+            return dv.down(idx), dv.down(d2)
+
+    def validate_groundtruth(self, base, q, gt_ids, sample_size=100, tolerance=0.05, dtype=None):
+        """GroundtruthValidator.validate (FSA:2144-2193) of host arrays: a deterministic sample of the queries, the exact nearest row
+        of each against gt_ids[qi][0].  base, dtype= and q as nn1_exact takes them; gt_ids [gt_rows][stride] int32 (fewer rows than
+        queries: the queries past them are skipped but stay in the denominator).  sample_size <= 0 becomes 100 and tolerance <= 0
+        becomes 0.05 (FSA:2151-2152).  Returns dict(valid, sample_size, mismatches, mismatch_rate, message, mismatched (the first 10,
+        in the sample's order), gt_min_id, gt_max_id, consistent, ...); nothing is raised for an invalid result."""
+        sample_size, tolerance = self._validator_defaults(sample_size, tolerance)
+        if dtype is None and getattr(base, "dtype", None) in (np.uint8, np.int8, np.float16):
+            dtype = base.dtype
+        b, code, _ = _typed_rows(base, dtype, "validate_groundtruth")
+        qq, qcode = self._validator_queries(q)
+        if b.ndim != 2 or qq.ndim != 2 or b.shape[1] != qq.shape[1]:
+            raise N.FspannArgumentError("base [n][dim] and q [nq][dim] must share dim")
+        g = _c(gt_ids, np.int32)
+        if g.ndim != 2:
+            raise N.FspannArgumentError("gt_ids must be [gt_rows][stride]")
+        with self._Dev(self) as dv:
+            bd, qd, gd = dv.up(b), dv.up(qq), dv.up(g)
+            v = self.gt_validate_dev(b.shape[0], bd, code, qq.shape[0], qd, qcode, b.shape[1], gd, g.shape[0], g.shape[1], sample_size, tolerance)
+        return self._validation_dict(v, tolerance)
+
+    def validate_groundtruth_store(self, q, gt_ids, sample_size=100, tolerance=0.05):
+        """validate_groundtruth against the resident store (store_set or store_attach_dev)."""
+        sample_size, tolerance = self._validator_defaults(sample_size, tolerance)
+        qq, qcode = self._validator_queries(q)
+        qq = qq.reshape(-1, self.cfg.dim)
+        g = _c(gt_ids, np.int32)
+        if g.ndim != 2:
+            raise N.FspannArgumentError("gt_ids must be [gt_rows][stride]")
+        with self._Dev(self) as dv:
+            qd, gd = dv.up(qq), dv.up(g)
+            v = self.gt_validate_store_dev(qq.shape[0], qd, qcode, gd, g.shape[0], g.shape[1], sample_size, tolerance)
+        return self._validation_dict(v, tolerance)
+
+    def run_queries(self, q, k_variants, gt_ids=None, probe_override=-1, B=None, validate=None):
         """ForwardSecureANNSystem.runQueries (FSA:622-748) for a batch over the resident store: one search at K = max(k_variants) with
         its adaptive retry and the empty-result fallback (search_fallback_dev + its finish call), the ground truth over the store
         (groundtruth_store_dev) unless gt_ids [nq][>= K] is given, and recall / ratio / candidate ratio at every k of k_variants
         from that one result list (eval_kvariants_dev with unique = sel_count).  q [nq][dim] goes as fp32.  B: candidates per query
         (cfg.refinement_limit).  An FSPANN_F64 store is refused: the reference's ground truth reads floats.
+        validate=(sample_size, tolerance) with gt_ids given: GroundtruthValidator.validate over the store runs first (FSA:2144-2193);
+        an invalid result raises FspannStateError with its message (IllegalStateException, FSA:2185), a valid one is returned as
+        gt_validation.  validate=None (the default): no validation, the same launches and the same keys as before.
         Returns dict(ids, dist, count, scored, sel_count, bad, retried, fellback, resolved, gt_ids, recall, ratio, cand_ratio), the
-        last three float64 [nk][nq]."""
+        last three float64 [nk][nq].  (plus gt_validation when it ran)"""
         code = C.c_int(0)
         store = self.L.fspann_store_dev_ptr(self._h, C.byref(code))
         if not store:
@@ -801,6 +920,11 @@ class FspannContext:
             g = _c(gt_ids, np.int32)
             if g.ndim != 2 or g.shape[0] != nq or g.shape[1] < K:
                 raise N.FspannArgumentError("gt_ids must be [nq][>= max(k_variants)]")
+        validation = None
+        if validate is not None and g is not None:
+            validation = self.validate_groundtruth_store(qq, g, *validate)
+            if not validation["valid"]:
+                raise N.FspannStateError(validation["message"])
         with self._Dev(self) as dv:
             qd = dv.up(qq)
             ids, dist = dv.new((nq, K), np.int32), dv.new((nq, K), np.float64)
@@ -816,9 +940,12 @@ class FspannContext:
                 gd, gs = dv.up(g), g.shape[1]
             rec, rat, cr = (dv.new((nk, nq), np.float64) for _ in range(3))
             self.eval_kvariants_dev(self._store_n, store, code.value, nq, qd, N.F32, self.cfg.dim, ks, ids, K, cnt, gd, gs, selc, rec, rat, cr)
-            return dict(ids=dv.down(ids), dist=dv.down(dist), count=dv.down(cnt), scored=dv.down(sc), sel_count=dv.down(selc), bad=dv.down(bad),
-                        retried=dv.down(ret), fellback=dv.down(fb), resolved=resolved, gt_ids=dv.down(gd), recall=dv.down(rec), ratio=dv.down(rat),
-                        cand_ratio=dv.down(cr))
+            out = dict(ids=dv.down(ids), dist=dv.down(dist), count=dv.down(cnt), scored=dv.down(sc), sel_count=dv.down(selc), bad=dv.down(bad),
+                       retried=dv.down(ret), fellback=dv.down(fb), resolved=resolved, gt_ids=dv.down(gd), recall=dv.down(rec), ratio=dv.down(rat),
+                       cand_ratio=dv.down(cr))
+            if validation is not None:
+                out["gt_validation"] = validation
+            return out
 
     def _groundtruth_host(self, b, qq, k, run):
         """base b and queries qq (host arrays as they go to the device) -> ids, d2 of the device call `run`"""

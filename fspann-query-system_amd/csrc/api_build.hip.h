@@ -54,7 +54,7 @@ int build_append_impl(fspann_ctx* c, int64_t nrows, const void* rows, int dtype)
             using T = typename decltype(tr)::type;
             if constexpr (!DtypeOf<T>::query) {
                 const int64_t ne = cn * d;
-                hipLaunchKernelGGL(build_widen_kernel(static_cast<const T*>(nullptr)), dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
+                hipLaunchKernelGGL(build_widen_kernel<T>, dim3(static_cast<unsigned>((ne + 4 * 256 - 1) / (4 * 256))), dim3(256), 0, c->stream,
                                    static_cast<const T*>(c->ws_io[0].p), ne, static_cast<float*>(c->ws_io[1].p));
             }
         });

@@ -3,6 +3,33 @@
 #pragma once
 #include "../../include/fspann_groundtruth_rows.h"     // the two ground-truth calls over typed rows (not part of fspann.h's counted set)
 
+namespace {
+// The ground truth of fp32 queries over rows of type TB (arguments checked by the caller): gt_dist_kernel fills a [chunk x n] fp64
+// distance matrix in scratch, at most the context's budget at a time (FSPANN_GT_SCRATCH_MB, 8 GiB) and a grid whose y dimension
+// stays within 65535 query tiles, and gt_select_kernel picks every query's k.
+template <typename TB>
+int gt_rows_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const float* q, int dim, int k, int32_t* out_ids, double* out_d2) {
+    int64_t chunk = std::max<int64_t>(kGtQT, std::min<int64_t>(nq, (c->gt_scratch_bytes / (n * 8)) / kGtQT * kGtQT));
+    chunk = std::min<int64_t>(chunk, int64_t(65535) * kGtQT);
+    int rc = ensure(c, c->ws_gt, static_cast<size_t>(chunk) * n * 8);
+    if (rc) return rc;
+    double* dist = static_cast<double*>(c->ws_gt.p);
+    // a lane reads its typed row 16 bytes at a time when every row starts on a 16-byte boundary and ends on one; fp32 rows: element loads
+    auto dist_kernel = gt_dist_kernel<TB, false>;
+    if constexpr (!std::is_same<TB, float>::value)
+        if ((static_cast<int64_t>(dim) * static_cast<int64_t>(sizeof(TB))) % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0) dist_kernel = gt_dist_kernel<TB, true>;
+    for (int64_t s = 0; s < nq; s += chunk) {
+        const int64_t cq = std::min(chunk, nq - s);
+        dim3 grid(static_cast<unsigned>((n + kGtRows - 1) / kGtRows), static_cast<unsigned>((cq + kGtQT - 1) / kGtQT));
+        hipLaunchKernelGGL(dist_kernel, grid, dim3(kGtRows), 0, c->stream, base, n, q + s * dim, cq, dim, dist);
+        FSP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(gt_select_kernel, dim3(static_cast<unsigned>(cq)), dim3(kGtSelThreads), 0, c->stream, dist, n, k, out_ids + s * k,
+                           out_d2 ? out_d2 + s * k : nullptr);
+        FSP_HIP(hipGetLastError());
+    }
+    return FSPANN_OK;
+}
+}  // namespace
 extern "C" {
 
 // ---- exact ground truth + evaluation metrics (groundtruth.hip.h) -------------------------------------------------------------
@@ -13,21 +40,7 @@ int fspann_groundtruth_dev(fspann_ctx* c, int64_t n, const float* base_dev, int6
     if (n <= 0 || n >= (1LL << 31) || nq < 0 || dim <= 0) return fail(FSPANN_E_ARG, "Empty or malformed vector files (zero records).");
     if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
-    // the [chunk x n] fp64 distance matrix lives in scratch: at most the context's budget at a time (FSPANN_GT_SCRATCH_MB, 8 GiB)
-    const int64_t chunk = std::max<int64_t>(kGtQT, std::min<int64_t>(nq, (c->gt_scratch_bytes / (n * 8)) / kGtQT * kGtQT));
-    int rc = ensure(c, c->ws_gt, static_cast<size_t>(chunk) * n * 8);
-    if (rc) return rc;
-    double* dist = static_cast<double*>(c->ws_gt.p);
-    for (int64_t s = 0; s < nq; s += chunk) {
-        const int64_t cq = std::min(chunk, nq - s);
-        dim3 grid(static_cast<unsigned>((n + kGtRows - 1) / kGtRows), static_cast<unsigned>((cq + kGtQT - 1) / kGtQT));
-        hipLaunchKernelGGL(gt_dist_kernel, grid, dim3(kGtRows), 0, c->stream, base_dev, n, q_dev + s * dim, cq, dim, dist);
-        FSP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(gt_select_kernel, dim3(static_cast<unsigned>(cq)), dim3(kGtSelThreads), 0, c->stream, dist, n, k, out_ids_dev + s * k,
-                           out_d2_dev ? out_d2_dev + s * k : nullptr);
-        FSP_HIP(hipGetLastError());
-    }
-    return FSPANN_OK;
+    return gt_rows_run(c, n, base_dev, nq, q_dev, dim, k, out_ids_dev, out_d2_dev);
 }
 
 // (Every check stands before the `nq == 0` return, and nq == 0 launches nothing: fspann_eval_kvariants_dev, api_eval.hip.h, runs
@@ -39,7 +52,7 @@ int fspann_eval_metrics_dev(fspann_ctx* c, int64_t n, const float* base_dev, int
     if (!base_dev || !q_dev || !ann_ids_dev || !gt_ids_dev || !recall_dev || !ratio_dev) return fail(FSPANN_E_NULL, "metrics buffer is null");
     if (n <= 0 || nq < 0 || dim <= 0 || k <= 0 || k > kGtMaxK || gt_stride < k || ann_stride <= 0) return fail(FSPANN_E_ARG, "k must be in [1, %d] and gt must hold >= k ids per query", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
-    hipLaunchKernelGGL(gt_metrics_kernel, dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base_dev, n, q_dev, dim, k, ann_ids_dev, ann_stride,
+    hipLaunchKernelGGL((gt_metrics_kernel<float, float>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, base_dev, n, q_dev, dim, k, ann_ids_dev, ann_stride,
                        ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
@@ -51,6 +64,45 @@ int gt8_digits(uint64_t v) {      // 8-bit digits that hold v
     int nd = 1;
     while (nd < 4 && (v >> (8 * nd)) != 0) nd++;
     return nd;
+}
+
+// The ground truth of byte queries over byte rows of the same type TB (uint8_t or int8_t; arguments checked by the caller):
+// integer distances on the int8 matrix cores (groundtruth_u8.hip.h).
+template <typename TB>
+int gt8_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const TB* q, int dim, int k, int32_t* out_ids, double* out_d2) {
+    // scratch: |x'|^2 [n], |q'|^2 [chunk], then the [chunk x ld] uint32 distances, every part 256-byte aligned, rows 16-byte aligned
+    const int64_t ld = (n + 3) & ~int64_t(3);
+    const int64_t nbt = (n + kGt8Rows - 1) / kGt8Rows;
+    int64_t chunk = std::max<int64_t>(32, std::min<int64_t>((nq + 31) / 32 * 32, (c->gt_scratch_bytes / (ld * 4)) / 32 * 32));
+    chunk = std::min<int64_t>(chunk, std::max<int64_t>(kGt8Q, ((int64_t(1) << 31) - 1) / nbt / 2 * kGt8Q));      // the distance grid stays below 2^31 workgroups
+    const size_t xn_bytes = (static_cast<size_t>(n) * 4 + 255) & ~size_t(255);
+    const size_t qn_bytes = (static_cast<size_t>(chunk) * 4 + 255) & ~size_t(255);
+    int rc = ensure(c, c->ws_gt, xn_bytes + qn_bytes + static_cast<size_t>(chunk) * ld * 4);
+    if (rc) return rc;
+    unsigned* xn = static_cast<unsigned*>(c->ws_gt.p);
+    unsigned* qn = reinterpret_cast<unsigned*>(static_cast<char*>(c->ws_gt.p) + xn_bytes);
+    unsigned* dist = reinterpret_cast<unsigned*>(static_cast<char*>(c->ws_gt.p) + xn_bytes + qn_bytes);
+    // rows that start at odd addresses (dim % 16, or a matrix off a 16-byte boundary) take the byte-load instantiation
+    const bool aligned = (dim % 16 == 0) && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(q)) & 15) == 0;
+    const int ndd = gt8_digits(static_cast<uint64_t>(dim) * 255 * 255), ndi = gt8_digits(static_cast<uint64_t>(n - 1));
+    auto xnorm_kernel = aligned ? gt8_norm_kernel<TB, true> : gt8_norm_kernel<TB, false>;
+    hipLaunchKernelGGL(xnorm_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, c->stream, base, n, dim, xn);
+    FSP_HIP(hipGetLastError());
+    for (int64_t s = 0; s < nq; s += chunk) {
+        const int64_t cq = std::min(chunk, nq - s);
+        const TB* qs = q + s * dim;
+        const bool qal = aligned && (reinterpret_cast<uintptr_t>(qs) & 15) == 0;      // (dim % 16 == 0: every chunk starts aligned)
+        const int nqb = static_cast<int>((cq + kGt8Q - 1) / kGt8Q);
+        auto qnorm_kernel = qal ? gt8_norm_kernel<TB, true> : gt8_norm_kernel<TB, false>;
+        auto dist_kernel = qal ? gt8_dist_kernel<TB, true> : gt8_dist_kernel<TB, false>;
+        hipLaunchKernelGGL(qnorm_kernel, dim3(static_cast<unsigned>((cq + 255) / 256)), dim3(256), 0, c->stream, qs, cq, dim, qn);
+        hipLaunchKernelGGL(dist_kernel, dim3(static_cast<unsigned>(nbt * nqb)), dim3(256), 0, c->stream, base, n, qs, cq, dim, xn, qn, dist, ld, nqb);
+        FSP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(gt8_select_kernel, dim3(static_cast<unsigned>(cq)), dim3(kGt8SelThreads), 0, c->stream, dist, ld, n, k, ndd, ndi, out_ids + s * k,
+                           out_d2 ? out_d2 + s * k : nullptr);
+        FSP_HIP(hipGetLastError());
+    }
+    return FSPANN_OK;
 }
 }  // namespace
 extern "C" {
@@ -73,57 +125,12 @@ int fspann_groundtruth_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev,
     if (dim > kGt8MaxDim) return fail(FSPANN_E_ARG, "dim %d > %d: %s distances would not fit 32 bits", dim, kGt8MaxDim, dtype_name(base_dtype));
     if (k <= 0 || k > kGtMaxK) return fail(FSPANN_E_ARG, "k must be in [1, %d]", kGtMaxK);
     if (nq == 0) return FSPANN_OK;
-    const bool sgn = base_dtype == FSPANN_I8;     // signed bytes: the gt8s_* kernels (no flip); everything else is shared
-    const uint8_t* base = static_cast<const uint8_t*>(base_dev);
-    const uint8_t* q = static_cast<const uint8_t*>(q_dev);
-    const int8_t* sbase = static_cast<const int8_t*>(base_dev);
-    // scratch: |x'|^2 [n], |q'|^2 [chunk], then the [chunk x ld] uint32 distances, every part 256-byte aligned, rows 16-byte aligned
-    const int64_t ld = (n + 3) & ~int64_t(3);
-    const int64_t nbt = (n + kGt8Rows - 1) / kGt8Rows;
-    int64_t chunk = std::max<int64_t>(32, std::min<int64_t>((nq + 31) / 32 * 32, (c->gt_scratch_bytes / (ld * 4)) / 32 * 32));
-    chunk = std::min<int64_t>(chunk, std::max<int64_t>(kGt8Q, ((int64_t(1) << 31) - 1) / nbt / 2 * kGt8Q));      // the distance grid stays below 2^31 workgroups
-    const size_t xn_bytes = (static_cast<size_t>(n) * 4 + 255) & ~size_t(255);
-    const size_t qn_bytes = (static_cast<size_t>(chunk) * 4 + 255) & ~size_t(255);
-    int rc = ensure(c, c->ws_gt, xn_bytes + qn_bytes + static_cast<size_t>(chunk) * ld * 4);
-    if (rc) return rc;
-    unsigned* xn = static_cast<unsigned*>(c->ws_gt.p);
-    unsigned* qn = reinterpret_cast<unsigned*>(static_cast<char*>(c->ws_gt.p) + xn_bytes);
-    unsigned* dist = reinterpret_cast<unsigned*>(static_cast<char*>(c->ws_gt.p) + xn_bytes + qn_bytes);
-    // rows that start at odd addresses (dim % 16, or a matrix off a 16-byte boundary) take the byte-load instantiation
-    const bool aligned = (dim % 16 == 0) && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(q)) & 15) == 0;
-    const int ndd = gt8_digits(static_cast<uint64_t>(dim) * 255 * 255), ndi = gt8_digits(static_cast<uint64_t>(n - 1));
-    const dim3 ngrid(static_cast<unsigned>((n + 255) / 256));
-    if (sgn && aligned) hipLaunchKernelGGL(gt8s_norm_kernel<true>, ngrid, dim3(256), 0, c->stream, sbase, n, dim, xn);
-    else if (sgn) hipLaunchKernelGGL(gt8s_norm_kernel<false>, ngrid, dim3(256), 0, c->stream, sbase, n, dim, xn);
-    else if (aligned) hipLaunchKernelGGL(gt8_norm_kernel<true>, ngrid, dim3(256), 0, c->stream, base, n, dim, xn);
-    else hipLaunchKernelGGL(gt8_norm_kernel<false>, ngrid, dim3(256), 0, c->stream, base, n, dim, xn);
-    FSP_HIP(hipGetLastError());
-    for (int64_t s = 0; s < nq; s += chunk) {
-        const int64_t cq = std::min(chunk, nq - s);
-        const uint8_t* qs = q + s * dim;
-        const bool qal = aligned && (reinterpret_cast<uintptr_t>(qs) & 15) == 0;      // (dim % 16 == 0: every chunk starts aligned)
-        const int nqb = static_cast<int>((cq + kGt8Q - 1) / kGt8Q);
-        const dim3 qgrid(static_cast<unsigned>((cq + 255) / 256)), dgrid(static_cast<unsigned>(nbt * nqb));
-        const int8_t* sqs = reinterpret_cast<const int8_t*>(qs);
-        if (sgn && qal) {
-            hipLaunchKernelGGL(gt8s_norm_kernel<true>, qgrid, dim3(256), 0, c->stream, sqs, cq, dim, qn);
-            hipLaunchKernelGGL(gt8s_dist_kernel<true>, dgrid, dim3(256), 0, c->stream, sbase, n, sqs, cq, dim, xn, qn, dist, ld, nqb);
-        } else if (sgn) {
-            hipLaunchKernelGGL(gt8s_norm_kernel<false>, qgrid, dim3(256), 0, c->stream, sqs, cq, dim, qn);
-            hipLaunchKernelGGL(gt8s_dist_kernel<false>, dgrid, dim3(256), 0, c->stream, sbase, n, sqs, cq, dim, xn, qn, dist, ld, nqb);
-        } else if (qal) {
-            hipLaunchKernelGGL(gt8_norm_kernel<true>, qgrid, dim3(256), 0, c->stream, qs, cq, dim, qn);
-            hipLaunchKernelGGL(gt8_dist_kernel<true>, dgrid, dim3(256), 0, c->stream, base, n, qs, cq, dim, xn, qn, dist, ld, nqb);
-        } else {
-            hipLaunchKernelGGL(gt8_norm_kernel<false>, qgrid, dim3(256), 0, c->stream, qs, cq, dim, qn);
-            hipLaunchKernelGGL(gt8_dist_kernel<false>, dgrid, dim3(256), 0, c->stream, base, n, qs, cq, dim, xn, qn, dist, ld, nqb);
-        }
-        FSP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(gt8_select_kernel, dim3(static_cast<unsigned>(cq)), dim3(kGt8SelThreads), 0, c->stream, dist, ld, n, k, ndd, ndi,
-                           out_ids_dev + s * k, out_d2_dev ? out_d2_dev + s * k : nullptr);
-        FSP_HIP(hipGetLastError());
-    }
-    return FSPANN_OK;
+    int rc = FSPANN_OK;
+    with_row_type(base_dtype, [&](auto tb) {
+        using TB = typename decltype(tb)::type;
+        if constexpr (DtypeOf<TB>::finite) rc = gt8_run(c, n, static_cast<const TB*>(base_dev), nq, static_cast<const TB*>(q_dev), dim, k, out_ids_dev, out_d2_dev);
+    });
+    return rc;
 }
 
 // This function is also the argument check of fspann_eval_kvariants_dev (api_eval.hip.h), which calls it with nq = 0 and relies on
@@ -161,7 +168,7 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
         using TB = typename decltype(tb)::type;
         auto go = [&](auto tq) {
             using TQ = typename decltype(tq)::type;
-            hipLaunchKernelGGL((gt_metrics_typed_kernel<TB, TQ>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const TB*>(base_dev), n,
+            hipLaunchKernelGGL((gt_metrics_kernel<TB, TQ>), dim3(static_cast<unsigned>(nq)), dim3(64), 0, c->stream, static_cast<const TB*>(base_dev), n,
                                static_cast<const TQ*>(q_dev), dim, k, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, recall_dev, ratio_dev);
         };
         if constexpr (DtypeOf<TB>::finite) { if (same_bytes) go(tb); else go(DtypeTag<float>{}); }
@@ -170,34 +177,6 @@ int fspann_eval_metrics_typed_dev(fspann_ctx* c, int64_t n, const void* base_dev
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
 }
-
-}  // extern "C"
-namespace {
-// fspann_groundtruth_dev's loop with gt_rows_dist_kernel<TB, .> in the place of gt_dist_kernel (arguments checked by the caller)
-template <typename TB>
-int gt_rows_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const float* q, int dim, int k, int32_t* out_ids, double* out_d2) {
-    // the same [chunk x n] fp64 matrix in the same scratch, and a grid whose y dimension stays within 65535 query tiles
-    int64_t chunk = std::max<int64_t>(kGtQT, std::min<int64_t>(nq, (c->gt_scratch_bytes / (n * 8)) / kGtQT * kGtQT));
-    chunk = std::min<int64_t>(chunk, int64_t(65535) * kGtQT);
-    int rc = ensure(c, c->ws_gt, static_cast<size_t>(chunk) * n * 8);
-    if (rc) return rc;
-    double* dist = static_cast<double*>(c->ws_gt.p);
-    // a lane reads its row 16 bytes at a time when every row starts on a 16-byte boundary and ends on one
-    const bool vec = (static_cast<int64_t>(dim) * static_cast<int64_t>(sizeof(TB))) % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
-    for (int64_t s = 0; s < nq; s += chunk) {
-        const int64_t cq = std::min(chunk, nq - s);
-        dim3 grid(static_cast<unsigned>((n + kGtRows - 1) / kGtRows), static_cast<unsigned>((cq + kGtQT - 1) / kGtQT));
-        if (vec) hipLaunchKernelGGL((gt_rows_dist_kernel<TB, true>), grid, dim3(kGtRows), 0, c->stream, base, n, q + s * dim, cq, dim, dist);
-        else hipLaunchKernelGGL((gt_rows_dist_kernel<TB, false>), grid, dim3(kGtRows), 0, c->stream, base, n, q + s * dim, cq, dim, dist);
-        FSP_HIP(hipGetLastError());
-        hipLaunchKernelGGL(gt_select_kernel, dim3(static_cast<unsigned>(cq)), dim3(kGtSelThreads), 0, c->stream, dist, n, k, out_ids + s * k,
-                           out_d2 ? out_d2 + s * k : nullptr);
-        FSP_HIP(hipGetLastError());
-    }
-    return FSPANN_OK;
-}
-}  // namespace
-extern "C" {
 
 // Ground truth of fp32 queries over typed rows: the element widened exactly, then fspann_groundtruth_dev's arithmetic and select.
 int fspann_groundtruth_rows_dev(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const float* q_dev, int dim, int k,

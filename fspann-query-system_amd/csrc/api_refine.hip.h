@@ -113,10 +113,8 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
                     else hipLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
                     return FSPANN_OK;
                 };
-                // fp32 rows have the kernel of their own; every narrower row type the one with the row type as a template parameter
-                if constexpr (std::is_same<TC, float>::value) { auto fk = refine_stream_fix_kernel<GATHER>; lrc = hand_over(fk); }
-                else { auto fk = refine_stream_fix_kernel<TC, GATHER>; lrc = hand_over(fk); }
-                if (lrc) return lrc;
+                auto fk = refine_stream_fix_kernel<TC, GATHER>;
+                if ((lrc = hand_over(fk))) return lrc;
                 fixed = true;
                 c->refine_fix_used = true;
             }

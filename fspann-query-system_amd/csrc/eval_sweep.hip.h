@@ -1,6 +1,6 @@
 // eval_sweep.hip.h — computeMetricsAtK (FSA:770-835) for EVERY k of kVariants from one result list, one launch
 // (fspann_eval_kvariants_dev, include/fspann_eval.h): runQueries' metric loop (FSA:684-692).  Row j of the outputs is what
-// gt_metrics_kernel / gt_metrics_typed_kernel (groundtruth.hip.h) write for k = ks[j], bit for bit; those kernels stay as they are.
+// gt_metrics_kernel (groundtruth.hip.h) writes for k = ks[j], bit for bit.
 // Included from fspann_api.hip behind groundtruth.hip.h (gt_u32x4, gt_piece_f32, kGtMaxK).
 #pragma once
 
@@ -20,16 +20,10 @@ __host__ __device__ inline size_t eval_q_slots(int d) { return d <= kEvalQLdsMax
 __host__ __device__ inline size_t eval_k_slots(int kmax) { return static_cast<size_t>((kmax + 3) & ~3); }
 inline size_t eval_lds_bytes(int d, int kmax) { return eval_q_slots(d) * 8 + eval_k_slots(kmax) * (8 + 8 + 4 + 4); }
 
-// element e of a 16-byte piece of a row of type TB as the float it is (gt_piece_f32, and fp32 rows: the dword itself)
-template <typename TB> __device__ __forceinline__ float eval_piece_f32(gt_u32x4 v, int e) {
-    if constexpr (std::is_same<TB, float>::value) return __uint_as_float(v[e]);
-    else return gt_piece_f32<TB>(v, e);
-}
-
 // One workgroup per query.
 //   1. the query goes to LDS as fp64, the first kmax gt ids too;
 //   2. lane r owns ONE row: ann[i] (r = 2 i) or gt[i] (r = 2 i + 1) of a place i < min(kmax, na) whose two ids are rows of the base,
-//      and sums BaseVectorReader.l2 over it in dimension order (the statements of gt_metrics_typed_kernel; d is split over lanes
+//      and sums BaseVectorReader.l2 over it in dimension order (the statements of gt_metrics_kernel; d is split over lanes
 //      nowhere), 16 bytes at a time when kVec (every row starts on a 16-byte boundary and is whole pieces: the caller checks);
 //      the lanes r = 2 i also find m(i) = max(i, first place of ann[i] in gt[0..kmax)) and count it in the histogram;
 //   3. wave 0 folds the terms dAnn_i / dGt_i in index order (rounds of 64, sequential inside a round: the fold of the existing
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(kEvalThreads) void eval_kvariants_kernel(const TB* 
 #pragma unroll
                     for (int e = 0; e < kPer; e++) {
                         const double qv = s_q[t0 + e];
-                        const double dg = qv - static_cast<double>(eval_piece_f32<TB>(piece, e));
+                        const double dg = qv - static_cast<double>(gt_piece_f32<TB>(piece, e));
                         const double pg = dg * dg;
                         s = s + pg;
                     }

@@ -25,8 +25,43 @@ constexpr int kGtRows = 256;       // base rows (= lanes) per workgroup
 constexpr int kGtSelThreads = 1024;
 constexpr int kGtMaxK = 1024;
 
-// dist[q][r] = sum_i (double)(q[q][i] - base[r][i])^2 for the queries [q0, q0 + kGtQT) of this tile.
-__global__ __launch_bounds__(kGtRows) void gt_dist_kernel(const float* __restrict__ base, int64_t n, const float* __restrict__ q, int64_t nq, int d,
+// A 16-byte piece of a row: four dwords, element e in the bits its little-endian position gives it (4 floats, 8 halves or
+// bfloat16, 16 bytes or fp8).
+typedef uint32_t gt_u32x4 __attribute__((ext_vector_type(4)));
+
+// Element e of a 16-byte piece (e is a constant after unrolling), widened EXACTLY to fp32 by the hardware's conversion of the
+// type: float the dword itself, _Float16 v_cvt_f32_f16 (the high half of a dword through SDWA WORD_1), fsp_bf16 the 16 bits moved to the top of a dword,
+// fsp_f8e4m3 one v_cvt_pk_f32_fp8 per pair, uint8_t v_cvt_f32_ubyte0..3, int8_t v_cvt_f32_i32 of the sign-extended byte (SDWA sext).
+// Every value of the six types is a float, so nothing rounds; kernels keep fp16 and fp32 denormals, so a subnormal half or
+// bfloat16 arrives as its value.
+template <typename TB> __device__ __forceinline__ float gt_piece_f32(gt_u32x4 v, int e) {
+    if constexpr (std::is_same<TB, float>::value) {
+        return __uint_as_float(v[e]);
+    } else if constexpr (std::is_same<TB, _Float16>::value) {
+        const uint32_t w = v[e >> 1];
+        return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>((e & 1) ? (w >> 16) : (w & 0xffffu))));
+    } else if constexpr (std::is_same<TB, fsp_bf16>::value) {
+        const uint32_t w = v[e >> 1];
+        return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
+    } else if constexpr (std::is_same<TB, fsp_f8e4m3>::value) {
+        const int w = static_cast<int>(v[e >> 2]);
+        return (e & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true)[e & 1] : __builtin_amdgcn_cvt_pk_f32_fp8(w, false)[e & 1];
+    } else if constexpr (std::is_same<TB, uint8_t>::value) {
+        return static_cast<float>((v[e >> 2] >> (8 * (e & 3))) & 0xffu);
+    } else {
+        static_assert(std::is_same<TB, int8_t>::value, "ground truth rows: float, uint8_t, int8_t, _Float16, fsp_bf16 or fsp_f8e4m3");
+        return static_cast<float>(static_cast<int32_t>(v[e >> 2] << (24 - 8 * (e & 3))) >> 24);
+    }
+}
+
+// dist[q][r] = sum_i (double)(q[q][i] - base[r][i])^2 for the queries [q0, q0 + kGtQT) of this tile, base rows of type TB
+// (fspann_groundtruth_dev: float; fspann_groundtruth_rows_dev / _store_dev: every row type): the element widened to the float
+// it is, then the reference's statements (float subtraction, fp64 square, sums in dimension order), so the matrix of typed rows
+// is bit-identical to the one of the same values held as fp32, and gt_select_kernel reads either.  kVec: every row starts on a
+// 16-byte boundary and is a whole number of 16-byte pieces (the caller checks both), and a lane reads its row a piece at a time;
+// otherwise element loads, any alignment and any d.  (fp32 rows are launched with kVec = false only.)
+template <typename TB, bool kVec>
+__global__ __launch_bounds__(kGtRows) void gt_dist_kernel(const TB* __restrict__ base, int64_t n, const float* __restrict__ q, int64_t nq, int d,
                                                           double* __restrict__ dist) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * kGtRows + threadIdx.x;
     const int64_t q0 = static_cast<int64_t>(blockIdx.y) * kGtQT;
@@ -38,15 +73,42 @@ __global__ __launch_bounds__(kGtRows) void gt_dist_kernel(const float* __restric
 #pragma unroll
     for (int t = 0; t < kGtQT; t++) acc[t] = 0.0;
     if (r < n) {
-        const float* row = base + r * d;
-        for (int i = 0; i < d; i++) {
-            const float v = row[i];
+        const TB* row = base + r * d;
+        if constexpr (kVec) {
+            constexpr int kPer = 16 / static_cast<int>(sizeof(TB));
+            const gt_u32x4* pieces = reinterpret_cast<const gt_u32x4*>(row);
+            for (int i0 = 0; i0 < d; i0 += kPer) {
+                const gt_u32x4 piece = pieces[i0 / kPer];
+                float v[kPer];
 #pragma unroll
-            for (int t = 0; t < kGtQT; t++) {
-                const float df = qt[t][i] - v;                    // float - float (GroundtruthPrecompute.java:150)
-                const double dd = static_cast<double>(df);
-                const double sq = dd * dd;
-                acc[t] = acc[t] + sq;
+                for (int e = 0; e < kPer; e++) v[e] = gt_piece_f32<TB>(piece, e);
+                // Query by query (the sums of different queries do not meet, and each still takes its squares in dimension order):
+                // one query's kPer floats are one scalar load.  The empty asm makes query t's pointer depend on the sums of query
+                // t - 2, so its load is issued one query ahead and no earlier: left alone, the scheduler starts all kGtQT loads of
+                // a piece at once (kGtQT x kPer scalar registers, of about 100) and spills hundreds of them into vector lanes.
+#pragma unroll
+                for (int t = 0; t < kGtQT; t++) {
+                    asm volatile("" : "+s"(qt[t]) : "v"(acc[(t + kGtQT - 2) % kGtQT]));
+#pragma unroll
+                    for (int e = 0; e < kPer; e++) {
+                        const float df = qt[t][e] - v[e];             // float - float (GroundtruthPrecompute.java:150)
+                        const double dd = static_cast<double>(df);
+                        const double sq = dd * dd;
+                        acc[t] = acc[t] + sq;
+                    }
+                    qt[t] += kPer;
+                }
+            }
+        } else {
+            for (int i = 0; i < d; i++) {
+                const float v = static_cast<float>(row[i]);
+#pragma unroll
+                for (int t = 0; t < kGtQT; t++) {
+                    const float df = qt[t][i] - v;                    // float - float (GroundtruthPrecompute.java:150)
+                    const double dd = static_cast<double>(df);
+                    const double sq = dd * dd;
+                    acc[t] = acc[t] + sq;
+                }
             }
         }
 #pragma unroll
@@ -134,74 +196,14 @@ __global__ __launch_bounds__(kGtSelThreads) void gt_select_kernel(const double* 
 
 // computeMetricsAtK (FSA:770-835) for one query per workgroup (64 lanes).  ann = [nq][ann_stride] ids (count per query),
 // gt = [nq][gt_stride] ground-truth ids (>= k of them).  recall[q], ratio[q] (NaN when the reference returns NaN).
-__global__ __launch_bounds__(64) void gt_metrics_kernel(const float* __restrict__ base, int64_t n, const float* __restrict__ q, int d, int k,
+// Rows of type TB, queries of type TQ: float over float (fspann_eval_metrics_dev), and for fspann_eval_metrics_typed_dev
+// TB = uint8_t or int8_t (the integer, exact in fp64) with TQ = TB or float, or TB = _Float16 (the half widened exactly),
+// fsp_bf16 (the bits shifted up, exact) or fsp_f8e4m3 (the hardware conversion, exact) with TQ = float.
+template <typename TB, typename TQ>
+__global__ __launch_bounds__(64) void gt_metrics_kernel(const TB* __restrict__ base, int64_t n, const TQ* __restrict__ q, int d, int k,
                                                         const int32_t* __restrict__ ann, int64_t ann_stride, const int32_t* __restrict__ ann_count,
                                                         const int32_t* __restrict__ gt, int64_t gt_stride, double* __restrict__ recall,
                                                         double* __restrict__ ratio) {
-    const int64_t qi = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int na = ann_count ? max(0, min(ann_count[qi], static_cast<int>(ann_stride))) : static_cast<int>(ann_stride);
-    const int32_t* a = ann + qi * ann_stride;
-    const int32_t* g = gt + qi * gt_stride;
-    // recall: hits among the first min(k, na) results that are in gt[0..k)  (a Set: a repeated id counts each time it appears, like the Java loop)
-    int hits = 0;
-    for (int i = lane; i < min(k, na); i += 64) {
-        const int32_t id = a[i];
-        bool in = false;
-        for (int j = 0; j < k; j++) in = in || (g[j] == id);
-        hits += in ? 1 : 0;
-    }
-    for (int off = 32; off > 0; off >>= 1) hits += __shfl_xor(hits, off);
-    // ratio: needs k results; BaseVectorReader.l2 = sqrt(sum (q_i - v_i)^2), q widened to double first (FSA:1017-1073)
-    // the reference adds the k terms in index order: rounds of 64 terms, lane l holds term 64 r + l, and a sequential fold over
-    // the lanes inside every round reproduces the Java sum exactly (any k)
-    double tot = 0.0;
-    int usedt = 0;
-    if (na >= k) {
-        const float* qr = q + qi * d;
-        for (int i0 = 0; i0 < k; i0 += 64) {
-            const int i = i0 + lane;
-            double term = 0.0;
-            int used = 0;
-            if (i < k) {
-                const int32_t ai = a[i], gi = g[i];
-                if (!(ai < 0 || ai >= n || gi < 0 || gi >= n)) {
-                    double sg = 0.0, sa = 0.0;
-                    for (int t = 0; t < d; t++) {
-                        const double qv = static_cast<double>(qr[t]);
-                        const double dg = qv - static_cast<double>(base[static_cast<int64_t>(gi) * d + t]);
-                        const double pg = dg * dg;
-                        sg = sg + pg;
-                        const double da = qv - static_cast<double>(base[static_cast<int64_t>(ai) * d + t]);
-                        const double pa = da * da;
-                        sa = sa + pa;
-                    }
-                    const double dGt = sqrt(sg);
-                    if (dGt > 0) { term = sqrt(sa) / dGt; used = 1; }
-                }
-            }
-            for (int l = 0; l < 64; l++) {
-                const double v = __shfl(term, l);
-                const int u = __shfl(used, l);
-                if (u) { tot = tot + v; usedt += u; }
-            }
-        }
-    }
-    if (lane == 0) {
-        recall[qi] = static_cast<double>(hits) / static_cast<double>(k);
-        ratio[qi] = (na >= k && usedt == k) ? tot / static_cast<double>(k) : __longlong_as_double(0x7FF8000000000000LL);
-    }
-}
-
-// gt_metrics_kernel over typed rows and queries (fspann_eval_metrics_typed_dev): TB = uint8_t (FSPANN_U8: the integer 0..255,
-// exact in fp64) with TQ = uint8_t or float, or TB = _Float16 (FSPANN_F16: the half widened exactly) or fsp_bf16 (FSPANN_BF16: the bits shifted up, exact) or fsp_f8e4m3 (FSPANN_F8E4M3: the hardware conversion, exact) with TQ = float; the same fp64 arithmetic and the same ordered fold, statement for statement.  The
-// fp32 kernel above stays as it is and is what fspann_eval_metrics_dev launches: routed through this template it compiled to
-// the same instructions but for the operand order of one integer add, and that kernel is kept instruction-identical.
-template <typename TB, typename TQ>
-__global__ __launch_bounds__(64) void gt_metrics_typed_kernel(const TB* __restrict__ base, int64_t n, const TQ* __restrict__ q, int d, int k,
-                                                              const int32_t* __restrict__ ann, int64_t ann_stride, const int32_t* __restrict__ ann_count,
-                                                              const int32_t* __restrict__ gt, int64_t gt_stride, double* __restrict__ recall,
-                                                              double* __restrict__ ratio) {
     const int64_t qi = blockIdx.x;
     const int lane = threadIdx.x;
     const int na = ann_count ? max(0, min(ann_count[qi], static_cast<int>(ann_stride))) : static_cast<int>(ann_stride);
@@ -254,96 +256,6 @@ __global__ __launch_bounds__(64) void gt_metrics_typed_kernel(const TB* __restri
     if (lane == 0) {
         recall[qi] = static_cast<double>(hits) / static_cast<double>(k);
         ratio[qi] = (na >= k && usedt == k) ? tot / static_cast<double>(k) : __longlong_as_double(0x7FF8000000000000LL);
-    }
-}
-
-// ---- gt_dist_kernel over typed rows with fp32 queries (fspann_groundtruth_rows_dev / _store_dev) --------------------------
-// A 16-byte piece of a typed row: four dwords, element e in the bits its little-endian position gives it (8 halves or bfloat16,
-// 16 bytes or fp8).
-typedef uint32_t gt_u32x4 __attribute__((ext_vector_type(4)));
-
-// Element e of a 16-byte piece (e is a constant after unrolling), widened EXACTLY to fp32 by the hardware's conversion of the
-// type: _Float16 v_cvt_f32_f16 (the high half of a dword through SDWA WORD_1), fsp_bf16 the 16 bits moved to the top of a dword,
-// fsp_f8e4m3 one v_cvt_pk_f32_fp8 per pair, uint8_t v_cvt_f32_ubyte0..3, int8_t v_cvt_f32_i32 of the sign-extended byte (SDWA sext).
-// Every value of the five types is a float, so nothing rounds; kernels keep fp16 and fp32 denormals, so a subnormal half or
-// bfloat16 arrives as its value.
-template <typename TB> __device__ __forceinline__ float gt_piece_f32(gt_u32x4 v, int e) {
-    if constexpr (std::is_same<TB, _Float16>::value) {
-        const uint32_t w = v[e >> 1];
-        return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>((e & 1) ? (w >> 16) : (w & 0xffffu))));
-    } else if constexpr (std::is_same<TB, fsp_bf16>::value) {
-        const uint32_t w = v[e >> 1];
-        return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
-    } else if constexpr (std::is_same<TB, fsp_f8e4m3>::value) {
-        const int w = static_cast<int>(v[e >> 2]);
-        return (e & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true)[e & 1] : __builtin_amdgcn_cvt_pk_f32_fp8(w, false)[e & 1];
-    } else if constexpr (std::is_same<TB, uint8_t>::value) {
-        return static_cast<float>((v[e >> 2] >> (8 * (e & 3))) & 0xffu);
-    } else {
-        static_assert(std::is_same<TB, int8_t>::value, "typed ground truth rows: uint8_t, int8_t, _Float16, fsp_bf16 or fsp_f8e4m3");
-        return static_cast<float>(static_cast<int32_t>(v[e >> 2] << (24 - 8 * (e & 3))) >> 24);
-    }
-}
-
-// dist[q][r] as gt_dist_kernel fills it, base rows of type TB: the element widened to the float it is, then the reference's
-// statements (float subtraction, fp64 square, sums in dimension order), so the matrix is bit-identical to the one gt_dist_kernel
-// makes of the same values held as fp32, and gt_select_kernel reads it unchanged.  kVec: every row starts on a 16-byte boundary
-// and is a whole number of 16-byte pieces (the caller checks both), and a lane reads its row a piece at a time; otherwise element
-// loads, any alignment and any d.  The fp32 kernel above is not an instantiation of this one: it stays instruction-identical.
-template <typename TB, bool kVec>
-__global__ __launch_bounds__(kGtRows) void gt_rows_dist_kernel(const TB* __restrict__ base, int64_t n, const float* __restrict__ q, int64_t nq, int d,
-                                                               double* __restrict__ dist) {
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * kGtRows + threadIdx.x;
-    const int64_t q0 = static_cast<int64_t>(blockIdx.y) * kGtQT;
-    typedef const float __attribute__((address_space(4)))* const_row_t;     // uniform loads -> scalar loads
-    const_row_t qt[kGtQT];
-#pragma unroll
-    for (int t = 0; t < kGtQT; t++) qt[t] = (const_row_t)(q + min(q0 + t, nq - 1) * d);
-    double acc[kGtQT];
-#pragma unroll
-    for (int t = 0; t < kGtQT; t++) acc[t] = 0.0;
-    if (r < n) {
-        const TB* row = base + r * d;
-        if constexpr (kVec) {
-            constexpr int kPer = 16 / static_cast<int>(sizeof(TB));
-            const gt_u32x4* pieces = reinterpret_cast<const gt_u32x4*>(row);
-            for (int i0 = 0; i0 < d; i0 += kPer) {
-                const gt_u32x4 piece = pieces[i0 / kPer];
-                float v[kPer];
-#pragma unroll
-                for (int e = 0; e < kPer; e++) v[e] = gt_piece_f32<TB>(piece, e);
-                // Query by query (the sums of different queries do not meet, and each still takes its squares in dimension order):
-                // one query's kPer floats are one scalar load.  The empty asm makes query t's pointer depend on the sums of query
-                // t - 2, so its load is issued one query ahead and no earlier: left alone, the scheduler starts all kGtQT loads of
-                // a piece at once (kGtQT x kPer scalar registers, of about 100) and spills hundreds of them into vector lanes.
-#pragma unroll
-                for (int t = 0; t < kGtQT; t++) {
-                    asm volatile("" : "+s"(qt[t]) : "v"(acc[(t + kGtQT - 2) % kGtQT]));
-#pragma unroll
-                    for (int e = 0; e < kPer; e++) {
-                        const float df = qt[t][e] - v[e];             // float - float (GroundtruthPrecompute.java:150)
-                        const double dd = static_cast<double>(df);
-                        const double sq = dd * dd;
-                        acc[t] = acc[t] + sq;
-                    }
-                    qt[t] += kPer;
-                }
-            }
-        } else {
-            for (int i = 0; i < d; i++) {
-                const float v = static_cast<float>(row[i]);
-#pragma unroll
-                for (int t = 0; t < kGtQT; t++) {
-                    const float df = qt[t][i] - v;
-                    const double dd = static_cast<double>(df);
-                    const double sq = dd * dd;
-                    acc[t] = acc[t] + sq;
-                }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kGtQT; t++)
-            if (q0 + t < nq) dist[(q0 + t) * n + r] = acc[t];
     }
 }
 

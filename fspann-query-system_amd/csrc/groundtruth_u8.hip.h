@@ -8,7 +8,7 @@
 // and runs on v_mfma_i32_32x32x32_i8; the two norms come from a small kernel of their own (v_dot4_i32_i8).  The [Q x N]
 // distances go to a scratch matrix of uint32 (half the bytes of the fp32 path's fp64 matrix) and the same exact selection as
 // gt_select_kernel runs over them: an MSB radix select of the k-th smallest composite key (distance, id).
-// Signed bytes (FSPANN_I8 base and queries) take the gt8s_* kernels further down: the same product without the flip.
+// Signed bytes (FSPANN_I8 base and queries) are the int8_t instantiations of the same kernels: the same product without the flip.
 #pragma once
 #include "fspann_common.h"
 
@@ -23,35 +23,48 @@ constexpr int kGt8Q = 128;           // queries per workgroup: 4 tiles of 32, wa
 constexpr int kGt8MaxDim = 32768;    // 32768 * 255^2 < 2^31
 constexpr int kGt8SelThreads = 1024;
 
-// Bytes [k0, k0 + 16) of one row as four words of SIGNED bytes (x ^ 0x80 = x - 128).  Bytes at k >= d are signed zeros, put
-// there AFTER the flip (a raw 0 would count as -128).  kAligned: d % 16 == 0 and a 16-byte aligned matrix, one 16-byte load.
-template <bool kAligned>
-__device__ __forceinline__ gt8_i32x4 gt8_frag(const uint8_t* __restrict__ row, int k0, int d) {
+// Bytes [k0, k0 + 16) of one row as four words of SIGNED bytes, which is what the matrix cores take.  TB = uint8_t: every byte
+// flipped (x ^ 0x80 = x - 128); bytes at k >= d are signed zeros, put there AFTER the flip (a raw 0 would count as -128).
+// TB = int8_t: the bytes as they are, and a raw 0 is the right pad.  kAligned: d % 16 == 0 and a 16-byte aligned matrix, one
+// 16-byte load.
+//
+// The distances are formed in uint32 arithmetic from the norms and the product of these signed bytes (q', x' below: q - 128 and
+// x - 128 for uint8_t, q and x themselves for int8_t).  Why that lands on the exact distance: |q'|^2 and |x'|^2 are at most
+// 16384 d <= 2^29 each, q'.x' lies in [-16256 d, 16384 d], so 2 q'.x' as an unsigned wraps when the product is negative, and
+// |q'|^2 + |x'|^2 - 2 q'.x' may pass through values >= 2^32 or "below 0" on the way.  Addition, subtraction and the
+// multiplication by 2 are those of the ring Z / 2^32, where the result depends on the operands' residues only; the true value
+// sum (q_i - x_i)^2 lies in [0, d * 255^2] with d * 255^2 < 2^31 for d <= 32768, and a residue in that range is the integer
+// itself.  (The accumulator of the MFMA is the exact q'.x': |q'.x'| <= 2^29.)  gt8_select_kernel serves both types: a distance
+// is an integer in 0 .. d * 255^2 either way.
+template <typename TB, bool kAligned>
+__device__ __forceinline__ gt8_i32x4 gt8_frag(const TB* __restrict__ row, int k0, int d) {
+    static_assert(std::is_same<TB, uint8_t>::value || std::is_same<TB, int8_t>::value, "byte ground truth rows: uint8_t or int8_t");
+    constexpr unsigned kFlip = std::is_same<TB, uint8_t>::value ? 0x80u : 0u;      // per byte; ^ 0 compiles to nothing
     gt8_u32x4 w = {0u, 0u, 0u, 0u};
     if constexpr (kAligned) {       // (d >= 16 here; the load is made at a clamped address so that the K loop holds no branch)
         w = *reinterpret_cast<const gt8_u32x4*>(row + min(k0, d - 16));
-        w ^= 0x80808080u;
+        w ^= kFlip * 0x01010101u;
         if (k0 >= d) w = gt8_u32x4{0u, 0u, 0u, 0u};
     } else {
 #pragma unroll
         for (int j = 0; j < 16; j++) {
             const int k = k0 + j;
-            const unsigned b = (k < d) ? (static_cast<unsigned>(row[k]) ^ 0x80u) : 0u;
+            const unsigned b = (k < d) ? ((static_cast<unsigned>(row[k]) & 0xFFu) ^ kFlip) : 0u;
             w[j >> 2] |= b << (8 * (j & 3));
         }
     }
     return __builtin_bit_cast(gt8_i32x4, w);
 }
 
-// out[r] = sum_i (rows[r][i] - 128)^2, one lane per row.
-template <bool kAligned>
-__global__ __launch_bounds__(256) void gt8_norm_kernel(const uint8_t* __restrict__ rows, int64_t n, int d, unsigned* __restrict__ out) {
+// out[r] = |x'|^2 = sum_i (rows[r][i] - 128)^2 (uint8_t) or sum_i rows[r][i]^2 (int8_t), at most 16384 d; one lane per row.
+template <typename TB, bool kAligned>
+__global__ __launch_bounds__(256) void gt8_norm_kernel(const TB* __restrict__ rows, int64_t n, int d, unsigned* __restrict__ out) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (r >= n) return;
-    const uint8_t* row = rows + r * d;
+    const TB* row = rows + r * d;
     int s = 0;
     for (int k0 = 0; k0 < d; k0 += 16) {
-        const gt8_i32x4 v = gt8_frag<kAligned>(row, k0, d);
+        const gt8_i32x4 v = gt8_frag<TB, kAligned>(row, k0, d);
 #pragma unroll
         for (int j = 0; j < 4; j++) s = __builtin_amdgcn_sdot4(v[j], v[j], s, false);
     }
@@ -64,8 +77,8 @@ __global__ __launch_bounds__(256) void gt8_norm_kernel(const uint8_t* __restrict
 // B: base row l & 31), i.e. 16-byte pieces of row-major data, nothing transposed; the result has the base row on the lane
 // (l & 31) and the query on the register: query (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  So one register's 32 lanes store 32
 // consecutive base rows of one query.  No barrier: a wave whose 32 rows lie beyond n leaves at once.
-template <bool kAligned>
-__global__ __launch_bounds__(256) void gt8_dist_kernel(const uint8_t* __restrict__ base, int64_t n, const uint8_t* __restrict__ q, int64_t nq, int d,
+template <typename TB, bool kAligned>
+__global__ __launch_bounds__(256) void gt8_dist_kernel(const TB* __restrict__ base, int64_t n, const TB* __restrict__ q, int64_t nq, int d,
                                                        const unsigned* __restrict__ xn, const unsigned* __restrict__ qn,
                                                        unsigned* __restrict__ dist, int64_t ld, int nqb) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -74,13 +87,13 @@ __global__ __launch_bounds__(256) void gt8_dist_kernel(const uint8_t* __restrict
     const int64_t r0 = bt * kGt8Rows + wave * 32;
     if (r0 >= n) return;
     const int64_t r = r0 + (lane & 31);
-    const uint8_t* brow = base + min(r, n - 1) * d;           // rows >= n of an edge tile: computed on a copy, never stored
+    const TB* brow = base + min(r, n - 1) * d;           // rows >= n of an edge tile: computed on a copy, never stored
     const int kh = 16 * (lane >> 5);
     const unsigned nx = xn[min(r, n - 1)];
     for (int g = 0; g < kGt8Q / 32; g++) {
         const int64_t q0 = qb * kGt8Q + g * 32;
         if (q0 >= nq) break;
-        const uint8_t* qrow = q + min(q0 + (lane & 31), nq - 1) * d;
+        const TB* qrow = q + min(q0 + (lane & 31), nq - 1) * d;
         // |q'|^2 of this lane's 16 queries, four 16-byte loads (qn holds whole tiles of 32: entries >= nq are never used for a store)
         const gt8_u32x4* qn4 = reinterpret_cast<const gt8_u32x4*>(qn + q0 + 4 * (lane >> 5));
         gt8_u32x4 nqv[4];
@@ -88,101 +101,10 @@ __global__ __launch_bounds__(256) void gt8_dist_kernel(const uint8_t* __restrict
         for (int j = 0; j < 4; j++) nqv[j] = qn4[2 * j];
         gt8_i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int k0 = 0; k0 < d; k0 += 64) {      // two K steps per turn, their four loads in flight together (a step past d is zeros)
-            const gt8_i32x4 a0 = gt8_frag<kAligned>(qrow, k0 + kh, d);
-            const gt8_i32x4 b0 = gt8_frag<kAligned>(brow, k0 + kh, d);
-            const gt8_i32x4 a1 = gt8_frag<kAligned>(qrow, k0 + 32 + kh, d);
-            const gt8_i32x4 b1 = gt8_frag<kAligned>(brow, k0 + 32 + kh, d);
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc, 0, 0, 0);
-        }
-        if (r < n) {
-            const int64_t qa = q0 + 4 * (lane >> 5);
-            unsigned* o = dist + qa * ld + r;
-            if (q0 + 32 <= nq) {
-#pragma unroll
-                for (int reg = 0; reg < 16; reg++)
-                    o[((reg & 3) + 8 * (reg >> 2)) * ld] = nqv[reg >> 2][reg & 3] + nx - 2u * static_cast<unsigned>(acc[reg]);
-            } else {
-#pragma unroll
-                for (int reg = 0; reg < 16; reg++) {
-                    const int qo = (reg & 3) + 8 * (reg >> 2);
-                    if (qa + qo < nq) o[qo * ld] = nqv[reg >> 2][reg & 3] + nx - 2u * static_cast<unsigned>(acc[reg]);
-                }
-            }
-        }
-    }
-}
-
-// ---- the same over SIGNED bytes (FSPANN_I8 base and queries, values -128..127) ------------------------------------------------------
-// The bytes are what the matrix cores take, so nothing is flipped and a raw 0 is the right pad beyond d.  Kernels of their own
-// beside the unsigned ones (which keep their names and their code); gt8_select_kernel serves both: a distance is an integer in
-// 0 .. d * 255^2 either way.
-// Why uint32 arithmetic lands on the exact distance: |q|^2 and |x|^2 are at most 16384 d <= 2^29 each, q.x lies in
-// [-16256 d, 16384 d], so 2 q.x as an unsigned wraps when the product is negative, and |q|^2 + |x|^2 - 2 q.x may pass through
-// values >= 2^32 or "below 0" on the way.  Addition, subtraction and the multiplication by 2 are those of the ring Z / 2^32,
-// where the result depends on the operands' residues only; the true value sum (q_i - x_i)^2 lies in [0, d * 255^2] with
-// d * 255^2 < 2^31 for d <= 32768, and a residue in that range is the integer itself.  (The accumulator of the MFMA is the exact
-// q.x: |q.x| <= 2^29.)
-template <bool kAligned>
-__device__ __forceinline__ gt8_i32x4 gt8s_frag(const int8_t* __restrict__ row, int k0, int d) {
-    gt8_u32x4 w = {0u, 0u, 0u, 0u};
-    if constexpr (kAligned) {       // (d >= 16 here; the load is made at a clamped address so that the K loop holds no branch)
-        w = *reinterpret_cast<const gt8_u32x4*>(row + min(k0, d - 16));
-        if (k0 >= d) w = gt8_u32x4{0u, 0u, 0u, 0u};
-    } else {
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const int k = k0 + j;
-            const unsigned b = (k < d) ? (static_cast<unsigned>(row[k]) & 0xFFu) : 0u;
-            w[j >> 2] |= b << (8 * (j & 3));
-        }
-    }
-    return __builtin_bit_cast(gt8_i32x4, w);
-}
-
-// out[r] = sum_i rows[r][i]^2 (at most 16384 d), one lane per row.
-template <bool kAligned>
-__global__ __launch_bounds__(256) void gt8s_norm_kernel(const int8_t* __restrict__ rows, int64_t n, int d, unsigned* __restrict__ out) {
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (r >= n) return;
-    const int8_t* row = rows + r * d;
-    int s = 0;
-    for (int k0 = 0; k0 < d; k0 += 16) {
-        const gt8_i32x4 v = gt8s_frag<kAligned>(row, k0, d);
-#pragma unroll
-        for (int j = 0; j < 4; j++) s = __builtin_amdgcn_sdot4(v[j], v[j], s, false);
-    }
-    out[r] = static_cast<unsigned>(s);
-}
-
-// gt8_dist_kernel over signed bytes: dist[q][r] = |q|^2 + |x|^2 - 2 q.x, the same tiling, lanes and stores.
-template <bool kAligned>
-__global__ __launch_bounds__(256) void gt8s_dist_kernel(const int8_t* __restrict__ base, int64_t n, const int8_t* __restrict__ q, int64_t nq, int d,
-                                                        const unsigned* __restrict__ xn, const unsigned* __restrict__ qn,
-                                                        unsigned* __restrict__ dist, int64_t ld, int nqb) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t bt = blockIdx.x / static_cast<unsigned>(nqb);
-    const int64_t qb = blockIdx.x % static_cast<unsigned>(nqb);
-    const int64_t r0 = bt * kGt8Rows + wave * 32;
-    if (r0 >= n) return;
-    const int64_t r = r0 + (lane & 31);
-    const int8_t* brow = base + min(r, n - 1) * d;            // rows >= n of an edge tile: computed on a copy, never stored
-    const int kh = 16 * (lane >> 5);
-    const unsigned nx = xn[min(r, n - 1)];
-    for (int g = 0; g < kGt8Q / 32; g++) {
-        const int64_t q0 = qb * kGt8Q + g * 32;
-        if (q0 >= nq) break;
-        const int8_t* qrow = q + min(q0 + (lane & 31), nq - 1) * d;
-        const gt8_u32x4* qn4 = reinterpret_cast<const gt8_u32x4*>(qn + q0 + 4 * (lane >> 5));
-        gt8_u32x4 nqv[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) nqv[j] = qn4[2 * j];
-        gt8_i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k0 = 0; k0 < d; k0 += 64) {      // two K steps per turn, their four loads in flight together (a step past d is zeros)
-            const gt8_i32x4 a0 = gt8s_frag<kAligned>(qrow, k0 + kh, d);
-            const gt8_i32x4 b0 = gt8s_frag<kAligned>(brow, k0 + kh, d);
-            const gt8_i32x4 a1 = gt8s_frag<kAligned>(qrow, k0 + 32 + kh, d);
-            const gt8_i32x4 b1 = gt8s_frag<kAligned>(brow, k0 + 32 + kh, d);
+            const gt8_i32x4 a0 = gt8_frag<TB, kAligned>(qrow, k0 + kh, d);
+            const gt8_i32x4 b0 = gt8_frag<TB, kAligned>(brow, k0 + kh, d);
+            const gt8_i32x4 a1 = gt8_frag<TB, kAligned>(qrow, k0 + 32 + kh, d);
+            const gt8_i32x4 b1 = gt8_frag<TB, kAligned>(brow, k0 + 32 + kh, d);
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc, 0, 0, 0);
         }

@@ -28,12 +28,6 @@ __device__ __forceinline__ bool nn1_before(unsigned long long a, int32_t ai, uns
     return a < b || (a == b && static_cast<uint32_t>(ai) < static_cast<uint32_t>(bi));
 }
 
-// gt_piece_f32 with fp32 rows added: element e of a 16-byte piece, widened exactly to fp32
-template <typename TB> __device__ __forceinline__ float nn1_piece_f32(gt_u32x4 v, int e) {
-    if constexpr (std::is_same<TB, float>::value) return __uint_as_float(v[e]);
-    else return gt_piece_f32<TB>(v, e);
-}
-
 // qd[j][i] = (double) q[qsel ? qsel[s0 + j] : s0 + j][i] for the cq queries of a chunk; a selection outside [0, nq) becomes a
 // row of NaN (every sum NaN: no row wins, -1 / +inf)
 template <typename TQ>
@@ -80,8 +74,8 @@ __global__ __launch_bounds__(kGtRows) void nn1_exact_kernel(const TB* __restrict
                     for (int s = 0; s < kPer; s += kSub) {
                         double v[kSub];
 #pragma unroll
-                        for (int e = 0; e < kSub; e++) v[e] = static_cast<double>(nn1_piece_f32<TB>(piece, s + e));
-                        // query by query, the load of query t issued one query ahead and no earlier (gt_rows_dist_kernel says why)
+                        for (int e = 0; e < kSub; e++) v[e] = static_cast<double>(gt_piece_f32<TB>(piece, s + e));
+                        // query by query, the load of query t issued one query ahead and no earlier (gt_dist_kernel says why)
 #pragma unroll
                         for (int t = 0; t < kGtQT; t++) {
                             const_row_t p = qt[t] + (i0 + s);

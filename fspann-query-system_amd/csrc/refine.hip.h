@@ -1001,14 +1001,12 @@ __global__ __launch_bounds__(kRefRows, (DC * sizeof(TC) <= 128 ? 4 : (DC * sizeo
 // every list), so only each list's PREFIX up to that key can hold a winner — ~3 k elements instead of nchunks * k, and
 // the searches run over prefixes of a few entries (SIFT_P10_HIGH: 86 lists x 100 -> ~4 per list).
 template <bool KEYS_IN_LDS>
-__global__ __launch_bounds__(256) void refine_merge_kernel(const RefinePartial* __restrict__ partial,
-                                                           const int32_t* __restrict__ partial_cnt, int nchunks, int k,
-                                                           int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
-                                                           int32_t* __restrict__ out_count, int32_t* __restrict__ scored) {
+__device__ __forceinline__ void refine_merge_body(const RefinePartial* __restrict__ partial, const int32_t* __restrict__ partial_cnt, int nchunks, int k,
+                                                  int32_t* __restrict__ out_ids, double* __restrict__ out_dist, int32_t* __restrict__ out_count,
+                                                  int32_t* __restrict__ scored, const int64_t qi) {
     extern __shared__ __align__(16) unsigned char merge_smem[];
     uint64_t* s_keys = reinterpret_cast<uint64_t*>(merge_smem);                       // [nchunks][k]            (KEYS_IN_LDS)
     int32_t* s_pref = reinterpret_cast<int32_t*>(merge_smem + (KEYS_IN_LDS ? static_cast<size_t>(nchunks) * k * 8 : 0));   // [nchunks] prefix lengths
-    const int64_t qi = blockIdx.x;
     const int tid = threadIdx.x;
     const int nelem = nchunks * k;
     __shared__ int s_total, s_nvalid, s_short;
@@ -1081,89 +1079,25 @@ __global__ __launch_bounds__(256) void refine_merge_kernel(const RefinePartial* 
     }
 }
 
+// One workgroup per query of the batch.
+template <bool KEYS_IN_LDS>
+__global__ __launch_bounds__(256) void refine_merge_kernel(const RefinePartial* __restrict__ partial,
+                                                           const int32_t* __restrict__ partial_cnt, int nchunks, int k,
+                                                           int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
+                                                           int32_t* __restrict__ out_count, int32_t* __restrict__ scored) {
+    refine_merge_body<KEYS_IN_LDS>(partial, partial_cnt, nchunks, k, out_ids, out_dist, out_count, scored, blockIdx.x);
+}
+
 // List mode (the retry pass): workgroup `slot` merges query qlist[slot]; the grid is the whole batch, the workgroups past *qcount
-// leave at once.  (A copy of refine_merge_kernel's body, so that the kernel every batch runs keeps its code.)
+// leave at once.
 template <bool KEYS_IN_LDS>
 __global__ __launch_bounds__(256) void refine_merge_list_kernel(const RefinePartial* __restrict__ partial,
                                                                 const int32_t* __restrict__ partial_cnt, int nchunks, int k,
                                                                 int32_t* __restrict__ out_ids, double* __restrict__ out_dist,
                                                                 int32_t* __restrict__ out_count, int32_t* __restrict__ scored,
                                                                 const int32_t* __restrict__ qlist, const int32_t* __restrict__ qcount) {
-    extern __shared__ __align__(16) unsigned char merge_smem[];
-    uint64_t* s_keys = reinterpret_cast<uint64_t*>(merge_smem);                       // [nchunks][k]            (KEYS_IN_LDS)
-    int32_t* s_pref = reinterpret_cast<int32_t*>(merge_smem + (KEYS_IN_LDS ? static_cast<size_t>(nchunks) * k * 8 : 0));   // [nchunks] prefix lengths
     if (static_cast<int64_t>(blockIdx.x) >= static_cast<int64_t>(*qcount)) return;
-    const int64_t qi = qlist[blockIdx.x];
-    const int tid = threadIdx.x;
-    const int nelem = nchunks * k;
-    __shared__ int s_total, s_nvalid, s_short;
-    __shared__ unsigned long long s_cut;
-    auto key_at = [&](int c, int i) -> uint64_t { return KEYS_IN_LDS ? s_keys[c * k + i] : partial[(qi * nchunks + c) * k + i].key; };
-    if (tid == 0) { s_total = 0; s_nvalid = 0; s_short = 0; s_cut = 0ull; }
-    if constexpr (KEYS_IN_LDS)
-        for (int e = tid; e < nelem; e += blockDim.x) s_keys[e] = partial[qi * nelem + e].key;     // entries beyond a list's length are never read
-    __syncthreads();
-    // Only lists that HOLD j keys can vouch for j keys at or below the cut.  A query with fewer candidates than B leaves trailing
-    // lists empty or short (the common partial-count case): with m lists of at least ceil(k / nchunks) keys, j = ceil(k / m) is tried —
-    // the lists holding j vouch, and the cut stands when they vouch for k between them; the shorter lists are searched like the others.
-    __shared__ int s_m;
-    const int j0 = (k + nchunks - 1) / nchunks;
-    if (tid == 0) s_m = 0;
-    __syncthreads();
-    for (int c = tid; c < nchunks; c += blockDim.x) {
-        const int cc = partial_cnt[(qi * nchunks + c) * 2];
-        s_pref[c] = cc;                                            // the list's length until the cut is known
-        atomicAdd(&s_total, cc);
-        atomicAdd(&s_nvalid, partial_cnt[(qi * nchunks + c) * 2 + 1]);
-        if (cc >= j0) atomicAdd(&s_m, 1);
-    }
-    __syncthreads();
-    const int j = s_m > 0 ? (k + s_m - 1) / s_m : 0;
-    for (int c = tid; c < nchunks; c += blockDim.x) {
-        const int cc = s_pref[c];
-        if (j > 0 && cc >= j) { atomicAdd(&s_short, 1); atomicMax(&s_cut, static_cast<unsigned long long>(key_at(c, j - 1))); }   // s_short: lists that vouch
-    }
-    __syncthreads();
-    const int eff = min(k, s_total);
-    if (j > 0 && static_cast<long long>(s_short) * j >= k) {        // the vouching lists hold >= k keys <= cut between them
-        const uint64_t cut = s_cut;
-        for (int c = tid; c < nchunks; c += blockDim.x) {
-            int lo = 0, hi = s_pref[c];                            // first index with key > cut
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (key_at(c, mid) <= cut) lo = mid + 1; else hi = mid; }
-            s_pref[c] = lo;
-        }
-    }
-    __syncthreads();
-    for (int e = tid; e < nelem; e += blockDim.x) {
-        const int c = e / k, rk = e - c * k;
-        if (rk >= s_pref[c]) continue;
-        const uint64_t mykey = key_at(c, rk);
-        int rank = rk;
-        for (int c2 = 0; c2 < nchunks && rank < eff; c2++) {
-            if (c2 == c) continue;
-            // c2 < c: count keys <= mykey (earlier positions win ties); c2 > c: keys < mykey
-            int lo = 0, hi = s_pref[c2];
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                const uint64_t km = key_at(c2, mid);
-                const bool before = (c2 < c) ? (km <= mykey) : (km < mykey);
-                if (before) lo = mid + 1; else hi = mid;
-            }
-            rank += lo;
-        }
-        if (rank < eff) {
-            out_ids[qi * k + rank] = partial[qi * nelem + e].id;
-            out_dist[qi * k + rank] = __longlong_as_double(static_cast<long long>(mykey));
-        }
-    }
-    for (int i = eff + tid; i < k; i += blockDim.x) {
-        out_ids[qi * k + i] = -1;
-        out_dist[qi * k + i] = __longlong_as_double(0x7FF0000000000000LL);
-    }
-    if (tid == 0) {
-        out_count[qi] = eff;
-        if (scored) scored[qi] = s_nvalid;
-    }
+    refine_merge_body<KEYS_IN_LDS>(partial, partial_cnt, nchunks, k, out_ids, out_dist, out_count, scored, qlist[blockIdx.x]);
 }
 
 // Plaintext-store gather (TEST/BENCH stand-in for host load+decrypt): one wave-

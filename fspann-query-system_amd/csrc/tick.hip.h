@@ -19,7 +19,7 @@
 //
 // tick_kernel is fp32-only (queries and rows).  A tick over FSPANN_U8, FSPANN_I8, FSPANN_F16, FSPANN_BF16 or FSPANN_F8E4M3 rows that would have fused runs the stand-alone kernels in
 // stream order instead (fspann_last_tick_fused says 0; results identical); a refine-only tick with a hand-over buffer keeps its
-// one launch through the typed refine_stream_fix_kernel overload below.
+// one launch through refine_stream_fix_kernel<TC, GATHER> below.
 #pragma once
 #include "encode.hip.h"
 #include "refine.hip.h"
@@ -151,20 +151,12 @@ struct RefineRouteFix {
         __syncthreads();                                            // F_q and its count are in global memory, LDS is free again
     }
 };
-template <bool GATHER>
-__global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_fix_kernel(const RefineArgs<float, float> a, const int64_t nq,
-                                                                                       const RouteParams* __restrict__ fix_dev) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    refine_stream_run<float, float, 32, GATHER, RefineRouteFix>(a, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), nq, true,
-                                                                RefineRouteFix{fix_dev, smem});
-}
-
-// The same kernel over FSPANN_U8 / FSPANN_F16 / FSPANN_BF16 / FSPANN_F8E4M3 / FSPANN_I8 rows (one 128-byte tile per 128 / 64 / 64 / 128 / 128 dims; an overload with the row type as a template parameter, so
-// that the fp32 kernel above keeps its symbol and its code): a U8, F16, BF16, F8E4M3 or I8 batch keeps the front pipeline.
+// Rows of type TC, one 128-byte tile at a time (32 fp32 dims; 128 / 64 / 64 / 128 / 128 dims of FSPANN_U8 / FSPANN_F16 / FSPANN_BF16 /
+// FSPANN_F8E4M3 / FSPANN_I8): a batch of any of these row types keeps the front pipeline.
 template <typename TC, bool GATHER>
 __global__ __launch_bounds__(kRefRows, (GATHER ? 2 : 4)) void refine_stream_fix_kernel(const RefineArgs<TC, float> a, const int64_t nq,
                                                                                        const RouteParams* __restrict__ fix_dev) {
-    static_assert(sizeof(TC) <= 2, "fp32 rows: refine_stream_fix_kernel<GATHER>");
+    static_assert(sizeof(TC) <= 4, "refine_stream_fix_kernel rows: float, uint8_t, int8_t, _Float16, fsp_bf16 or fsp_f8e4m3 (no hand-over kernel reads double rows)");
     extern __shared__ __align__(16) unsigned char smem[];
     refine_stream_run<TC, float, 128 / static_cast<int>(sizeof(TC)), GATHER, RefineRouteFix>(a, smem, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(gridDim.x), nq, true,
                                                               RefineRouteFix{fix_dev, smem});

@@ -108,8 +108,8 @@ F16_KERNELS = [
     ("store_gather_kernel<_Float16>", False),
     ("touch_mark_rows_kernel<float, _Float16>", False),
     ("touch_store_valid_kernel<_Float16>", False),
-    ("build_widen_f16_kernel", False),
-    ("gt_metrics_typed_kernel<_Float16, float>", False),
+    ("build_widen_kernel<_Float16>", False),
+    ("gt_metrics_kernel<_Float16, float>", False),
 ]
 
 
@@ -125,10 +125,10 @@ def test_f16_kernels_exist_without_scratch(kernels, frag, dense_stream):
         assert 256 * (64 + 8) * 2 + md["group_segment_fixed_size"] <= 160 * 1024 // 4, md
 
 
-def test_fp32_hand_over_kernel_keeps_its_symbol(kernels):
-    """the typed hand-over kernel is an overload: the fp32 one is still refine_stream_fix_kernel<GATHER>, the U8 one stays"""
+def test_one_hand_over_kernel_per_row_type(kernels):
+    """refine_stream_fix_kernel<row type, GATHER>: exactly one instantiation for fp32, for U8 and for F16 rows, per GATHER"""
     for g in ("true", "false"):
-        assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<{g}>(" in k]) == 1
+        assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<float, {g}>(" in k]) == 1
         assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<unsigned char, {g}>(" in k]) == 1
 
 

@@ -214,8 +214,8 @@ F8_KERNELS = [
     (f"touch_mark_rows_kernel<float, {T}>", False),
     (f"touch_mark_rows_kernel<double, {T}>", False),
     (f"touch_store_valid_kernel<{T}>", False),
-    ("build_widen_f8_kernel", False),
-    (f"gt_metrics_typed_kernel<{T}, float>", False),
+    (f"build_widen_kernel<{T}>", False),
+    (f"gt_metrics_kernel<{T}, float>", False),
 ]
 
 
@@ -234,10 +234,10 @@ def test_f8_kernels_exist_without_scratch(kernels, frag, dense_stream):
         assert md["group_segment_fixed_size"] == kernels[u8[0]]["group_segment_fixed_size"]
 
 
-def test_fp32_hand_over_kernel_keeps_its_symbol(kernels):
-    """the typed hand-over kernel is an overload: the fp32 one is still refine_stream_fix_kernel<GATHER>, the other row types stay"""
+def test_one_hand_over_kernel_per_row_type(kernels):
+    """refine_stream_fix_kernel<row type, GATHER>: exactly one instantiation for fp32, for U8, for BF16 and for F8E4M3 rows, per GATHER"""
     for g in ("true", "false"):
-        assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<{g}>(" in k]) == 1
+        assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<float, {g}>(" in k]) == 1
         assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<unsigned char, {g}>(" in k]) == 1
         assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<fspann::fsp_bf16, {g}>(" in k]) == 1
         assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<{T}, {g}>(" in k]) == 1

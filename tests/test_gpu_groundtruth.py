@@ -79,3 +79,34 @@ def test_metrics_match_compute_metrics_at_k(pkg, oracle):
     assert np.array_equal(np.isnan(rat), np.isnan(ref_rat)) and np.isnan(rat[[3, 5, 9, 11]]).all()
     ok = ~np.isnan(rat)
     assert np.array_equal(rat[ok], ref_rat[ok]) and (rat[ok] >= 1.0 - 1e-12).all()
+
+
+@pytest.mark.parametrize("call,rows", [("groundtruth_dev", np.float32), ("groundtruth_rows_dev", np.uint8)])
+def test_groundtruth_past_65535_query_tiles_runs_in_chunks(pkg, call, rows):
+    """nq = 65535 * 16 + 17: one query tile more than gridDim.y can hold, plus a ragged tail.  At the default scratch budget the
+    whole batch would be one chunk ([nq x 3] fp64 is 25 MB); the chunk loop cuts it at 65535 tiles, on the fp32 path as on the typed
+    one.  Rows and queries are small integers, so every distance is exact and many tie: every id (ties to the lower id) and every
+    squared distance is held against numpy."""
+    import torch
+    dev = torch.device("cuda", 0)
+    n, d, k, nq = 3, 2, 2, 65535 * 16 + 17
+    X = np.array([[0, 0], [2, 0], [0, 2]], rows)
+    Q = np.random.default_rng(65535).integers(0, 4, (nq, d)).astype(np.float32)
+    D = ((Q[:, None, :].astype(np.float64) - X[None].astype(np.float64)) ** 2).sum(-1)
+    ref_ids = np.argsort(D, axis=1, kind="stable")[:, :k].astype(np.int32)             # stable: ties go to the lower id
+    ref_d2 = np.take_along_axis(D, ref_ids.astype(np.int64), axis=1)
+    assert (D[:, 0] == D[:, 1]).any() and (D[:, 1] == D[:, 2]).any()                   # ties do decide
+    cfg = pkg.PaperRuntimeConfig(tables=1, divisions=1, m=4, lambda_=2, dim=d)
+    with pkg.FspannContext(cfg, 0) as ctx:
+        xd, qd = torch.from_numpy(X).to(dev), torch.from_numpy(Q).to(dev)
+        ids = torch.full((nq, k), -7, dtype=torch.int32, device=dev)
+        d2 = torch.full((nq, k), -7.0, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        if call == "groundtruth_dev":
+            ctx.groundtruth_dev(n, xd.data_ptr(), nq, qd.data_ptr(), d, k, ids.data_ptr(), d2.data_ptr())
+        else:
+            ctx.groundtruth_rows_dev(n, xd.data_ptr(), pkg._native.U8, nq, qd.data_ptr(), d, k, ids.data_ptr(), d2.data_ptr())
+        ctx.sync()
+        ids, d2 = ids.cpu().numpy(), d2.cpu().numpy()
+    assert np.array_equal(ids, ref_ids), np.flatnonzero((ids != ref_ids).any(axis=1))[:8]
+    assert np.array_equal(d2, ref_d2)

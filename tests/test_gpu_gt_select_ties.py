@@ -3,7 +3,7 @@ groups of rows at one distance, so that the id digits of the radix walk choose t
 which need n > 65536 and n > 2^24 -- the boundary at which gt8_select_kernel may skip the id digits (k = the size of the tie group,
 and one to either side), keys that differ in their low mantissa bytes only, k = 1024, non-finite distances and the tile edges of
 gt_dist_kernel.  Cases a, b and c hold small integers, which every row type holds, and run through five callers: groundtruth_dev
-(F32), groundtruth_rows_dev with F16 and with U8 rows and fp32 queries (gt_rows_dist_kernel, 16 bytes at a time where a row is a
+(F32), groundtruth_rows_dev with F16 and with U8 rows and fp32 queries (gt_dist_kernel over typed rows, 16 bytes at a time where a row is a
 whole number of 16-byte pieces and by element otherwise, then gt_select_kernel), and groundtruth_typed_dev over (U8, U8) and
 (I8, I8) (gt8_select_kernel).  Expected values come from tests/gt_ref.py's knn() -- which tests/test_gt_ref_cpu.py holds against the
 oracle on the same data sets -- and, where the data set has one, from the closed form of the ids.  Every comparison is exact."""

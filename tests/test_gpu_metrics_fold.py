@@ -1,4 +1,4 @@
-"""GPU: gt_metrics_kernel / gt_metrics_typed_kernel (fspann_eval_metrics_dev / _typed_dev) at k on both sides of 64 and up to 1024,
+"""GPU: gt_metrics_kernel<TB, TQ> (fspann_eval_metrics_dev / _typed_dev) at k on both sides of 64 and up to 1024,
 where the ratio's fold takes more than one round of 64 lanes and the recall loop strides: k in {1, 63, 64, 65, 100, 128, 129, 1000,
 1024} at d = 24, {65, 100, 1024} at d = 1 and 100, n = 3000, 12 queries, every pair of row and query type the call takes, rows on
 each type's own grid.  Expected values come from tests/gt_ref.py (a plain restatement of computeMetricsAtK; typed rows go in as the

@@ -370,7 +370,7 @@ def _tick_bufs(ctx, nq, B, K, TD, W):
 @pytest.mark.parametrize("dense", [True, False], ids=["dense", "gather"])
 def test_refine_only_tick_finishes_handed_over_queries(pkg, oracle, dense, monkeypatch):
     """Route as a tick with a hand-over buffer (a tiny entry budget: queries stay PENDING), then a refine-only tick over U8 rows: the
-    scan's own workgroups finish the PENDING queries first (the U8 refine_stream_fix_kernel: one launch, last_tick_fused)."""
+    scan's own workgroups finish the PENDING queries first (refine_stream_fix_kernel<uint8_t, GATHER>: one launch, last_tick_fused)."""
     import torch
     monkeypatch.setenv("FSPANN_ROUTE_LAZY_CAP", "258")
     N = pkg._native

@@ -47,7 +47,7 @@ def test_gt8_dist_kernel_runs_on_the_int8_matrix_cores(pkg, tmp_path):
             cur = bodies.setdefault(m.group(1), []) if "gt8_dist_kernel" in m.group(1) and not m.group(1).endswith(".kd") else None
         elif cur is not None and line.startswith("\t"):
             cur.append(line.split("//")[0].strip())
-    assert len(bodies) >= 2, list(bodies)                 # the 16-byte-load and the byte-load instantiation
+    assert len(bodies) >= 2, list(bodies)                 # the 16-byte-load and the byte-load instantiation, of uint8_t and of int8_t
     for name, ins in bodies.items():
         assert len(ins) > 50, (name, len(ins))
         assert any(i.startswith("v_mfma_i32_") for i in ins), name

@@ -150,7 +150,7 @@ def test_null_context_without_gpu(pkg):
 
 @pytest.mark.parametrize("d", [1, 7, 100, 960, 32768])
 def test_wraparound_identity_at_the_extremes(d):
-    """What gt8s_dist_kernel stores is |q|^2 + |x|^2 - 2 q.x in uint32 arithmetic.  Restated in numpy with the same wrap-around:
+    """What gt8_dist_kernel<int8_t, .> stores is |q|^2 + |x|^2 - 2 q.x in uint32 arithmetic.  Restated in numpy with the same wrap-around:
     it equals sum (q - x)^2 for every pairing of all -128, all 127, all -1 and mixed rows, up to d = 32768, where |q|^2 + |x|^2
     reaches 2^30, 2 q.x is negative (wraps as an unsigned) and the distance itself is d * 65025 < 2^31."""
     rng = np.random.default_rng(d)
@@ -228,13 +228,13 @@ I8_KERNELS = [
     (f"store_gather_kernel<{T}>", False),
     (f"touch_mark_rows_kernel<float, {T}>", False),
     (f"touch_mark_rows_kernel<double, {T}>", False),
-    ("build_widen_i8_kernel", False),
-    (f"gt_metrics_typed_kernel<{T}, {T}>", False),
-    (f"gt_metrics_typed_kernel<{T}, float>", False),
-    ("gt8s_norm_kernel<true>", False),
-    ("gt8s_norm_kernel<false>", False),
-    ("gt8s_dist_kernel<true>", False),
-    ("gt8s_dist_kernel<false>", False),
+    (f"build_widen_kernel<{T}>", False),
+    (f"gt_metrics_kernel<{T}, {T}>", False),
+    (f"gt_metrics_kernel<{T}, float>", False),
+    (f"gt8_norm_kernel<{T}, true>", False),
+    (f"gt8_norm_kernel<{T}, false>", False),
+    (f"gt8_dist_kernel<{T}, true>", False),
+    (f"gt8_dist_kernel<{T}, false>", False),
 ]
 
 
@@ -255,17 +255,21 @@ def test_i8_kernels_exist_without_scratch(kernels, frag, dense_stream):
         assert 256 * (128 + 16) * 1 + md["group_segment_fixed_size"] <= 160 * 1024 // 4, md
 
 
-def test_unsigned_kernels_keep_their_symbols(kernels):
-    """the signed ground-truth kernels stand beside the unsigned ones, and each hand-over kernel is an overload of its own"""
+def test_one_byte_kernel_per_type_and_alignment(kernels):
+    """one instantiation of the byte ground-truth kernels per (type, aligned) and one select for both; one hand-over kernel per
+    (row type, GATHER), fp32 rows included"""
     ks = kernels["k"]
     for a in ("true", "false"):
-        assert len([k for k in ks if f"fspann::gt8_norm_kernel<{a}>(" in k]) == 1
-        assert len([k for k in ks if f"fspann::gt8_dist_kernel<{a}>(" in k]) == 1
-        assert len([k for k in ks if f"fspann::refine_stream_fix_kernel<{a}>(" in k]) == 1
+        for t in ("unsigned char", T):
+            assert len([k for k in ks if f"fspann::gt8_norm_kernel<{t}, {a}>(" in k]) == 1
+            assert len([k for k in ks if f"fspann::gt8_dist_kernel<{t}, {a}>(" in k]) == 1
+        assert len([k for k in ks if f"fspann::refine_stream_fix_kernel<float, {a}>(" in k]) == 1
+        assert len([k for k in ks if f"fspann::refine_stream_fix_kernel<{T}, {a}>(" in k]) == 1
         assert len([k for k in ks if f"fspann::refine_stream_fix_kernel<unsigned char, {a}>(" in k]) == 1
         assert len([k for k in ks if f"fspann::refine_stream_fix_kernel<fspann::fsp_f8e4m3, {a}>(" in k]) == 1
     assert len([k for k in ks if "fspann::gt8_select_kernel(" in k]) == 1
-    assert not [k for k in ks if "gt8s_select" in k]                      # one selection serves both
+    assert len([k for k in ks if "gt8_norm_kernel<" in k]) == 4 and len([k for k in ks if "gt8_dist_kernel<" in k]) == 4
+    assert not [k for k in ks if "gt8s_" in k]                            # no kernel of its own for signed bytes: one selection serves both
 
 
 def _body(kernels, frag):
@@ -303,9 +307,9 @@ def test_dense_stream_kernel_widens_signed_and_does_not_contract(kernels, tq):
 
 def test_signed_dist_kernel_runs_on_the_int8_matrix_cores(kernels):
     for a in ("true", "false"):
-        ins = _body(kernels, f"gt8s_dist_kernel<{a}>")
+        ins = _body(kernels, f"gt8_dist_kernel<{T}, {a}>")
         assert len(ins) > 50 and any(i.startswith("v_mfma_i32_32x32x32_i8") for i in ins)
         assert not [i for i in ins if "_f64" in i]
     # the aligned load takes the bytes as they are: the unsigned kernel's flip constant is not in it
-    assert not [i for i in _body(kernels, "gt8s_dist_kernel<true>") if "0x80808080" in i]
-    assert [i for i in _body(kernels, "gt8_dist_kernel<true>") if "0x80808080" in i]
+    assert not [i for i in _body(kernels, f"gt8_dist_kernel<{T}, true>") if "0x80808080" in i]
+    assert [i for i in _body(kernels, "gt8_dist_kernel<unsigned char, true>") if "0x80808080" in i]

@@ -87,7 +87,7 @@ U8_KERNELS = [
     ("refine_scan_kernel<unsigned char, float, 128, true, true>", False),
     ("store_gather_kernel<unsigned char>", False),
     ("touch_mark_rows_kernel<float, unsigned char>", False),
-    ("build_widen_u8_kernel", False),
+    ("build_widen_kernel<unsigned char>", False),
 ]
 
 
@@ -102,7 +102,8 @@ def test_u8_kernels_exist_without_scratch(kernels, frag, dense_stream):
         assert 256 * (128 + 16) + md["group_segment_fixed_size"] <= 160 * 1024 // 4, md    # 36 KB tile + static LDS
 
 
-def test_fp32_hand_over_kernel_keeps_its_symbol(kernels):
-    """the U8 hand-over kernel is an overload: the fp32 one is still refine_stream_fix_kernel<GATHER>"""
+def test_one_hand_over_kernel_per_row_type(kernels):
+    """refine_stream_fix_kernel<row type, GATHER>: exactly one instantiation for fp32 rows and one for U8 rows, per GATHER"""
     for g in ("true", "false"):
-        assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<{g}>(" in k]) == 1
+        assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<float, {g}>(" in k]) == 1
+        assert len([k for k in kernels if f"fspann::refine_stream_fix_kernel<unsigned char, {g}>(" in k]) == 1

@@ -87,7 +87,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -234,6 +234,12 @@ _SIGS_VALIDATE = {
 }
 
 
+# include/fspann_route_plan.h: the plan of a Route call, a diagnostic (a fifth table: the four above stay as they are)
+_SIGS_PLAN = {
+    "fspann_route_plan_info": (_i, [_vp, _i, C.c_int32, _i, _vp, _i]),
+}
+
+
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
     global _LIB
@@ -243,7 +249,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -275,3 +281,8 @@ def eval_symbols():
 def validate_symbols():
     """the entry points of include/fspann_gt_validate.h"""
     return sorted(_SIGS_VALIDATE)
+
+
+def plan_symbols():
+    """the entry points of include/fspann_route_plan.h"""
+    return sorted(_SIGS_PLAN)

@@ -1,6 +1,7 @@
 // api_route.hip.h — Route entry points: the plan of a Route call, fspann_route[_dev], the select switch and its counters (PIS:592-715, QSI:169-214)
 // Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
+#include "../../include/fspann_route_plan.h"
 
 namespace {
 
@@ -13,6 +14,8 @@ struct RoutePlan {
     // bounded select (route_lazy.hip.h)
     int lds_sort_words;
     bool long_lists;
+    bool g_sub;                    // the grouped ordering of long lists gets its sub-key buffer
+    int seq_bits, wave_sort;       // bits of a tuple number; groups sorted by single waves (route.hip.h, phase C)
     int lazy, lazy_cap, lz_ht_size, lz_grid, lz_entries;
     bool bincheck;                 // the bounded select runs its exact treeify check (bin16)
     int slice_bits, slice_ht;      // sliced hash build of the full select in global-arena mode (0 / 0: off)
@@ -63,6 +66,10 @@ int plan_route(fspann_ctx* c, int probe_override, int64_t nq, int32_t limit, Rou
     // reused, in global mode 64 KB behind the small arrays are reserved for it
     pl.lds_sort_words = 0;
     pl.long_lists = std::min<int64_t>(limit, pl.maxcand) > kRankSortMax - 128;
+    pl.g_sub = pl.long_lists && pl.maxcand > 0 && c->knob_wave_sort >= 0;   // (FSPANN_ROUTE_WAVE_SORT=-1: the general sort only)
+    pl.wave_sort = c->knob_wave_sort > 0 ? 1 : 0;
+    pl.seq_bits = 1;
+    while ((1 << pl.seq_bits) < pl.max_tuples) pl.seq_bits++;
     if (!pl.lds_mode && small + 65536 + 64 <= budget) {
         // room for every sub-key of the longest possible list + eight wave slices + the cursors when the budget allows (one workgroup
         // per CU in this mode anyway), 64 KB otherwise (the sub-keys then go through global memory)
@@ -140,6 +147,22 @@ int64_t fspann_route_max_candidates(fspann_ctx* c, int probe_override) {
     return std::min<int64_t>(mt, static_cast<int64_t>(c->hard_cap) - 1 + c->cfg.block_size);
 }
 
+// Diagnostics: the plan a Route call with these arguments would run with (host only: nothing is launched or synchronised).
+// The field order is part of the ABI (include/fspann_route_plan.h); returns how many fields exist, writes min(n_out, that many).
+int fspann_route_plan_info(fspann_ctx* c, int probe_override, int32_t limit, int want_counters, int32_t* out, int n_out) {
+    if (!c) return fail(FSPANN_E_NULL, "ctx is null");
+    if (!out && n_out > 0) return fail(FSPANN_E_NULL, "output buffer is null");
+    if (limit <= 0) return fail(FSPANN_E_ARG, "limit must be > 0");
+    RoutePlan pl;
+    if (int rc = plan_route(c, probe_override, 1, limit, pl, want_counters != 0)) return rc;
+    const int32_t v[] = {pl.ht_size, pl.lds_sort_words, pl.sort_cap, pl.lds_mode, pl.threads, pl.max_tuples, pl.maxcand, pl.nbins,
+                         c->cap0, pl.slice_ht, pl.lazy, pl.g_sub ? 1 : 0,
+                         pl.seq_bits, pl.wave_sort, pl.lazy ? pl.lazy_cap : 0, pl.P};
+    constexpr int kFields = static_cast<int>(sizeof(v) / sizeof(v[0]));
+    for (int i = 0; i < kFields && i < n_out; i++) out[i] = v[i];
+    return kFields;
+}
+
 
 }  // extern "C"
 
@@ -163,7 +186,7 @@ int prepare_route(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int prob
     // global arenas of the full select: per-workgroup scratch when it does not fit LDS, the sort buffer of long lists
     const size_t ar_g = pl.lds_mode ? 0 : static_cast<size_t>(pl.grid) * pl.arena_bytes;
     const size_t so_g = static_cast<size_t>(pl.grid) * pl.g_sort_stride * 8;
-    const size_t su_g = pl.long_lists ? static_cast<size_t>(pl.grid) * static_cast<size_t>(pl.maxcand) * 4 : 0;     // sub-keys grouped by score
+    const size_t su_g = pl.g_sub ? static_cast<size_t>(pl.grid) * static_cast<size_t>(pl.maxcand) * 4 : 0;          // sub-keys grouped by score
     if (ar_g + so_g + su_g && (rc = ensure(c, c->ws_route, ar_g + so_g + su_g + 1024))) return rc;
     RouteParams p{};
     p.codes = codes_dev; p.tables = c->d_tables; p.recs = c->d_recs; p.rec_words = c->rec_words; p.ids = c->d_ids;
@@ -171,7 +194,7 @@ int prepare_route(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int prob
     p.java_hash = c->d_java_hash; p.deleted_bits = index_owner(c)->d_deleted_bits.load(std::memory_order_acquire);
     p.nq = nq; p.TD = c->TD; p.W = c->W; p.P = pl.P; p.S = pl.S; p.S_shift = pl.S_shift;
     p.hard_cap = c->hard_cap; p.cap0 = c->cap0; p.limit = limit; p.need_cap = pl.need_cap; p.nbins = pl.nbins;
-    p.seq_bits = 1; while ((1 << p.seq_bits) < pl.max_tuples) p.seq_bits++;
+    p.seq_bits = pl.seq_bits;
     p.ht_size = pl.ht_size; p.ht_shift = pl.ht_shift; p.sort_cap = pl.sort_cap; p.max_tuples = pl.max_tuples;
     p.g_sort = so_g ? static_cast<uint64_t*>(c->ws_route.p) : nullptr;
     p.g_sort_stride = pl.g_sort_stride;
@@ -181,8 +204,7 @@ int prepare_route(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int prob
     p.g_sub_stride = pl.maxcand;
     p.lds_sort_words = pl.lds_sort_words;
     p.slice_bits = pl.slice_bits; p.slice_ht = pl.slice_ht; p.dev_flags = c->knob_devflags;
-    p.wave_sort = c->knob_wave_sort > 0 ? 1 : 0;
-    if (c->knob_wave_sort < 0) p.g_sub = nullptr;
+    p.wave_sort = pl.wave_sort;
     p.dbg = c->dbg_route;
     p.unmodelled = c->d_unmodelled;
     p.decimal_ids = c->decimal_ids ? 1 : 0;

@@ -435,6 +435,19 @@ class FspannContext:
     def route_max_candidates(self, probe_override=-1):
         return int(self.L.fspann_route_max_candidates(self._h, probe_override))
 
+    ROUTE_PLAN_FIELDS = ("ht_size", "lds_sort_words", "sort_cap", "lds_mode", "threads", "max_tuples", "maxcand", "nbins", "cap0",
+                         "slice_ht", "lazy", "g_sub", "seq_bits", "wave_sort", "lazy_cap", "probes")
+
+    def route_plan_info(self, probe_override=-1, limit=N.INT32_MAX, counters=True):
+        """Diagnostics: the plan route(..., probe_override, limit, counters) would run with, as a dict (fspann_route_plan_info;
+        host only, nothing is launched)."""
+        out = np.zeros(len(self.ROUTE_PLAN_FIELDS), np.int32)
+        rc = self.L.fspann_route_plan_info(self._h, probe_override, min(limit, N.INT32_MAX), 1 if counters else 0, _p(out), len(out))
+        if rc < 0:
+            N.check(rc)
+        assert rc == len(out), rc
+        return {k: int(v) for k, v in zip(self.ROUTE_PLAN_FIELDS, out)}
+
     def route(self, codes, probe_override=-1, limit=N.INT32_MAX, cap=None, counters=True, allow_unmodelled=False):
         """allow_unmodelled: return the per-query flags (count = -1: a HashMap bin would be treeified, the JVM's order
         is not modelled) instead of raising FspannStateError for the whole batch."""

@@ -155,12 +155,32 @@ def test_global_arena_path(pkg, oracle):
     check_route(pkg, sc, nq=6, probes=20, limits=(None, 512))
 
 
+def _ordering_tiers(pkg, oracle, sc, nq, probes, rng_state):
+    """The ordering path (tests/route_order_model.py) of each of the queries check_route drew from `rng_state`, full lists."""
+    from route_order_scenes import predict
+    p, o = sc["params"], sc["oracle"]
+    sc["rng"].bit_generator.state = rng_state
+    codes = o.encode(sc["rng"].standard_normal((nq, p["d"])).astype(np.float32).astype(np.float64))
+    ids, score, count, _ = o.route(codes, probe_override=probes)
+    with ctx_for(pkg, sc) as ctx:
+        plan = ctx.route_plan_info(probes, 2**31 - 1, True)
+    return plan, [predict(plan, oracle.decimal_hashes(p["n"]), ids, score, count, i, 2**31 - 1) for i in range(nq)]
+
+
 def test_long_lists_sorted_in_lds_and_global(pkg, oracle):
-    # full lists of ~3-4k entries (LDS bitonic) and ~20k entries (global bitonic)
+    # full lists of ~4k entries (scratch in LDS) and ~17k entries (scratch in the global arena).  Both are ordered by the GROUP path —
+    # per-wave sorts, the whole workgroup for the few groups above a wave's slice — not by the general bitonic sort in LDS / in
+    # global memory this test was written for (tests/test_gpu_route_order_tiers.py reaches those on purpose)
     sc = make_scene(oracle, n=20000, d=16, T=8, D=1, m=12, lam=2, B=4000, seed=51)
+    state = sc["rng"].bit_generator.state
     check_route(pkg, sc, nq=8, probes=10, limits=(None, 4000, 1500))
+    plan, tiers = _ordering_tiers(pkg, oracle, sc, 8, 10, state)
+    assert plan["lds_mode"] and all("wave" in t and t <= {"wave", "workgroup"} for t in tiers), [sorted(t) for t in tiers]
     sc = make_scene(oracle, n=60000, d=16, T=8, D=4, m=14, lam=2, B=20000, hard_cap=30000, seed=52)
+    state = sc["rng"].bit_generator.state
     check_route(pkg, sc, nq=4, probes=10, limits=(None, 20000))
+    plan, tiers = _ordering_tiers(pkg, oracle, sc, 4, 10, state)
+    assert not plan["lds_mode"] and all("wave" in t and t <= {"wave", "workgroup"} for t in tiers), [sorted(t) for t in tiers]
 
 
 def test_string_ids_via_java_hash(pkg, oracle):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import make_scene
+from route_order_scenes import max_bin_load, spread_inv as _spread_inv
 
 pytestmark = pytest.mark.gpu
 
@@ -32,12 +33,6 @@ def _import(ctx, o):
     for td in range(o.TD):
         ctx.set_index(td, **o.get_index(td))
     ctx.finalize()
-
-
-def _spread_inv(s):
-    """String.hashCode values whose HashMap.hash() spread is `s` (h ^ h >>> 16 is an involution)."""
-    s = np.asarray(s).astype(np.uint32)
-    return (s ^ (s >> 16)).view(np.int32)
 
 
 def _crowded_distinct_hashes(rng, n, nbins, cap):
@@ -241,9 +236,7 @@ def _crowd(oracle, o, sc, codes, q, k, rng, positions=None):
 
 def _max_bin_load(jh, lists, counts):
     """Per query: the largest number of (distinct, live — the lists hold nothing else) ids sharing one bin of the 32768-table."""
-    h = jh.view(np.uint32)
-    sp = (h ^ (h >> 16)) & 32767
-    return np.array([np.unique(sp[l[:c]], return_counts=True)[1].max() for l, c in zip(lists, counts)])
+    return max_bin_load(jh, lists, counts, 32768)
 
 
 @pytest.mark.parametrize("mode", [0, 2])

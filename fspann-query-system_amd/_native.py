@@ -1,5 +1,5 @@
 """ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
-include/fspann_gt_validate.h).
+include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -87,7 +87,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -239,6 +239,16 @@ _SIGS_PLAN = {
     "fspann_route_plan_info": (_i, [_vp, _i, C.c_int32, _i, _vp, _i]),
 }
 
+# include/fspann_sweep.h: Refine and search at several refinement limits in one pass (a table of its own: those above stay as they are)
+_i64p = C.POINTER(_i64)
+_SIGS_SWEEP = {
+    "fspann_refine_sweep_dev": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i64, _vp, _vp, _i64p, _i, _i, _vp, _vp, _vp, _vp]),
+    "fspann_refine_store_sweep_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _vp, _i64p, _i, _i, _vp, _vp, _vp, _vp]),
+    "fspann_search_sweep_dev": (_i, [_vp, _i64, _vp, _i, _i, _i64p, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fspann_search_sweep_finish_dev": (_i, [_vp, _i64, _vp, _i, _i, _i64p, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64p]),
+}
+
+
 
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
@@ -249,7 +259,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -286,3 +296,8 @@ def validate_symbols():
 def plan_symbols():
     """the entry points of include/fspann_route_plan.h"""
     return sorted(_SIGS_PLAN)
+
+
+def sweep_symbols():
+    """the entry points of include/fspann_sweep.h"""
+    return sorted(_SIGS_SWEEP)

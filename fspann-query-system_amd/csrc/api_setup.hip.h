@@ -359,7 +359,7 @@ void fspann_ctx_destroy(fspann_ctx* c) {
     free_dev(c->store_ok.p); free_dev(c->ws_touch.p);
     if (c->store_owned) free_dev(c->d_store);
     free_dev(c->ws_tickfix.p); free_dev(c->d_fixparams); free_dev(c->ws_gt.p); free_dev(c->bld_codes.p);
-    free_dev(c->ws_route.p); free_dev(c->ws_refine.p); free_dev(c->ws_probe.p); free_dev(c->ws_ovf.p); free_dev(c->ws_search.p); free_dev(c->ws_retry.p); free_dev(c->ws_fallback.p); free_devt(c->d_inv); free_devt(c->d_ids_bk); free_devt(c->d_bin16);
+    free_dev(c->ws_route.p); free_dev(c->ws_refine.p); free_dev(c->ws_probe.p); free_dev(c->ws_ovf.p); free_dev(c->ws_search.p); free_dev(c->ws_retry.p); free_dev(c->ws_fallback.p); free_dev(c->ws_sweep.p); free_devt(c->d_inv); free_devt(c->d_ids_bk); free_devt(c->d_bin16);
     for (hipEvent_t e : c->rt_events) (void)hipEventDestroy(e);
     for (auto& b : c->ws_io) free_dev(b.p);
     if (c->h_pin) (void)hipHostFree(c->h_pin);

@@ -20,6 +20,7 @@
 #include "gt_validate.hip.h"
 #include "hostpipe.hip.h"
 #include "refine.hip.h"
+#include "refine_sweep.hip.h"
 #include "route.hip.h"
 #include "route_lazy.hip.h"
 #include "tick.hip.h"
@@ -42,3 +43,4 @@
 #include "api_retry.hip.h"
 #include "api_eval.hip.h"
 #include "api_gt_validate.hip.h"
+#include "api_sweep.hip.h"

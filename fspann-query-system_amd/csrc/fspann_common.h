@@ -195,6 +195,9 @@ struct fspann_ctx {
     fspann::DevBuf ws_search;        // codes / F_q ids / counts of fspann_search_store_dev
     fspann::DevBuf ws_retry;         // pick list, its count, retried / scored of fspann_search_retry_dev (api_retry.hip.h)
     fspann::DevBuf ws_fallback;      // fallback list, its count, member / fellback flags of fspann_search_fallback_dev (api_eval.hip.h)
+    fspann::DevBuf ws_sweep;         // keys, clipped counts, pick list and planes of the sweep calls (api_sweep.hip.h)
+    int64_t sweep_nq = 0, sweep_bmax = 0;   // the last fspann_search_sweep_dev: what its finish call must repeat (0: none)
+    int sweep_nl = 0, sweep_k = 0;
     struct LdsCeiling { const void* kernel; size_t bytes; };
     static constexpr int kLdsCeilings = 64;
     LdsCeiling lds_ceilings[kLdsCeilings] = {};   // kernels whose dynamic-LDS ceiling this context has raised on its device, and to what (raise_lds_ceiling)

@@ -514,8 +514,17 @@ __device__ __forceinline__ void refine_topk_running(const RefineArgs<TC, TQ>& a,
     }
 }
 
+// The key epilogue (KEYS / kKeys below; refine_sweep.hip.h): instead of a top-k the scan leaves every row's key — the fp64 bits of
+// its distance, kInvalidKey for a row that is not scored — in a [nq][nchunks * kRefRows] array, whose address travels in `partial`
+// (no partial list exists in that mode; RefineArgs keeps its layout for every kernel that takes it).
+template <typename TC, typename TQ>
+__device__ __forceinline__ void refine_keys_emit(const RefineArgs<TC, TQ>& a, const uint64_t key, const int64_t qi, const int chunk) {
+    uint64_t* __restrict__ keys = reinterpret_cast<uint64_t*>(a.partial);
+    keys[(qi * a.nchunks + chunk) * kRefRows + threadIdx.x] = key;
+}
+
 // One workgroup (kRefRows threads) = one 256-row chunk of one query: block `bidx` of nq * nchunks.  `smem` = dynamic LDS.
-template <typename TC, typename TQ, int DC, bool VEC, bool GATHER>
+template <typename TC, typename TQ, int DC, bool VEC, bool GATHER, bool KEYS = false>
 __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, unsigned char* smem, const int64_t bidx,
                                                   const int cnt_known = kRefCountUnknown) {
     const TQ* __restrict__ q = a.q;
@@ -648,7 +657,8 @@ __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, u
     const bool valid = (tid < nrows) && ok && !qbad;
     uint64_t key = kInvalidKey;
     if (valid) key = static_cast<uint64_t>(__double_as_longlong(sqrt(s)));  // QSI.java:371
-    refine_topk_emit<TC, TQ, PITCH>(a, tile, valid, key, my_id, qi, chunk, r0);
+    if constexpr (KEYS) refine_keys_emit<TC, TQ>(a, key, qi, chunk);
+    else refine_topk_emit<TC, TQ, PITCH>(a, tile, valid, key, my_id, qi, chunk, r0);
 }
 
 template <typename TC, typename TQ, int DC, bool VEC, bool GATHER>
@@ -682,10 +692,12 @@ struct RefineNoFix {
 // query (item = query * npieces + piece, items wg, wg + nwg, ...; a.cpp chunks per run) and the top-K is refine_topk_running.
 // kList (the retry pass of fspann_search_retry_dev): `nq` counts list slots and unit u belongs to query qlist[u / nchunks]; every
 // row, count and output is addressed by that query's own index.
-template <typename TC, typename TQ, int DC, bool GATHER, class FixFn = RefineNoFix, bool kMulti = false, bool kList = false>
+// kKeys: the key epilogue (refine_keys_emit) instead of a top-k.
+template <typename TC, typename TQ, int DC, bool GATHER, class FixFn = RefineNoFix, bool kMulti = false, bool kList = false, bool kKeys = false>
 __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, unsigned char* smem, const int64_t wg, const int64_t nwg,
                                                   const int64_t nq, const bool counts_fresh, const FixFn fix = FixFn(),
                                                   const int32_t* __restrict__ qlist = nullptr) {
+    static_assert(!(kKeys && (kMulti || FixFn::enabled)), "keys: one unit per chunk, no hand-over");
     static_assert(!(kMulti && (GATHER || FixFn::enabled)), "runs of chunks: dense blocks, no hand-over");
     static_assert(!(kList && (kMulti || FixFn::enabled)), "list mode: one partial list per chunk, no hand-over");
     using V = typename VecOf<TC>::type;
@@ -938,7 +950,9 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
         uint64_t key = kInvalidKey;
         if (valid) key = static_cast<uint64_t>(__double_as_longlong(sqrt(s)));  // QSI.java:371
         RS_STAMP(5);
-        if constexpr (kMulti) {
+        if constexpr (kKeys) {
+            refine_keys_emit<TC, TQ>(a, key, qi, chunk);
+        } else if constexpr (kMulti) {
             refine_topk_running<TC, TQ, PITCH>(a, tile, valid, key, my_id, qi, static_cast<int>(cp.item - qi * a.npieces), r0 + tid, cp.cc == 0, cp.cc == cp.nch - 1);
         } else {
 #ifdef FSPANN_DEBUG_STAMPS

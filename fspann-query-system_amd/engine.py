@@ -960,6 +960,114 @@ class FspannContext:
                 out["gt_validation"] = validation
             return out
 
+    @staticmethod
+    def _limits(limits):
+        """limits of a sweep call as the host array the C side reads (it checks count, order and range)"""
+        ll = [int(x) for x in limits]
+        return (C.c_int64 * max(1, len(ll)))(*ll), len(ll)
+
+    def refine_store_sweep_dev(self, nq, q_ptr, q_dtype, stride, cand_ids_ptr, cand_count_ptr, limits, k, out_ids_ptr, out_dist_ptr,
+                               out_count_ptr, scored_ptr=0):
+        """refine_store_dev at every limit of limits (a host sequence, ascending, at most 16) from one scan: plane j of ids / dist
+        [nl][nq][k] and count / scored [nl][nq] is what refine_store_dev writes with B = stride and the counts clipped to limits[j]."""
+        arr, nl = self._limits(limits)
+        N.check(self.L.fspann_refine_store_sweep_dev(self._h, nq, q_ptr, q_dtype, stride, cand_ids_ptr, cand_count_ptr, arr, nl, k,
+                                                     out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr or None))
+
+    def refine_sweep_dev(self, nq, q_ptr, q_dtype, cand_ptr, cand_dtype, stride, cand_ids_ptr, cand_count_ptr, limits, k, out_ids_ptr,
+                         out_dist_ptr, out_count_ptr, scored_ptr=0):
+        """refine_store_sweep_dev over caller-held candidate rows [nq][stride][dim] (refine_dev's)."""
+        arr, nl = self._limits(limits)
+        N.check(self.L.fspann_refine_sweep_dev(self._h, nq, q_ptr, q_dtype, cand_ptr, cand_dtype, stride, cand_ids_ptr, cand_count_ptr, arr, nl, k,
+                                               out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr or None))
+
+    def search_sweep_dev(self, nq, q_ptr, q_dtype, probe_override, limits, k, out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr=0,
+                         unique_ptr=0, bad_ptr=0, retried_ptr=0):
+        """search_retry_dev at every refinement limit of limits in one pass: one encode, one Route at max(limits), one scan; plane j of
+        every output is what search_retry_dev + its finish call write at B = limits[j] (unique = that call's sel_count)."""
+        arr, nl = self._limits(limits)
+        N.check(self.L.fspann_search_sweep_dev(self._h, nq, q_ptr, q_dtype, probe_override, arr, nl, k, out_ids_ptr, out_dist_ptr, out_count_ptr,
+                                               scored_ptr or None, unique_ptr or None, bad_ptr or None, retried_ptr or None))
+
+    def search_sweep_finish_dev(self, nq, q_ptr, q_dtype, probe_override, limits, k, out_ids_ptr, out_dist_ptr, out_count_ptr, scored_ptr=0,
+                                unique_ptr=0, bad_ptr=0, retried_ptr=0) -> int:
+        """Completes the preceding search_sweep_dev call (same arguments) as search_retry_finish_dev completes its call.  Returns how
+        many queries were finished on the host."""
+        arr, nl = self._limits(limits)
+        done = C.c_int64(0)
+        N.check(self.L.fspann_search_sweep_finish_dev(self._h, nq, q_ptr, q_dtype, probe_override, arr, nl, k, out_ids_ptr, out_dist_ptr,
+                                                      out_count_ptr, scored_ptr or None, unique_ptr or None, bad_ptr or None,
+                                                      retried_ptr or None, C.byref(done)))
+        return int(done.value)
+
+    def _search_sweep(self, dv, qd, nq, limits, k, probe_override):
+        """search_sweep_dev + its finish call into fresh device planes: (ids, dist, count, scored, unique, bad, retried, resolved)"""
+        nl = len(limits)
+        ids, dist = dv.new((nl, nq, k), np.int32), dv.new((nl, nq, k), np.float64)
+        cnt, sc, un, ret = (dv.new((nl, nq), np.int32) for _ in range(4))
+        bad = dv.new((nq,), np.int32)
+        args = (nq, qd, N.F32, probe_override, limits, k, ids, dist, cnt, sc, un, bad, ret)
+        self.search_sweep_dev(*args)
+        resolved = self.search_sweep_finish_dev(*args)
+        return ids, dist, cnt, sc, un, bad, ret, resolved
+
+    def search_sweep(self, q, limits, k, probe_override=-1):
+        """QueryServiceImpl.search with its adaptive retry at every refinement limit of limits (ascending, at most 16) in one pass over
+        the resident store.  q [nq][dim] goes as fp32.  Returns dict(ids, dist [nl][nq][k], count, scored, unique, retried [nl][nq],
+        bad [nq], resolved): plane j is the search at refinement limit limits[j]."""
+        ll = [int(x) for x in limits]
+        qq = _c(q, np.float32).reshape(-1, self.cfg.dim)
+        nq = qq.shape[0]
+        with self._Dev(self) as dv:
+            qd = dv.up(qq)
+            ids, dist, cnt, sc, un, bad, ret, resolved = self._search_sweep(dv, qd, nq, ll, int(k), probe_override)
+            return dict(ids=dv.down(ids), dist=dv.down(dist), count=dv.down(cnt), scored=dv.down(sc), unique=dv.down(un), retried=dv.down(ret),
+                        bad=dv.down(bad), resolved=resolved)
+
+    def limit_sweep(self, q, limits, k_variants, gt_ids=None, probe_override=-1):
+        """recall@k / ratio@k / candidate ratio@k against the refinement limit, from one pass: one search_sweep at K = max(k_variants),
+        the ground truth over the store once (groundtruth_store_dev) unless gt_ids [nq][>= K] is given, and eval_kvariants_dev once per
+        limit with that plane's unique.  An FSPANN_F64 store is refused as run_queries refuses it.  The sweep is QueryServiceImpl.search,
+        not runQueries: would_fall_back [nl][nq] (count == 0 and not bad) says where run_queries would have searched again.
+        Returns the keys of search_sweep plus gt_ids, recall, ratio, cand_ratio (float64 [nl][nk][nq]) and would_fall_back."""
+        code = C.c_int(0)
+        store = self.L.fspann_store_dev_ptr(self._h, C.byref(code))
+        if not store:
+            raise N.FspannStateError("plaintext store not set")
+        if code.value == N.F64:
+            raise N.FspannArgumentError("limit_sweep over an FSPANN_F64 store: the reference's ground truth reads floats")
+        ks = [int(x) for x in k_variants]
+        if not ks:
+            raise N.FspannArgumentError("k_variants is empty")
+        ll = [int(x) for x in limits]
+        K, nk, nl = max(ks), len(ks), len(ll)
+        qq = _c(q, np.float32).reshape(-1, self.cfg.dim)
+        nq = qq.shape[0]
+        g = None
+        if gt_ids is not None:
+            g = _c(gt_ids, np.int32)
+            if g.ndim != 2 or g.shape[0] != nq or g.shape[1] < K:
+                raise N.FspannArgumentError("gt_ids must be [nq][>= max(k_variants)]")
+        with self._Dev(self) as dv:
+            qd = dv.up(qq)
+            ids, dist, cnt, sc, un, bad, ret, resolved = self._search_sweep(dv, qd, nq, ll, K, probe_override)
+            if g is None:
+                gd, gs = dv.new((nq, K), np.int32), K
+                self.groundtruth_store_dev(nq, qd, K, gd)
+            else:
+                gd, gs = dv.up(g), g.shape[1]
+            rec, rat, cr = (dv.new((nl, nk, nq), np.float64) for _ in range(3))
+            for j in range(nl):
+                def plane(p, per_q, size):
+                    return C.c_void_p(p.value + j * per_q * size)
+                self.eval_kvariants_dev(self._store_n, store, code.value, nq, qd, N.F32, self.cfg.dim, ks, plane(ids, nq * K, 4), K,
+                                        plane(cnt, nq, 4), gd, gs, plane(un, nq, 4), plane(rec, nk * nq, 8), plane(rat, nk * nq, 8),
+                                        plane(cr, nk * nq, 8))
+            out = dict(ids=dv.down(ids), dist=dv.down(dist), count=dv.down(cnt), scored=dv.down(sc), unique=dv.down(un), retried=dv.down(ret),
+                       bad=dv.down(bad), resolved=resolved, gt_ids=dv.down(gd), recall=dv.down(rec), ratio=dv.down(rat), cand_ratio=dv.down(cr))
+            out["would_fall_back"] = (out["count"] == 0) & (out["bad"][None, :] == 0)
+            return out
+
     def _groundtruth_host(self, b, qq, k, run):
         """base b and queries qq (host arrays as they go to the device) -> ids, d2 of the device call `run`"""
         if b.ndim != 2 or qq.ndim != 2 or b.shape[1] != qq.shape[1]:

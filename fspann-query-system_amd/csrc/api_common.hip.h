@@ -94,31 +94,60 @@ inline fspann_ctx* index_owner(fspann_ctx* c) { return c->share_parent ? c->shar
 
 
 
-// The work area of fspann_search_store_dev (codes | F_q ids | counts | bad, each rounded to 256 bytes), shared with the calls
-// that complete or extend it (fspann_search_store_finish_dev, fspann_search_retry_dev / _finish_dev): ONE layout.
+// Work areas.  A Carver hands out 256-byte-rounded pieces of a buffer in order; over a null base it only adds up the size.  An area
+// is a struct of pointers with ONE description of its layout, lay(base, dims...), which carves its pieces and returns its size.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+    template <typename T> T* take(size_t bytes) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (bytes + 255) & ~size_t(255);
+        return p;
+    }
+};
+// The area in buffer b, grown to the area's size first ...
+template <class A, class... D> int area_grow(fspann_ctx* c, DevBuf& b, A& a, D... dims) {
+    if (int rc = ensure(c, b, a.lay(nullptr, dims...))) return rc;
+    a.lay(b.p, dims...);
+    return FSPANN_OK;
+}
+// ... or as a call of this size left it; false when none precedes.
+template <class A, class... D> bool area_held(const DevBuf& b, A& a, D... dims) {
+    if (!b.p || b.bytes < a.lay(nullptr, dims...)) return false;
+    a.lay(b.p, dims...);
+    return true;
+}
+
+// The work area of fspann_search_store_dev (codes | F_q ids | counts | bad), shared with the calls that complete or extend it
+// (fspann_search_store_finish_dev, the retry, fallback and sweep calls).
 struct SearchArea {
     const uint64_t* codes;
     int32_t* sel;
     int32_t* cnt;
     int32_t* bad;
+    size_t lay(void* base, const fspann_ctx* c, int64_t nq, int64_t B) {
+        Carver w(base);
+        codes = w.take<uint64_t>(static_cast<size_t>(nq) * c->TD * c->W * 8);
+        sel = w.take<int32_t>(static_cast<size_t>(nq) * B * 4);
+        cnt = w.take<int32_t>(static_cast<size_t>(nq) * 4);
+        bad = w.take<int32_t>(static_cast<size_t>(nq) * 4);
+        return w.off;
+    }
+    void prefer(int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev) {     // the caller's buffers where it passed them
+        if (sel_ids_dev) sel = sel_ids_dev;
+        if (sel_count_dev) cnt = sel_count_dev;
+        if (bad_dev) bad = bad_dev;
+    }
 };
-size_t search_area_bytes(const fspann_ctx* c, int64_t nq, int64_t B) {
-    const size_t cb = (static_cast<size_t>(nq) * c->TD * c->W * 8 + 255) & ~size_t(255);
-    const size_t ib = (static_cast<size_t>(nq) * B * 4 + 255) & ~size_t(255);
-    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
-    return cb + ib + 2 * nb;
+int search_area_grow(fspann_ctx* c, int64_t nq, int64_t B, int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, SearchArea& s) {
+    if (int rc = area_grow(c, c->ws_search, s, c, nq, B)) return rc;
+    s.prefer(sel_ids_dev, sel_count_dev, bad_dev);
+    return FSPANN_OK;
 }
-// Pointers into the area (the caller's buffers where it passed them); false when no area of this size exists.
-bool search_area(const fspann_ctx* c, int64_t nq, int64_t B, int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, SearchArea& s) {
-    const size_t cb = (static_cast<size_t>(nq) * c->TD * c->W * 8 + 255) & ~size_t(255);
-    const size_t ib = (static_cast<size_t>(nq) * B * 4 + 255) & ~size_t(255);
-    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
-    if (!c->ws_search.p || c->ws_search.bytes < search_area_bytes(c, nq, B)) return false;
-    char* w = static_cast<char*>(c->ws_search.p);
-    s.codes = reinterpret_cast<const uint64_t*>(w);
-    s.sel = sel_ids_dev ? sel_ids_dev : reinterpret_cast<int32_t*>(w + cb);
-    s.cnt = sel_count_dev ? sel_count_dev : reinterpret_cast<int32_t*>(w + cb + ib);
-    s.bad = bad_dev ? bad_dev : reinterpret_cast<int32_t*>(w + cb + ib + nb);
+bool search_area(fspann_ctx* c, int64_t nq, int64_t B, int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, SearchArea& s) {
+    if (!area_held(c->ws_search, s, c, nq, B)) return false;
+    s.prefer(sel_ids_dev, sel_count_dev, bad_dev);
     return true;
 }
 

@@ -1,6 +1,6 @@
 // api_gt_validate.hip.h — GroundtruthValidator on the device (include/fspann_gt_validate.h): the validator's sample, the exact
 // top-1 of a list of queries (gt_validate.hip.h) over rows given by pointer or the resident store, and validate itself.
-// Part of the single translation unit fspann_api.hip (included there, last); product code, no CPU fallback.
+// Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
 #include "../../include/fspann_gt_validate.h"
 #include "../host/java_random.hpp"

@@ -4,51 +4,82 @@
 
 namespace {
 
+// Dims per tile, DC, as a constant for f.  One- and two-byte rows: a tile is 128 bytes (128 / 64 dims), FSPANN_REFINE_DC is an fp32 /
+// fp64 notion and is ignored; FSPANN_F32 / FSPANN_F64 rows: 128 bytes unless FSPANN_REFINE_DC asks for twice or four times that.
+template <typename TC, class F>
+int with_tile_width(const fspann_ctx* c, F&& f) {
+    constexpr int DC0 = 128 / static_cast<int>(sizeof(TC));
+    if constexpr (sizeof(TC) >= 4) {
+        if (c->knob_refine_dc == DC0 * 2) return f(std::integral_constant<int, DC0 * 2>{});
+        if (c->knob_refine_dc == DC0 * 4) return f(std::integral_constant<int, DC0 * 4>{});
+    }
+    return f(std::integral_constant<int, DC0>{});
+}
+
+// How the scan of one launch runs (every Refine call, the list mode and the sweep's key scan): 16 bytes at a time or not, its LDS,
+// and the one decision between the stream and one workgroup per (query, chunk).
+struct ScanPlan {
+    bool vec;
+    size_t lds;
+    int nchunks;
+    unsigned grid;       // one workgroup per (query, chunk)
+    int stream_wgs;      // workgroups per CU of the streaming scan: dense blocks run at 128 registers (4 per CU: a 1024-query batch is
+                         // exactly one unit per workgroup on 256 CUs), the store gather at 3 per CU; FSPANN_REFINE_STREAM overrides, 0 = off
+    int64_t slots;       // ... on the whole device
+    bool stream;         // the scan runs as a stream (a kernel built for 128-byte tiles only)
+    unsigned sgrid(int64_t units) const { return static_cast<unsigned>(std::min<int64_t>(units, slots)); }
+};
+template <typename TC, int DC, bool GATHER>
+ScanPlan scan_plan(const fspann_ctx* c, int64_t nq, const TC* cand, int nchunks) {
+    constexpr int VN = VecOf<TC>::N;
+    ScanPlan s{};
+    s.vec = (c->cfg.dim % VN == 0) && ((reinterpret_cast<uintptr_t>(cand) & 15) == 0);
+    s.lds = std::max<size_t>(static_cast<size_t>(kRefRows) * (s.vec ? DC + VN : DC + 1) * sizeof(TC), static_cast<size_t>(kRefRows) * 16);
+    s.nchunks = nchunks;
+    s.grid = static_cast<unsigned>(nq * nchunks);
+    s.stream_wgs = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, GATHER ? 3 : 4) : (GATHER ? 3 : 4);
+    s.slots = static_cast<int64_t>(c->num_cus) * s.stream_wgs;
+    s.stream = DC * sizeof(TC) == 128 && s.vec && s.stream_wgs > 0 && nq * nchunks < (int64_t(1) << 31);
+    return s;
+}
+
 template <typename TC, typename TQ, int DC, bool GATHER>
 int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids,
                      const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
                      int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
+    constexpr bool kStreamTile = DC * sizeof(TC) == 128;
     // qlist / qcount (device, the retry pass of fspann_search_retry_dev): only the queries qlist[0 .. *qcount) are scored, each at its
     // own index; the launches are sized for nq and their workgroups past the count leave at once.  One partial list per chunk
     // (no running top-k), no hand-over, no kernel-attached timing.
     const bool listed = qlist != nullptr;
-    constexpr int VN = VecOf<TC>::N;
     const int d = c->cfg.dim;
     const int nchunks = static_cast<int>((B + kRefRows - 1) / kRefRows);
+    const ScanPlan sp = scan_plan<TC, DC, GATHER>(c, nq, cand, nchunks);
+    const size_t lds = sp.lds;
     RefinePartial* partial = nullptr;
     int32_t* pcnt = nullptr;
     // Long candidate lists (B in the thousands, k = 100: the reference's shipped profiles): a workgroup walks a RUN of consecutive
     // chunks of one query and keeps its best k in LDS (refine_topk_running) — one list per run instead of one per chunk.  With at
     // least half a grid of queries a run is the whole query (no merge kernel at all); fewer queries are cut into as many runs as
     // fill the grid (one query: one chunk per workgroup, as before).
-    const int stream_wgs_m = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, 4) : 4;
     int npieces = 0, cpp = 0;
-    if (!listed && !GATHER && nchunks > 1 && k > kRefFilterMaxK && k <= kRunMaxK && c->knob_refine_run && stream_wgs_m > 0 && DC * sizeof(TC) == 128 &&
-        (d % VN == 0) && ((reinterpret_cast<uintptr_t>(cand) & 15) == 0) && nq * nchunks < (int64_t(1) << 31)) {   // (= the streaming scan will run)
-        const int64_t slots = static_cast<int64_t>(c->num_cus) * stream_wgs_m;
-        int np = (nq * 2 >= slots) ? 1 : static_cast<int>(std::min<int64_t>(nchunks, (slots + nq - 1) / std::max<int64_t>(nq, 1)));
+    if (!listed && !GATHER && nchunks > 1 && k > kRefFilterMaxK && k <= kRunMaxK && c->knob_refine_run && sp.stream) {
+        int np = (nq * 2 >= sp.slots) ? 1 : static_cast<int>(std::min<int64_t>(nchunks, (sp.slots + nq - 1) / std::max<int64_t>(nq, 1)));
         cpp = (nchunks + np - 1) / np;
         npieces = (nchunks + cpp - 1) / cpp;
         if (nq * npieces >= (int64_t(1) << 31)) { npieces = 0; cpp = 0; }
     }
-    if (npieces > 1) {
-        const size_t pb = static_cast<size_t>(nq) * npieces * k * sizeof(RefinePartial);
-        const size_t cb = static_cast<size_t>(nq) * npieces * 2 * 4;
-        int rc = ensure(c, c->ws_refine, pb + cb + 64);
-        if (rc) return rc;
-        partial = static_cast<RefinePartial*>(c->ws_refine.p);
-        pcnt = reinterpret_cast<int32_t*>(static_cast<char*>(c->ws_refine.p) + ((pb + 15) & ~size_t(15)));
-    } else if (nchunks > 1 && npieces == 0) {
-        const size_t pb = static_cast<size_t>(nq) * nchunks * k * sizeof(RefinePartial);
-        const size_t cb = static_cast<size_t>(nq) * nchunks * 2 * 4;
+    const int nlists = npieces > 0 ? npieces : nchunks;      // partial lists per query (runs of chunks, or chunks)
+    if (nlists > 1) {
+        const size_t pb = static_cast<size_t>(nq) * nlists * k * sizeof(RefinePartial);
+        const size_t cb = static_cast<size_t>(nq) * nlists * 2 * 4;
         int rc = ensure(c, c->ws_refine, pb + cb + 64);
         if (rc) return rc;
         partial = static_cast<RefinePartial*>(c->ws_refine.p);
         pcnt = reinterpret_cast<int32_t*>(static_cast<char*>(c->ws_refine.p) + ((pb + 15) & ~size_t(15)));
     }
-    const bool vec = (d % VN == 0) && ((reinterpret_cast<uintptr_t>(cand) & 15) == 0);
-    const size_t lds = std::max<size_t>(static_cast<size_t>(kRefRows) * (vec ? DC + VN : DC + 1) * sizeof(TC), static_cast<size_t>(kRefRows) * 16);
-    const unsigned grid = static_cast<unsigned>(nq * nchunks);
+    const bool vec = sp.vec;
+    const unsigned grid = sp.grid;
     const RefineArgs<TC, TQ> ra{q, cand, GATHER ? c->store_n : 0, B, d, cand_ids, cand_count, k, nchunks, out_ids, out_dist, out_count, scored, partial, pcnt, npieces, cpp, c->dbg_route};
     auto launch = [&](auto kern) -> int {
         if (lds > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, lds)) return rc;
@@ -63,41 +94,19 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
     int lrc = FSPANN_OK;
     bool streamed = false;
     if (listed) {
-        const int stream_wgs_l = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, GATHER ? 3 : 4) : (GATHER ? 3 : 4);
-        bool done = false;
-        if constexpr (DC * sizeof(TC) == 128) if (vec && stream_wgs_l > 0 && nq * nchunks < (int64_t(1) << 31)) {
-            const unsigned sgrid = static_cast<unsigned>(std::min<int64_t>(nq * nchunks, static_cast<int64_t>(c->num_cus) * stream_wgs_l));
-            hipLaunchKernelGGL((refine_stream_list_kernel<TC, TQ, DC, GATHER>), dim3(sgrid), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
-            done = true;
+        if constexpr (kStreamTile) if (sp.stream) {
+            hipLaunchKernelGGL((refine_stream_list_kernel<TC, TQ, DC, GATHER>), dim3(sp.sgrid(nq * nchunks)), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
+            streamed = true;
         }
-        if (!done) {
+        if (!streamed) {
             auto kern = vec ? refine_scan_list_kernel<TC, TQ, DC, true, GATHER> : refine_scan_list_kernel<TC, TQ, DC, false, GATHER>;
             if (lds > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, lds)) return rc;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
         }
-        FSP_HIP(hipGetLastError());
-        if (nchunks > 1) {
-            const size_t mlds = static_cast<size_t>(nchunks) * k * 8 + static_cast<size_t>(nchunks) * 4 + 16;
-            if (mlds <= 72 * 1024) {
-                auto mk = refine_merge_list_kernel<true>;
-                if (mlds > 64 * 1024) if (int rc = raise_lds_ceiling(c, mk, 72 * 1024)) return rc;
-                hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>(nq)), dim3(256), mlds, c->stream, partial, pcnt, nchunks, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-            } else {
-                hipLaunchKernelGGL(refine_merge_list_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(256), static_cast<size_t>(nchunks) * 4 + 16, c->stream, partial, pcnt,
-                                   nchunks, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-            }
-            FSP_HIP(hipGetLastError());
-        }
-        return FSPANN_OK;
-    }
-    // workgroups per CU of the streaming scan: dense blocks run at 128 registers (4 per CU: a 1024-query batch is exactly one
-    // unit per workgroup on 256 CUs), the store gather at 3 per CU; FSPANN_REFINE_STREAM overrides, 0 = per-query scan
-    const int stream_wgs = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, GATHER ? 3 : 4) : (GATHER ? 3 : 4);
-    if constexpr (DC * sizeof(TC) == 128) if (vec && stream_wgs > 0 && nq * nchunks < (int64_t(1) << 31)) {
-        // the scan as a stream: knob_refine_stream workgroups per CU, each walking several (query, chunk) units with the loads
+    } else if constexpr (kStreamTile) if (sp.stream) {
+        // the scan as a stream: stream_wgs workgroups per CU, each walking several (query, chunk) units with the loads
         // of the next tile in flight across unit boundaries (refine_stream_run)
-        const int64_t units = npieces > 0 ? nq * npieces : nq * nchunks;
-        const unsigned sgrid = static_cast<unsigned>(std::min<int64_t>(units, static_cast<int64_t>(c->num_cus) * stream_wgs));
+        const unsigned sgrid = sp.sgrid(nq * nlists);
         const bool timed = c->rt_on && (c->rt_seen++ % c->rt_every) == 0 && c->rt_used + 2 <= c->rt_events.size();
         hipEvent_t ev0 = timed ? c->rt_events[c->rt_used] : nullptr, ev1 = timed ? c->rt_events[c->rt_used + 1] : nullptr;
         if (timed) c->rt_used += 2;
@@ -136,24 +145,25 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
         }
         streamed = true;
     }
-    if (!streamed) lrc = vec ? launch(refine_scan_kernel<TC, TQ, DC, true, GATHER>) : launch(refine_scan_kernel<TC, TQ, DC, false, GATHER>);
+    if (!listed && !streamed) lrc = vec ? launch(refine_scan_kernel<TC, TQ, DC, true, GATHER>) : launch(refine_scan_kernel<TC, TQ, DC, false, GATHER>);
     if (lrc) return lrc;
     FSP_HIP(hipGetLastError());
     if (npieces > 0 && !streamed) return fail(FSPANN_E_STATE, "refine: the running top-k was planned but the streaming scan did not run");
-    const int nlists = npieces > 0 ? npieces : nchunks;      // partial lists per query (runs of chunks, or chunks)
     if (nlists > 1) {
-        const int nchunks = nlists;                          // (the merge below: one list per run)
-        // all keys of a query's partial lists in LDS when they fit (two workgroups per CU at least)
-        const size_t mlds = static_cast<size_t>(nchunks) * k * 8 + static_cast<size_t>(nchunks) * 4 + 16;
-        if (mlds <= 72 * 1024) {
-            auto mk = refine_merge_kernel<true>;
-            if (mlds > 64 * 1024) if (int rc = raise_lds_ceiling(c, mk, 72 * 1024)) return rc;
-            hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>(nq)), dim3(256), mlds, c->stream, partial, pcnt,
-                               nchunks, k, out_ids, out_dist, out_count, scored);
-        } else {
-            hipLaunchKernelGGL(refine_merge_kernel<false>, dim3(static_cast<unsigned>(nq)), dim3(256), static_cast<size_t>(nchunks) * 4 + 16, c->stream, partial, pcnt,
-                               nchunks, k, out_ids, out_dist, out_count, scored);
-        }
+        // the merge of a query's partial lists (one per run, or per chunk), all their keys in LDS when they fit (two workgroups per CU
+        // at least); over the listed queries when there is a list
+        const size_t mlds = static_cast<size_t>(nlists) * k * 8 + static_cast<size_t>(nlists) * 4 + 16;
+        const bool in_lds = mlds <= 72 * 1024;
+        auto merge = [&](auto mk, auto... list) -> int {
+            if (in_lds && mlds > 64 * 1024) if (int rc = raise_lds_ceiling(c, mk, 72 * 1024)) return rc;
+            hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>(nq)), dim3(256), in_lds ? mlds : static_cast<size_t>(nlists) * 4 + 16, c->stream, partial, pcnt, nlists, k,
+                               out_ids, out_dist, out_count, scored, list...);
+            return FSPANN_OK;
+        };
+        int rc;
+        if (listed) rc = in_lds ? merge(refine_merge_list_kernel<true>, qlist, qcount) : merge(refine_merge_list_kernel<false>, qlist, qcount);
+        else rc = in_lds ? merge(refine_merge_kernel<true>) : merge(refine_merge_kernel<false>);
+        if (rc) return rc;
         FSP_HIP(hipGetLastError());
     }
     return FSPANN_OK;
@@ -163,18 +173,9 @@ template <typename TC, typename TQ, bool GATHER>
 int launch_refine_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids,
                     const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
                     int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
-    auto run = [&](auto dc) {
+    int rc = with_tile_width<TC>(c, [&](auto dc) {
         return launch_refine_dc<TC, TQ, decltype(dc)::value, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
-    };
-    // dims per tile.  One- and two-byte rows: a tile is 128 bytes (128 / 64 dims), FSPANN_REFINE_DC is an fp32 / fp64 notion and is
-    // ignored; FSPANN_F32 / FSPANN_F64 rows: 128 bytes unless FSPANN_REFINE_DC asks for twice or four times that
-    constexpr int DC0 = 128 / static_cast<int>(sizeof(TC));
-    const int dc_env = c->knob_refine_dc;
-    int rc;
-    if constexpr (sizeof(TC) < 4) rc = run(std::integral_constant<int, DC0>{});
-    else if (dc_env == DC0 * 2) rc = run(std::integral_constant<int, DC0 * 2>{});
-    else if (dc_env == DC0 * 4) rc = run(std::integral_constant<int, DC0 * 4>{});
-    else rc = run(std::integral_constant<int, DC0>{});
+    });
     if (rc) return rc;
     // the touched-record set (api_touch.hip.h): the rows this launch scores, marked behind it (nothing while tracking is off)
     return touch_mark<TC, TQ, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, qlist, qcount);
@@ -429,9 +430,8 @@ int fspann_search_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
     int rc;
-    if ((rc = ensure(c, c->ws_search, search_area_bytes(c, nq, B)))) return rc;
     SearchArea sa;
-    (void)search_area(c, nq, B, sel_ids_dev, sel_count_dev, bad_dev, sa);
+    if ((rc = search_area_grow(c, nq, B, sel_ids_dev, sel_count_dev, bad_dev, sa))) return rc;
     uint64_t* codes = const_cast<uint64_t*>(sa.codes);
     int32_t* sel = sa.sel;
     int32_t* cnt = sa.cnt;

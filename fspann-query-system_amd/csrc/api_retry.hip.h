@@ -1,116 +1,166 @@
 // api_retry.hip.h — QueryServiceImpl.search with its adaptive retry (QSI:101-352, 327-337, 444-447) in one call on the device:
-// fspann_search_retry_dev / fspann_search_retry_finish_dev.  Pass 1 is fspann_search_store_dev; retry_pick_kernel lists the
-// short queries; pass 2 runs the list-mode Route (probe, bounded select, full select) and the list-mode refine over that list
-// only, with 10 probes, and overwrites those queries' rows in place.
-// Part of the single translation unit fspann_api.hip (included there, last); product code, no CPU fallback.
+// fspann_search_retry_dev / fspann_search_retry_finish_dev.  Pass 1 is fspann_search_store_dev; the pick kernel (search_pick.hip.h,
+// RetryRule) lists the short queries; pass 2 runs Route (probe, bounded select, full select) and the refine over that list only,
+// with 10 probes, and overwrites those queries' rows in place.  Also what the fallback and the sweep calls build on: the buffers of
+// a search call (SearchBufs) and the host's half of a search, finish_flagged.
+// Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
 
 namespace {
 
-constexpr int kPickThreads = 1024;
-
-// QSI's retry predicate per query (QSI:159, 293, 444-447): not rejected (bad), its Route not flagged (count -1), at least one
-// row scored, and fewer than k results or fewer than 10 k rows scored.
-__device__ __forceinline__ bool retry_wanted(const int32_t* __restrict__ bad, const int32_t* __restrict__ route_cnt,
-                                             const int32_t* __restrict__ out_count, const int32_t* __restrict__ scored, int64_t i, int k) {
-    const int32_t sc = scored[i];
-    return bad[i] == 0 && route_cnt[i] >= 0 && sc > 0 && (out_count[i] < k || static_cast<int64_t>(sc) < 10 * static_cast<int64_t>(k));
-}
-
-// One workgroup: wave w owns the contiguous slice [w * seg, (w + 1) * seg) of the batch.  Pass 1 writes retried[] and counts per
-// wave, the wave counts are scanned, pass 2 writes each picked index at its rank.  The list is ascending whatever nq is.
-__global__ __launch_bounds__(kPickThreads) void retry_pick_kernel(int64_t nq, int k, const int32_t* __restrict__ bad,
-                                                                  const int32_t* __restrict__ route_cnt, const int32_t* __restrict__ out_count,
-                                                                  const int32_t* __restrict__ scored, int32_t* __restrict__ retried,
-                                                                  int32_t* __restrict__ list, int32_t* __restrict__ count) {
-    constexpr int nwv = kPickThreads / 64;
-    __shared__ int s_base[nwv + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t seg = ((nq + nwv - 1) / nwv + 63) & ~int64_t(63);
-    const int64_t lo = min(nq, wave * seg), hi = min(nq, lo + seg);
-    int n = 0;
-    for (int64_t i0 = lo; i0 < hi; i0 += 64) {
-        const int64_t i = i0 + lane;
-        const bool p = i < hi && retry_wanted(bad, route_cnt, out_count, scored, i, k);
-        if (i < hi) retried[i] = p ? 1 : 0;
-        n += __popcll(__ballot(p));
-    }
-    if (lane == 0) s_base[wave] = n;
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int w = 0; w < nwv; w++) { const int x = s_base[w]; s_base[w] = acc; acc += x; }
-        s_base[nwv] = acc;
-        *count = acc;
-    }
-    __syncthreads();
-    int at = s_base[wave];
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int64_t i0 = lo; i0 < hi && at < s_base[wave + 1]; i0 += 64) {
-        const int64_t i = i0 + lane;
-        const bool p = i < hi && retried[i] != 0;
-        const unsigned long long m = __ballot(p);
-        if (p) list[at + __popcll(m & lt)] = static_cast<int32_t>(i);
-        at += __popcll(m);
-    }
-}
-
-// Route with limit = cap = B over the queries qlist[0 .. *qcount) only (launches sized for nq; the count is read on the device).
-int route_list_dev(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int probe_override, int64_t B, int32_t* sel, int32_t* cnt,
-                   const int32_t* qlist, const int32_t* qcount) {
-    RoutePlan pl;
-    RouteParams p{};
-    bool fused = false;
-    int rc = prepare_route(c, nq, codes_dev, probe_override, static_cast<int32_t>(B), B, sel, nullptr, cnt, nullptr, nullptr, &pl, &p, &fused);
-    if (rc) return rc;
-    p.qlist = qlist; p.qcount = qcount;
-    if (!fused) {
-        int G = 64;
-        while (G > 2 && G / 2 >= 2 * pl.P - 1 && G / 2 >= 16) G >>= 1;     // (as launch_route_probe)
-        const int gpb = kProbeThreads / G;
-        const unsigned grid1 = static_cast<unsigned>((nq * c->TD + gpb - 1) / gpb);
-        const size_t lds1 = static_cast<size_t>(gpb) * (2 * pl.P - 1) * 12;
-        hipLaunchKernelGGL(route_probe_list_kernel, dim3(grid1), dim3(kProbeThreads), lds1, c->stream, p, p.probe_g, p.nprobe_g, G);
-        FSP_HIP(hipGetLastError());
-    }
-    c->last_route_lazy = pl.lazy;
-    if (pl.lazy) {
-        auto go = [&](auto lk, bool big) -> int {      // big: the size class plans with more than the default 64 KB of LDS
-            if (big) if (int r = raise_lds_ceiling(c, lk, 159 * 1024)) return r;
-            hipLaunchKernelGGL(lk, dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
-            FSP_HIP(hipGetLastError());
-            return FSPANN_OK;
-        };
-        if (pl.lz_entries == 512) rc = go(route_select_lazy_list_kernel<kLzThreads, 512, false>, false);
-        else if (pl.lz_entries == 2048) rc = go(route_select_lazy_list_kernel<kLzThreads, 2048, true>, true);
-        else rc = go(route_select_lazy_list_kernel<kLzThreads, kLzEntriesMax, true>, true);
-        if (rc) return rc;
-        // the queries the bounded select handed over (none, normally): the full select over its overflow list, as fspann_route_dev
-        p.qcount = p.ovf_count; p.qlist = p.ovf_list;
-        pl.grid = std::min(pl.grid, 32);
-    }
-    return launch_full_select(c, pl, p);
-}
-
-// Work area of a retry call behind fspann_search_store_dev's: the pick list [nq], its count, retried [nq] (when the caller passes
-// none) and scored [nq] (when the caller passes none).
+// Work area of a retry call behind fspann_search_store_dev's: the pick list [nq], retried [nq] and scored [nq] (for the caller that
+// passes none), the list's count.
 struct RetryArea {
-    int32_t* list;
-    int32_t* count;
-    int32_t* retried;
-    int32_t* scored;
+    int32_t *list, *retried, *scored, *count;
+    size_t lay(void* base, int64_t nq) {
+        Carver w(base);
+        list = w.take<int32_t>(static_cast<size_t>(nq) * 4);
+        retried = w.take<int32_t>(static_cast<size_t>(nq) * 4);
+        scored = w.take<int32_t>(static_cast<size_t>(nq) * 4);
+        count = w.take<int32_t>(4);
+        return w.off;
+    }
 };
 
-int retry_area(fspann_ctx* c, int64_t nq, RetryArea& r) {
-    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
-    int rc = ensure(c, c->ws_retry, 3 * nb + 256);
-    if (rc) return rc;
-    char* w = static_cast<char*>(c->ws_retry.p);
-    r.list = reinterpret_cast<int32_t*>(w);
-    r.retried = reinterpret_cast<int32_t*>(w + nb);
-    r.scored = reinterpret_cast<int32_t*>(w + 2 * nb);
-    r.count = reinterpret_cast<int32_t*>(w + 3 * nb);
+// The buffers of one search call, the caller's or the work areas': what the passes and the host finish of every search family work
+// on.  In a sweep B is the largest limit and out_count / scored / retried are [nl][nq] planes.
+struct SearchBufs {
+    int64_t nq, B;
+    const void* q;
+    int q_dtype, k;
+    int32_t* out_ids;
+    double* out_dist;
+    int32_t* out_count;
+    int32_t *scored, *retried;
+    int32_t *list, *count;         // the pick list
+    SearchArea sa;
+};
+
+// ... with the area's (RetryArea, SweepArea) scored / retried where the caller passed none.
+template <class Area>
+SearchBufs search_bufs(int64_t nq, const void* q_dev, int q_dtype, int64_t B, int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev,
+                       int32_t* scored_dev, int32_t* retried_dev, const SearchArea& sa, const Area& a) {
+    return {nq, B, q_dev, q_dtype, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev ? scored_dev : a.scored, retried_dev ? retried_dev : a.retried, a.list, a.count, sa};
+}
+
+// The buffers of a retry call.  precedes (a call's name): the work areas must be as that call left them, nothing is allocated.
+int retry_bufs(fspann_ctx* c, const char* precedes, int64_t nq, const void* q_dev, int q_dtype, int64_t B, int k, int32_t* out_ids_dev, double* out_dist_dev,
+               int32_t* out_count_dev, int32_t* scored_dev, int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev, int32_t* retried_dev, SearchBufs& s) {
+    SearchArea sa;
+    RetryArea ra;
+    if (precedes) {
+        if (!search_area(c, nq, B, sel_ids_dev, sel_count_dev, bad_dev, sa) || !area_held(c->ws_retry, ra, nq))
+            return fail(FSPANN_E_STATE, "no %s call of this size precedes", precedes);
+    } else {
+        int rc;
+        if ((rc = search_area_grow(c, nq, B, sel_ids_dev, sel_count_dev, bad_dev, sa)) || (rc = area_grow(c, c->ws_retry, ra, nq))) return rc;
+    }
+    s = search_bufs(nq, q_dev, q_dtype, B, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev, retried_dev, sa, ra);
     return FSPANN_OK;
+}
+
+PickIn pick_in(const SearchBufs& s) { return {s.sa.bad, s.sa.cnt, s.out_count, s.scored, s.k}; }
+
+// QSI.search with its adaptive retry, in stream order: pass 1 is fspann_search_store_dev with the caller's probes; the pick; pass 2
+// with 10 probes (QSI:333) over the listed queries only, in place.  Pass 1 at 10 effective probes already is what pass 2 would
+// compute (same codes, same Route, same store): retried says 1 and nothing runs again.  Pass 1 receives the buffers s already
+// resolved (the caller's, or the search area's): it finds the area grown and hands the same pointers back.
+int search_retry_passes(fspann_ctx* c, const SearchBufs& s, int probe_override) {
+    int rc;
+    if ((rc = fspann_search_store_dev(c, s.nq, s.q, s.q_dtype, probe_override, s.B, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, s.sa.sel, s.sa.cnt, s.sa.bad))) return rc;
+    if ((rc = launch_pick(c, s.nq, RetryRule{pick_in(s), s.retried}, s.list, s.count))) return rc;
+    if (effective_probes(c, probe_override) == effective_probes(c, 10)) return FSPANN_OK;
+    if ((rc = route_list_dev(c, s.nq, s.sa.codes, 10, s.B, s.sa.sel, s.sa.cnt, s.list, s.count))) return rc;
+    return refine_store_list(c, s.nq, s.q, s.q_dtype, s.B, s.sa.sel, s.sa.cnt, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, s.list, s.count);
+}
+
+// First step of a finish call: the stream synchronised, the Route counts on the host; *any = one of them is flagged.
+int flagged_counts(fspann_ctx* c, const SearchBufs& s, std::vector<int32_t>& cnt, bool* any) {
+    FSP_HIP(hipStreamSynchronize(c->stream));
+    cnt.resize(static_cast<size_t>(s.nq));
+    FSP_HIP(hipMemcpy(cnt.data(), s.sa.cnt, cnt.size() * 4, hipMemcpyDeviceToHost));
+    *any = std::find(cnt.begin(), cnt.end(), kRouteUnmodelled) != cnt.end();
+    return FSPANN_OK;
+}
+
+// The host's half of one QSI.search over nl planes of (out_count, scored, retried) (the stream is synchronised): g1 = the queries
+// Route flagged in the pass at `probe_override` probes, g2 = those it flagged in the retry pass.  g1 is finished by the host model
+// and scored on every plane; the retry rule is applied to it again; the queries it sends on are routed with 10 probes on the device,
+// and what that flags joins g2; g2 is finished with 10 probes, and every query of a host-side pass 2 is scored on its retried planes.
+// score(masked) scores the queries of s.list / s.count in stream order (masked: their retried planes only; with one plane every such
+// query is retried, so both coincide).  requalified(i, count, last) follows the rule's verdict on query i: the Route count pass 1 ended
+// on and the largest retried plane (-1: none).
+template <class Score, class Requalified>
+int finish_flagged(fspann_ctx* c, const SearchBufs& s, int nl, int probe_override, std::vector<int64_t> g1, std::vector<int64_t> g2, int64_t* done, Score&& score,
+                   Requalified&& requalified) {
+    if (g1.empty() && g2.empty()) return FSPANN_OK;
+    const int64_t nq = s.nq;
+    const size_t n4 = static_cast<size_t>(nq) * 4;
+    const int32_t B32 = static_cast<int32_t>(s.B);
+    const bool same = effective_probes(c, probe_override) == effective_probes(c, 10);
+    auto put_list = [&](const std::vector<int64_t>& qs) -> int {
+        std::vector<int32_t> l(qs.begin(), qs.end());
+        const int32_t n = static_cast<int32_t>(l.size());
+        FSP_HIP(hipMemcpy(s.list, l.data(), l.size() * 4, hipMemcpyHostToDevice));
+        FSP_HIP(hipMemcpy(s.count, &n, 4, hipMemcpyHostToDevice));
+        return FSPANN_OK;
+    };
+    auto rescore = [&](const std::vector<int64_t>& qs, bool masked) -> int {
+        if (qs.empty()) return FSPANN_OK;
+        int r = put_list(qs);
+        if (r || (r = score(masked))) return r;
+        FSP_HIP(hipStreamSynchronize(c->stream));
+        return FSPANN_OK;
+    };
+    int64_t d1 = 0, d2 = 0, left = 0;
+    int r = resolve_queries(c, g1, s.sa.codes, probe_override, B32, s.B, s.sa.sel, nullptr, s.sa.cnt, nullptr, nullptr, &d1, &left);
+    if (r) return r;
+    if ((r = rescore(g1, false))) return r;
+    std::vector<int32_t> cnt(n4 / 4);
+    std::vector<int64_t> again;
+    if (!g1.empty()) {
+        std::vector<int32_t> bad(n4 / 4), oc(n4 / 4 * nl), sc(n4 / 4 * nl);
+        FSP_HIP(hipMemcpy(bad.data(), s.sa.bad, n4, hipMemcpyDeviceToHost));
+        FSP_HIP(hipMemcpy(oc.data(), s.out_count, n4 * nl, hipMemcpyDeviceToHost));
+        FSP_HIP(hipMemcpy(sc.data(), s.scored, n4 * nl, hipMemcpyDeviceToHost));
+        FSP_HIP(hipMemcpy(cnt.data(), s.sa.cnt, n4, hipMemcpyDeviceToHost));
+        for (int64_t i : g1) {
+            int last = -1;
+            for (int j = 0; j < nl; j++) {
+                const size_t pl = static_cast<size_t>(j) * nq + i;
+                if (!retry_wanted(bad[i], cnt[i], oc[pl], sc[pl], s.k)) continue;
+                const int32_t one = 1;
+                FSP_HIP(hipMemcpy(s.retried + pl, &one, 4, hipMemcpyHostToDevice));
+                last = j;
+            }
+            if ((r = requalified(i, cnt[i], last))) return r;
+            if (last >= 0) again.push_back(i);
+        }
+    }
+    std::vector<int64_t> s2 = g2;
+    if (!again.empty() && !same) {
+        if ((r = put_list(again))) return r;
+        if ((r = route_list_dev(c, nq, s.sa.codes, 10, s.B, s.sa.sel, s.sa.cnt, s.list, s.count))) return r;
+        FSP_HIP(hipStreamSynchronize(c->stream));
+        FSP_HIP(hipMemcpy(cnt.data(), s.sa.cnt, n4, hipMemcpyDeviceToHost));
+        for (int64_t i : again)
+            if (cnt[i] == kRouteUnmodelled) g2.push_back(i);
+        std::sort(g2.begin(), g2.end());
+        s2.insert(s2.end(), again.begin(), again.end());
+        std::sort(s2.begin(), s2.end());
+    }
+    if ((r = resolve_queries(c, g2, s.sa.codes, 10, B32, s.B, s.sa.sel, nullptr, s.sa.cnt, nullptr, nullptr, &d2, &left))) return r;
+    if ((r = rescore(s2, true))) return r;
+    *done += d1 + d2;
+    return FSPANN_OK;
+}
+
+// ... of a single-limit search: one plane, scored by the list-mode refine over the store.
+int finish_flagged(fspann_ctx* c, const SearchBufs& s, int probe_override, std::vector<int64_t> g1, std::vector<int64_t> g2, int64_t* done) {
+    return finish_flagged(
+        c, s, 1, probe_override, std::move(g1), std::move(g2), done,
+        [&](bool) { return refine_store_list(c, s.nq, s.q, s.q_dtype, s.B, s.sa.sel, s.sa.cnt, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, s.list, s.count); },
+        [](int64_t, int32_t, int) { return FSPANN_OK; });
 }
 
 // Stage C of the native pipeline with the retry on (fspann_pipeline_set_retry), behind pass 1's refine and under the context's
@@ -123,10 +173,9 @@ int pipeline_retry(fspann_pipeline* p, fspann_pipeline::Slot& s) {
     const double t0 = now_ms();
     int32_t* list_h = s.list_pin;
     int32_t* cnt_h = s.cnt_pin;
-    hipLaunchKernelGGL(retry_pick_kernel, dim3(1), dim3(kPickThreads), 0, c->stream, nq, p->k, static_cast<const int32_t*>(s.bad_dev),
-                       static_cast<const int32_t*>(s.cnt_dev), static_cast<const int32_t*>(s.oc_dev), static_cast<const int32_t*>(s.sc_dev),
-                       static_cast<int32_t*>(s.ret_dev), static_cast<int32_t*>(s.list_dev), static_cast<int32_t*>(s.lcnt_dev));
-    FSP_HIP(hipGetLastError());
+    const PickIn in{static_cast<const int32_t*>(s.bad_dev), static_cast<const int32_t*>(s.cnt_dev), static_cast<const int32_t*>(s.oc_dev),
+                    static_cast<const int32_t*>(s.sc_dev), p->k};
+    if (int rc = launch_pick(c, nq, RetryRule{in, static_cast<int32_t*>(s.ret_dev)}, static_cast<int32_t*>(s.list_dev), static_cast<int32_t*>(s.lcnt_dev))) return rc;
     FSP_HIP(hipMemcpyAsync(list_h + nq, s.lcnt_dev, 4, hipMemcpyDeviceToHost, c->stream));
     FSP_HIP(hipStreamSynchronize(c->stream));
     const int32_t n = list_h[nq];
@@ -205,22 +254,10 @@ int fspann_search_retry_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     CHECK_CTX(c);
     int rc = check_retry_args(c, nq, q_dev, B, k, out_ids_dev, out_dist_dev, out_count_dev);
     if (rc || nq == 0) return rc;
-    RetryArea ra;
-    if ((rc = retry_area(c, nq, ra))) return rc;
-    int32_t* scored = scored_dev ? scored_dev : ra.scored;
-    int32_t* retried = retried_dev ? retried_dev : ra.retried;
-    // pass 1: fspann_search_store_dev with the caller's probes
-    if ((rc = fspann_search_store_dev(c, nq, q_dev, q_dtype, probe_override, B, k, out_ids_dev, out_dist_dev, out_count_dev, scored,
-                                      sel_ids_dev, sel_count_dev, bad_dev))) return rc;
-    SearchArea sa;
-    if (!search_area(c, nq, B, sel_ids_dev, sel_count_dev, bad_dev, sa)) return fail(FSPANN_E_STATE, "search work area missing");
-    hipLaunchKernelGGL(retry_pick_kernel, dim3(1), dim3(kPickThreads), 0, c->stream, nq, k, sa.bad, sa.cnt, out_count_dev, scored, retried, ra.list, ra.count);
-    FSP_HIP(hipGetLastError());
-    // pass 2 with 10 probes (QSI:333) over the listed queries only.  Pass 1 at 10 effective probes already is what pass 2 would
-    // compute (same codes, same Route, same store): retried says 1 and nothing runs again.
-    if (effective_probes(c, probe_override) == effective_probes(c, 10)) return FSPANN_OK;
-    if ((rc = route_list_dev(c, nq, sa.codes, 10, B, sa.sel, sa.cnt, ra.list, ra.count))) return rc;
-    return refine_store_list(c, nq, q_dev, q_dtype, B, sa.sel, sa.cnt, k, out_ids_dev, out_dist_dev, out_count_dev, scored, ra.list, ra.count);
+    SearchBufs s;
+    if ((rc = retry_bufs(c, nullptr, nq, q_dev, q_dtype, B, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev, sel_ids_dev, sel_count_dev, bad_dev, retried_dev, s)))
+        return rc;
+    return search_retry_passes(c, s, probe_override);
 }
 
 int fspann_search_retry_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype, int probe_override, int64_t B, int k,
@@ -231,80 +268,21 @@ int fspann_search_retry_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev,
     if (int rc = refuse_row_only(q_dtype, "q_dtype")) return rc;     // (whether or not a query is left to finish)
     int rc = check_retry_args(c, nq, q_dev, B, k, out_ids_dev, out_dist_dev, out_count_dev);
     if (rc || nq == 0) return rc;
-    SearchArea sa;
-    if (!search_area(c, nq, B, sel_ids_dev, sel_count_dev, bad_dev, sa) || !c->ws_retry.p ||
-        c->ws_retry.bytes < 3 * ((static_cast<size_t>(nq) * 4 + 255) & ~size_t(255)) + 256)
-        return fail(FSPANN_E_STATE, "no fspann_search_retry_dev call of this size precedes");
-    RetryArea ra;
-    if ((rc = retry_area(c, nq, ra))) return rc;
-    int32_t* scored = scored_dev ? scored_dev : ra.scored;
-    int32_t* retried = retried_dev ? retried_dev : ra.retried;
+    SearchBufs s;
+    if ((rc = retry_bufs(c, "fspann_search_retry_dev", nq, q_dev, q_dtype, B, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev, sel_ids_dev, sel_count_dev, bad_dev,
+                         retried_dev, s))) return rc;
     return guarded([&]() -> int {
-        const size_t n4 = static_cast<size_t>(nq) * 4;
-        FSP_HIP(hipStreamSynchronize(c->stream));
-        std::vector<int32_t> cnt(static_cast<size_t>(nq));
-        FSP_HIP(hipMemcpy(cnt.data(), sa.cnt, n4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> cnt;
         bool any = false;
-        for (int64_t i = 0; i < nq && !any; i++) any = cnt[i] == kRouteUnmodelled;
+        if (int r = flagged_counts(c, s, cnt, &any)) return r;
         if (!any) return FSPANN_OK;
         std::vector<int32_t> ret(static_cast<size_t>(nq));
-        FSP_HIP(hipMemcpy(ret.data(), retried, n4, hipMemcpyDeviceToHost));
+        FSP_HIP(hipMemcpy(ret.data(), s.retried, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost));
         std::vector<int64_t> g1, g2;                 // flagged in pass 1 (never picked), flagged in pass 2
         for (int64_t i = 0; i < nq; i++)
             if (cnt[i] == kRouteUnmodelled) (ret[i] ? g2 : g1).push_back(i);
-        const bool same = effective_probes(c, probe_override) == effective_probes(c, 10);
-        int64_t done = 0, left = 0, d1 = 0;
-        auto rescore = [&](const std::vector<int64_t>& qs) -> int {
-            if (qs.empty()) return FSPANN_OK;
-            std::vector<int32_t> l(qs.begin(), qs.end());
-            const int32_t n = static_cast<int32_t>(l.size());
-            FSP_HIP(hipMemcpy(ra.list, l.data(), l.size() * 4, hipMemcpyHostToDevice));
-            FSP_HIP(hipMemcpy(ra.count, &n, 4, hipMemcpyHostToDevice));
-            int r = refine_store_list(c, nq, q_dev, q_dtype, B, sa.sel, sa.cnt, k, out_ids_dev, out_dist_dev, out_count_dev, scored, ra.list, ra.count);
-            if (r) return r;
-            FSP_HIP(hipStreamSynchronize(c->stream));
-            return FSPANN_OK;
-        };
-        // pass 1's flagged queries: finished with pass 1's probes and scored; the short ones go on to their pass 2
-        int r = resolve_queries(c, g1, sa.codes, probe_override, static_cast<int32_t>(B), B, sa.sel, nullptr, sa.cnt, nullptr, nullptr, &d1, &left);
-        if (r) return r;
-        done += d1;
-        if ((r = rescore(g1))) return r;
-        std::vector<int64_t> again;
-        if (!g1.empty()) {
-            std::vector<int32_t> bad(n4 / 4), oc(n4 / 4), sc(n4 / 4);
-            FSP_HIP(hipMemcpy(bad.data(), sa.bad, n4, hipMemcpyDeviceToHost));
-            FSP_HIP(hipMemcpy(oc.data(), out_count_dev, n4, hipMemcpyDeviceToHost));
-            FSP_HIP(hipMemcpy(sc.data(), scored, n4, hipMemcpyDeviceToHost));
-            FSP_HIP(hipMemcpy(cnt.data(), sa.cnt, n4, hipMemcpyDeviceToHost));
-            for (int64_t i : g1)
-                if (bad[i] == 0 && cnt[i] >= 0 && sc[i] > 0 && (oc[i] < k || static_cast<int64_t>(sc[i]) < 10 * static_cast<int64_t>(k))) {
-                    again.push_back(i);
-                    const int32_t one = 1;
-                    FSP_HIP(hipMemcpy(retried + i, &one, 4, hipMemcpyHostToDevice));
-                }
-        }
-        std::vector<int64_t> s2 = g2;
-        if (!again.empty() && !same) {
-            // their pass 2 on the device: Route with 10 probes over them; what it flags joins pass 2's flagged queries
-            std::vector<int32_t> l(again.begin(), again.end());
-            const int32_t n = static_cast<int32_t>(l.size());
-            FSP_HIP(hipMemcpy(ra.list, l.data(), l.size() * 4, hipMemcpyHostToDevice));
-            FSP_HIP(hipMemcpy(ra.count, &n, 4, hipMemcpyHostToDevice));
-            if ((r = route_list_dev(c, nq, sa.codes, 10, B, sa.sel, sa.cnt, ra.list, ra.count))) return r;
-            FSP_HIP(hipStreamSynchronize(c->stream));
-            FSP_HIP(hipMemcpy(cnt.data(), sa.cnt, n4, hipMemcpyDeviceToHost));
-            for (int64_t i : again)
-                if (cnt[i] == kRouteUnmodelled) g2.push_back(i);
-            std::sort(g2.begin(), g2.end());
-            s2.insert(s2.end(), again.begin(), again.end());
-            std::sort(s2.begin(), s2.end());
-        }
-        // pass 2's flagged queries: finished with 10 probes, then every query of a host-side pass 2 is scored
-        int64_t d2 = 0, left2 = 0;
-        if ((r = resolve_queries(c, g2, sa.codes, 10, static_cast<int32_t>(B), B, sa.sel, nullptr, sa.cnt, nullptr, nullptr, &d2, &left2))) return r;
-        done += d2;
-        if ((r = rescore(s2))) return r;
+        int64_t done = 0;
+        if (int r = finish_flagged(c, s, probe_override, g1, g2, &done)) return r;
         if (resolved) *resolved = done;
         return FSPANN_OK;
     });

@@ -243,7 +243,8 @@ int prepare_route(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int prob
     return FSPANN_OK;
 }
 
-// kernel 1 of the unfused route: search + probe order, one lane group per (query, table)
+// kernel 1 of the unfused route: search + probe order, one lane group per (query, table); p.qlist set: over the listed queries
+// (the launch is sized for the batch)
 int launch_route_probe(fspann_ctx* c, const RouteParams& p, const RoutePlan& pl) {
     int G = 64;
     while (G > 2 && G / 2 >= 2 * pl.P - 1 && G / 2 >= 16) G >>= 1;  // >= 16 lanes per table: 3-4 search rounds
@@ -251,9 +252,30 @@ int launch_route_probe(fspann_ctx* c, const RouteParams& p, const RoutePlan& pl)
     const int64_t nitems = p.nq * c->TD;
     const unsigned grid1 = static_cast<unsigned>((nitems + gpb - 1) / gpb);
     const size_t lds1 = static_cast<size_t>(gpb) * (2 * pl.P - 1) * 12;
-    hipLaunchKernelGGL(route_probe_kernel, dim3(grid1), dim3(kProbeThreads), lds1, c->stream, p, p.probe_g, p.nprobe_g, G);
+    auto probe = p.qlist ? route_probe_list_kernel : route_probe_kernel;
+    hipLaunchKernelGGL(probe, dim3(grid1), dim3(kProbeThreads), lds1, c->stream, p, p.probe_g, p.nprobe_g, G);
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
+}
+
+// the bounded select, one build per size class, over the batch or (p.qlist set) the listed queries
+int launch_bounded_select(fspann_ctx* c, const RoutePlan& pl, const RouteParams& p) {
+    const bool list = p.qlist != nullptr;
+    auto go = [&](auto lk, bool big) -> int {      // big: the size class plans with more than the default 64 KB of LDS
+        if (big) if (int rc = raise_lds_ceiling(c, lk, 159 * 1024)) return rc;
+        hipLaunchKernelGGL(lk, dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
+        FSP_HIP(hipGetLastError());
+        return FSPANN_OK;
+    };
+    if (pl.lz_entries == 512) {
+        if (list) return go(route_select_lazy_list_kernel<kLzThreads, 512, false>, false);
+        // (the shape of BASELINE configs #2 / #3 — 16 tables x 5 probes, blocks of 64 — has a build with the shape as constants)
+        if (c->knob_shape_spec && c->TD == 16 && pl.P == 5 && pl.S == 64 && c->W == 1 && c->rec_words == 4 && (p.probe_G == 16 || p.probe_G == 0))
+            return go(route_select_lazy_kernel<kLzThreads, 512, false, 16, 5>, false);
+        return go(route_select_lazy_kernel<kLzThreads, 512, false>, false);
+    }
+    if (pl.lz_entries == 2048) return list ? go(route_select_lazy_list_kernel<kLzThreads, 2048, true>, true) : go(route_select_lazy_kernel<kLzThreads, 2048, true>, true);
+    return list ? go(route_select_lazy_list_kernel<kLzThreads, kLzEntriesMax, true>, true) : go(route_select_lazy_kernel<kLzThreads, kLzEntriesMax, true>, true);
 }
 
 // the full select (every query, or — qcount / qlist set — the queries the bounded select handed over)
@@ -274,9 +296,12 @@ int launch_full_select(fspann_ctx* c, const RoutePlan& pl, const RouteParams& p)
 // fspann_route_dev.  deferred (optional): when the bounded select runs, the launch that finishes the queries it hands over — none,
 // normally — is NOT issued; its plan and parameters are returned instead and the caller issues it (launch_full_select) once it has
 // seen a PENDING count (fspann_route's calls of a handful of queries: one launch less in front of the synchronisation).
+// qlist / qcount (device; the retry passes): Route over the queries qlist[0 .. *qcount) only, each at its own index; the launches are
+// sized for nq and the count is read on the device.
 int route_dev_impl(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int probe_override, int32_t limit,
                    int64_t cap, int32_t* ids_dev, int32_t* score_dev, int32_t* count_dev, int32_t* kept_dev,
-                   int32_t* raw_seen_dev, RoutePlan* deferred_pl = nullptr, RouteParams* deferred_p = nullptr, bool* deferred = nullptr) {
+                   int32_t* raw_seen_dev, RoutePlan* deferred_pl = nullptr, RouteParams* deferred_p = nullptr, bool* deferred = nullptr,
+                   const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
     if (deferred) *deferred = false;
     if (!c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");  // PIS:594
     if (nq < 0) return fail(FSPANN_E_ARG, "nq < 0");
@@ -286,31 +311,23 @@ int route_dev_impl(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int pro
     bool fused = false;
     int rc = prepare_route(c, nq, codes_dev, probe_override, limit, cap, ids_dev, score_dev, count_dev, kept_dev, raw_seen_dev, &pl, &p, &fused);
     if (rc) return rc;
+    p.qlist = qlist; p.qcount = qcount;
     if (!fused && (rc = launch_route_probe(c, p, pl))) return rc;
     c->last_route_lazy = pl.lazy;
     if (pl.lazy) {
-        if (pl.lz_entries == 512) {
-            // (the shape of BASELINE configs #2 / #3 — 16 tables x 5 probes, blocks of 64 — has a build with the shape as constants)
-            if (c->knob_shape_spec && c->TD == 16 && pl.P == 5 && pl.S == 64 && c->W == 1 && c->rec_words == 4 && (p.probe_G == 16 || p.probe_G == 0))
-                hipLaunchKernelGGL((route_select_lazy_kernel<kLzThreads, 512, false, 16, 5>), dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
-            else
-                hipLaunchKernelGGL((route_select_lazy_kernel<kLzThreads, 512, false>), dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
-        } else if (pl.lz_entries == 2048) {
-            auto lk = route_select_lazy_kernel<kLzThreads, 2048, true>;
-            if ((rc = raise_lds_ceiling(c, lk, 159 * 1024))) return rc;
-            hipLaunchKernelGGL(lk, dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
-        } else {
-            auto lk = route_select_lazy_kernel<kLzThreads, kLzEntriesMax, true>;
-            if ((rc = raise_lds_ceiling(c, lk, 159 * 1024))) return rc;
-            hipLaunchKernelGGL(lk, dim3(pl.lz_grid), dim3(kLzThreads), pl.lz_lds_bytes, c->stream, p);
-        }
-        FSP_HIP(hipGetLastError());
+        if ((rc = launch_bounded_select(c, pl, p))) return rc;
         // queries the bounded select handed over (none, normally): the full select over the overflow list
         p.qcount = p.ovf_count; p.qlist = p.ovf_list;
         pl.grid = std::min(pl.grid, 32);    // normally nothing to do: keep the launch small
         if (deferred_pl && deferred_p && deferred) { *deferred_pl = pl; *deferred_p = p; *deferred = true; return FSPANN_OK; }
     }
     return launch_full_select(c, pl, p);
+}
+
+// Route with limit = cap = B over the queries qlist[0 .. *qcount) only.
+int route_list_dev(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int probe_override, int64_t B, int32_t* sel, int32_t* cnt,
+                   const int32_t* qlist, const int32_t* qcount) {
+    return route_dev_impl(c, nq, codes_dev, probe_override, static_cast<int32_t>(B), B, sel, nullptr, cnt, nullptr, nullptr, nullptr, nullptr, nullptr, qlist, qcount);
 }
 
 }  // namespace

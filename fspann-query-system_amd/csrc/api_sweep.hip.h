@@ -1,45 +1,29 @@
 // api_sweep.hip.h — include/fspann_sweep.h: Refine and QueryServiceImpl.search at several refinement limits in one pass
 // (fspann_refine_sweep_dev / fspann_refine_store_sweep_dev / fspann_search_sweep_dev / fspann_search_sweep_finish_dev).
 // Kernels in refine_sweep.hip.h; the argument why one pass is exact, the design and the measurements: DESIGN.md 3.3i.
-// Part of the single translation unit fspann_api.hip (included there, last); product code, no CPU fallback.
+// Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
 #include "../../include/fspann_sweep.h"
 
 namespace {
 
 // Work area of a sweep call: the keys [nq][kpitch], the clipped counts, pass 1's Route counts, each query's largest retried limit,
-// the pick list and its count, and retried / scored / unique [nl][nq] for the outputs the caller does not ask for.
+// the pick list and its count, and retried / scored [nl][nq] for the outputs the caller does not ask for.
 struct SweepArea {
     uint64_t* keys;
     int64_t kpitch;
     int32_t *clip, *cnt1, *cap_q, *list, *count, *retried, *scored;
+    size_t lay(void* base, int64_t nq, int nchunks, int nl) {
+        Carver w(base);
+        kpitch = static_cast<int64_t>(nchunks) * kRefRows;
+        keys = w.take<uint64_t>(static_cast<size_t>(nq) * kpitch * 8);
+        for (int32_t** p : {&clip, &cnt1, &cap_q, &list}) *p = w.take<int32_t>(static_cast<size_t>(nq) * 4);
+        count = w.take<int32_t>(4);
+        retried = w.take<int32_t>(static_cast<size_t>(nq) * nl * 4);
+        scored = w.take<int32_t>(static_cast<size_t>(nq) * nl * 4);
+        return w.off;
+    }
 };
-
-size_t sweep_area_bytes(int64_t nq, int nchunks, int nl) {
-    const size_t kb = (static_cast<size_t>(nq) * nchunks * kRefRows * 8 + 255) & ~size_t(255);
-    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
-    const size_t pb = (static_cast<size_t>(nq) * nl * 4 + 255) & ~size_t(255);
-    return kb + 4 * nb + 256 + 2 * pb;
-}
-
-int sweep_area(fspann_ctx* c, int64_t nq, int nchunks, int nl, SweepArea& s) {
-    const size_t kb = (static_cast<size_t>(nq) * nchunks * kRefRows * 8 + 255) & ~size_t(255);
-    const size_t nb = (static_cast<size_t>(nq) * 4 + 255) & ~size_t(255);
-    const size_t pb = (static_cast<size_t>(nq) * nl * 4 + 255) & ~size_t(255);
-    int rc = ensure(c, c->ws_sweep, sweep_area_bytes(nq, nchunks, nl));
-    if (rc) return rc;
-    char* w = static_cast<char*>(c->ws_sweep.p);
-    s.keys = reinterpret_cast<uint64_t*>(w);
-    s.kpitch = static_cast<int64_t>(nchunks) * kRefRows;
-    s.clip = reinterpret_cast<int32_t*>(w + kb);
-    s.cnt1 = reinterpret_cast<int32_t*>(w + kb + nb);
-    s.cap_q = reinterpret_cast<int32_t*>(w + kb + 2 * nb);
-    s.list = reinterpret_cast<int32_t*>(w + kb + 3 * nb);
-    s.count = reinterpret_cast<int32_t*>(w + kb + 4 * nb);
-    s.retried = reinterpret_cast<int32_t*>(w + kb + 4 * nb + 256);
-    s.scored = reinterpret_cast<int32_t*>(w + kb + 4 * nb + 256 + pb);
-    return FSPANN_OK;
-}
 
 // limits / nl / k of every sweep call (include/fspann_sweep.h): the checked copy travels in kernel arguments.
 int sweep_check(const int64_t* limits, int nl, int k, SweepLimits& lim) {
@@ -57,50 +41,32 @@ int sweep_check(const int64_t* limits, int nl, int k, SweepLimits& lim) {
     return FSPANN_OK;
 }
 
-// The scan with the key epilogue: launch_refine_dc's choice between the stream and one workgroup per chunk, without partial lists,
-// hand-over or kernel-attached timing.  B = the row pitch (stride); nchunks covers the largest limit only.
-template <typename TC, typename TQ, int DC, bool GATHER>
-int launch_refine_keys_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids, const int32_t* cand_count, int nchunks,
-                          uint64_t* keys, const int32_t* qlist, const int32_t* qcount) {
-    constexpr int VN = VecOf<TC>::N;
-    const int d = c->cfg.dim;
-    const bool vec = (d % VN == 0) && ((reinterpret_cast<uintptr_t>(cand) & 15) == 0);
-    const size_t lds = std::max<size_t>(static_cast<size_t>(kRefRows) * (vec ? DC + VN : DC + 1) * sizeof(TC), static_cast<size_t>(kRefRows) * 16);
-    const unsigned grid = static_cast<unsigned>(nq * nchunks);
-    const RefineArgs<TC, TQ> ra{q, cand, GATHER ? c->store_n : 0, B, d, cand_ids, cand_count, 0, nchunks, nullptr, nullptr, nullptr, nullptr,
-                                reinterpret_cast<RefinePartial*>(keys), nullptr, 0, 0, c->dbg_route};
-    const int stream_wgs = (c->knob_refine_stream >= 0) ? std::min(c->knob_refine_stream, GATHER ? 3 : 4) : (GATHER ? 3 : 4);
-    bool done = false;
-    if constexpr (DC * sizeof(TC) == 128) if (vec && stream_wgs > 0) {
-        const unsigned sgrid = static_cast<unsigned>(std::min<int64_t>(nq * nchunks, static_cast<int64_t>(c->num_cus) * stream_wgs));
-        if (qlist) hipLaunchKernelGGL((refine_stream_keys_kernel<TC, TQ, DC, GATHER, true>), dim3(sgrid), dim3(kRefRows), lds, c->stream, ra, nq, qlist, qcount);
-        else hipLaunchKernelGGL((refine_stream_keys_kernel<TC, TQ, DC, GATHER, false>), dim3(sgrid), dim3(kRefRows), lds, c->stream, ra, nq, qlist, qcount);
-        done = true;
-    }
-    if (!done) {
-        auto kern = vec ? refine_scan_keys_kernel<TC, TQ, DC, true, GATHER> : refine_scan_keys_kernel<TC, TQ, DC, false, GATHER>;
-        if (lds > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, lds)) return rc;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
-    }
-    FSP_HIP(hipGetLastError());
-    return FSPANN_OK;
-}
-
+// The scan with the key epilogue under launch_refine_dc's plan (scan_plan), without partial lists, hand-over or kernel-attached
+// timing, and the touched-record set behind it: the rows this scan scores (the clipped counts).  B = the row pitch (stride); nchunks
+// covers the largest limit only.
 template <typename TC, typename TQ, bool GATHER>
 int launch_refine_keys_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids, const int32_t* cand_count, int nchunks,
                          uint64_t* keys, const int32_t* qlist, const int32_t* qcount) {
-    auto run = [&](auto dc) {
-        return launch_refine_keys_dc<TC, TQ, decltype(dc)::value, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, nchunks, keys, qlist, qcount);
-    };
-    constexpr int DC0 = 128 / static_cast<int>(sizeof(TC));     // dims per tile, as launch_refine_t
-    const int dc_env = c->knob_refine_dc;
-    int rc;
-    if constexpr (sizeof(TC) < 4) rc = run(std::integral_constant<int, DC0>{});
-    else if (dc_env == DC0 * 2) rc = run(std::integral_constant<int, DC0 * 2>{});
-    else if (dc_env == DC0 * 4) rc = run(std::integral_constant<int, DC0 * 4>{});
-    else rc = run(std::integral_constant<int, DC0>{});
+    int rc = with_tile_width<TC>(c, [&](auto dc) -> int {
+        constexpr int DC = decltype(dc)::value;
+        const ScanPlan sp = scan_plan<TC, DC, GATHER>(c, nq, cand, nchunks);
+        const RefineArgs<TC, TQ> ra{q, cand, GATHER ? c->store_n : 0, B, c->cfg.dim, cand_ids, cand_count, 0, nchunks, nullptr, nullptr, nullptr, nullptr,
+                                    reinterpret_cast<RefinePartial*>(keys), nullptr, 0, 0, c->dbg_route};
+        bool streamed = false;
+        if constexpr (DC * sizeof(TC) == 128) if (sp.stream) {
+            auto kern = qlist ? refine_stream_keys_kernel<TC, TQ, DC, GATHER, true> : refine_stream_keys_kernel<TC, TQ, DC, GATHER, false>;
+            hipLaunchKernelGGL(kern, dim3(sp.sgrid(nq * nchunks)), dim3(kRefRows), sp.lds, c->stream, ra, nq, qlist, qcount);
+            streamed = true;
+        }
+        if (!streamed) {
+            auto kern = sp.vec ? refine_scan_keys_kernel<TC, TQ, DC, true, GATHER> : refine_scan_keys_kernel<TC, TQ, DC, false, GATHER>;
+            if (sp.lds > 64 * 1024) if (int r = raise_lds_ceiling(c, kern, sp.lds)) return r;
+            hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(kRefRows), sp.lds, c->stream, ra, qlist, qcount);
+        }
+        FSP_HIP(hipGetLastError());
+        return FSPANN_OK;
+    });
     if (rc) return rc;
-    // the touched-record set: the rows this scan scores (the clipped counts), marked behind it
     return touch_mark<TC, TQ, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, qlist, qcount);
 }
 
@@ -154,21 +120,20 @@ int refine_sweep_call(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
     const int nchunks = static_cast<int>((bmax + kRefRows - 1) / kRefRows);
     if (nq * nchunks >= (int64_t(1) << 31)) return fail(FSPANN_E_ARG, "nq x limit too large for one sweep");
     SweepArea sw;
-    if ((rc = sweep_area(c, nq, nchunks, nl, sw))) return rc;
+    if ((rc = area_grow(c, c->ws_sweep, sw, nq, nchunks, nl))) return rc;
     if ((rc = sweep_clip(c, nq, cand_count_dev, static_cast<int32_t>(bmax), nullptr, sw.clip))) return rc;
     return sweep_refine<GATHER>(c, sw, nchunks, row_dtype, q_dtype, nq, q_dev, rows, stride, cand_ids_dev, lim, k, out_ids_dev, out_dist_dev, out_count_dev,
                                 scored_dev, nullptr, nullptr, nullptr);
 }
 
-// What a search sweep call and its finish call share: the checked arguments, Route's work area (fspann_search_store_dev's layout at
-// Bmax), the sweep's own, and the outputs with the area's buffers where the caller passed none.
+// What a search sweep call and its finish call share: the checked arguments, the sweep's work area, and the buffers of the search
+// (Route's work area in fspann_search_store_dev's layout at Bmax; the sweep area's pick list and planes where the caller passed none).
 struct SweepCall {
     SweepLimits lim;
     int64_t bmax;
     int nchunks;
-    SearchArea sa;
     SweepArea sw;
-    int32_t *scored, *retried;
+    SearchBufs b;
 };
 
 int sweep_search_args(fspann_ctx* c, int64_t nq, const void* q_dev, const int64_t* limits, int nl, int k, int32_t* out_ids_dev, double* out_dist_dev,
@@ -185,9 +150,33 @@ int sweep_search_args(fspann_ctx* c, int64_t nq, const void* q_dev, const int64_
     return FSPANN_OK;
 }
 
+// The work areas of a checked call, grown to size or (held) as the preceding fspann_search_sweep_dev left them, and its buffers.
+int sweep_bufs(fspann_ctx* c, bool held, int64_t nq, const void* q_dev, int q_dtype, int nl, int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev,
+               int32_t* scored_dev, int32_t* bad_dev, int32_t* retried_dev, SweepCall& s) {
+    SearchArea sa;
+    if (held) {
+        if (!area_held(c->ws_sweep, s.sw, nq, s.nchunks, nl) || !search_area(c, nq, s.bmax, nullptr, nullptr, bad_dev, sa))
+            return fail(FSPANN_E_STATE, "no fspann_search_sweep_dev call of this size precedes");
+    } else {
+        int rc;
+        if ((rc = search_area_grow(c, nq, s.bmax, nullptr, nullptr, bad_dev, sa)) || (rc = area_grow(c, c->ws_sweep, s.sw, nq, s.nchunks, nl))) return rc;
+    }
+    s.b = search_bufs(nq, q_dev, q_dtype, s.bmax, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev, retried_dev, sa, s.sw);
+    return FSPANN_OK;
+}
+
+// Scores the queries of the pick list through the sweep, in place: on every plane, or (masked) on their retried planes only and up
+// to their largest retried limit — the rows nobody asked for are neither read nor marked.
+int sweep_score_list(fspann_ctx* c, const SweepCall& s, bool masked) {
+    const SearchBufs& b = s.b;
+    if (int rc = sweep_clip(c, b.nq, b.sa.cnt, static_cast<int32_t>(s.bmax), masked ? s.sw.cap_q : nullptr, s.sw.clip)) return rc;
+    return sweep_refine<true>(c, s.sw, s.nchunks, c->store_dtype, b.q_dtype, b.nq, b.q, c->d_store, s.bmax, b.sa.sel, s.lim, b.k, b.out_ids, b.out_dist, b.out_count,
+                              b.scored, masked ? b.retried : nullptr, b.list, b.count);
+}
+
 int sweep_unique(fspann_ctx* c, int64_t nq, const SweepCall& s, bool pass2, int32_t* unique_dev) {
     if (!unique_dev) return FSPANN_OK;
-    hipLaunchKernelGGL(sweep_unique_kernel, dim3(static_cast<unsigned>((nq + 255) / 256)), dim3(256), 0, c->stream, nq, s.lim, s.sw.cnt1, s.sa.cnt, s.retried,
+    hipLaunchKernelGGL(sweep_unique_kernel, dim3(static_cast<unsigned>((nq + 255) / 256)), dim3(256), 0, c->stream, nq, s.lim, s.sw.cnt1, s.b.sa.cnt, s.b.retried,
                        pass2 ? 1 : 0, unique_dev);
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
@@ -222,32 +211,24 @@ int fspann_search_sweep_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     int rc = sweep_search_args(c, nq, q_dev, limits, nl, k, out_ids_dev, out_dist_dev, out_count_dev, s);
     if (rc || nq == 0) return rc;
     c->sweep_nq = 0;                                   // (no finish call may follow a call that failed half-way)
-    if ((rc = ensure(c, c->ws_search, search_area_bytes(c, nq, s.bmax)))) return rc;
-    (void)search_area(c, nq, s.bmax, nullptr, nullptr, bad_dev, s.sa);
-    if ((rc = sweep_area(c, nq, s.nchunks, nl, s.sw))) return rc;
-    s.scored = scored_dev ? scored_dev : s.sw.scored;
-    s.retried = retried_dev ? retried_dev : s.sw.retried;
+    if ((rc = sweep_bufs(c, false, nq, q_dev, q_dtype, nl, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev, bad_dev, retried_dev, s))) return rc;
+    const SearchBufs& b = s.b;
     const int32_t bmax32 = static_cast<int32_t>(s.bmax);
     // pass 1: one encode, one Route at the largest limit with the caller's probes, one sweep refine over the store
-    if ((rc = fspann_encode_dev(c, nq, q_dev, q_dtype, const_cast<uint64_t*>(s.sa.codes), nullptr, s.sa.bad))) return rc;
-    if ((rc = fspann_route_dev(c, nq, s.sa.codes, probe_override, bmax32, s.bmax, s.sa.sel, nullptr, s.sa.cnt, nullptr, nullptr))) return rc;
-    FSP_HIP(hipMemcpyAsync(s.sw.cnt1, s.sa.cnt, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = sweep_clip(c, nq, s.sa.cnt, bmax32, nullptr, s.sw.clip))) return rc;
-    if ((rc = sweep_refine<true>(c, s.sw, s.nchunks, c->store_dtype, q_dtype, nq, q_dev, c->d_store, s.bmax, s.sa.sel, s.lim, k, out_ids_dev, out_dist_dev,
-                                 out_count_dev, s.scored, nullptr, nullptr, nullptr))) return rc;
+    if ((rc = fspann_encode_dev(c, nq, q_dev, q_dtype, const_cast<uint64_t*>(b.sa.codes), nullptr, b.sa.bad))) return rc;
+    if ((rc = fspann_route_dev(c, nq, b.sa.codes, probe_override, bmax32, s.bmax, b.sa.sel, nullptr, b.sa.cnt, nullptr, nullptr))) return rc;
+    FSP_HIP(hipMemcpyAsync(s.sw.cnt1, b.sa.cnt, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = sweep_clip(c, nq, b.sa.cnt, bmax32, nullptr, s.sw.clip))) return rc;
+    if ((rc = sweep_refine<true>(c, s.sw, s.nchunks, c->store_dtype, q_dtype, nq, q_dev, c->d_store, s.bmax, b.sa.sel, s.lim, k, out_ids_dev, out_dist_dev,
+                                 out_count_dev, b.scored, nullptr, nullptr, nullptr))) return rc;
     // QSI's retry predicate per (query, limit); the queries with any retried limit are listed
-    hipLaunchKernelGGL(sweep_pick_kernel, dim3(1), dim3(kSweepPickThreads), 0, c->stream, nq, k, s.lim, s.sa.bad, s.sa.cnt, out_count_dev, s.scored, s.retried,
-                       s.sw.cap_q, s.sw.list, s.sw.count);
-    FSP_HIP(hipGetLastError());
+    if ((rc = launch_pick(c, nq, SweepRule{pick_in(b), s.lim, nq, b.retried, s.sw.cap_q}, b.list, b.count))) return rc;
     c->sweep_nq = nq; c->sweep_bmax = s.bmax; c->sweep_nl = nl; c->sweep_k = k;
     // pass 2 with 10 probes (QSI:333) over the listed queries; pass 1 at 10 effective probes already is what it would compute
     const bool same = effective_probes(c, probe_override) == effective_probes(c, 10);
     if (!same) {
-        if ((rc = route_list_dev(c, nq, s.sa.codes, 10, s.bmax, s.sa.sel, s.sa.cnt, s.sw.list, s.sw.count))) return rc;
-        // a query's pass 2 is scored up to its largest retried limit: the rows nobody asked for are neither read nor marked
-        if ((rc = sweep_clip(c, nq, s.sa.cnt, bmax32, s.sw.cap_q, s.sw.clip))) return rc;
-        if ((rc = sweep_refine<true>(c, s.sw, s.nchunks, c->store_dtype, q_dtype, nq, q_dev, c->d_store, s.bmax, s.sa.sel, s.lim, k, out_ids_dev, out_dist_dev,
-                                     out_count_dev, s.scored, s.retried, s.sw.list, s.sw.count))) return rc;
+        if ((rc = route_list_dev(c, nq, b.sa.codes, 10, s.bmax, b.sa.sel, b.sa.cnt, b.list, b.count))) return rc;
+        if ((rc = sweep_score_list(c, s, true))) return rc;
     }
     return sweep_unique(c, nq, s, !same, unique_dev);
 }
@@ -261,92 +242,34 @@ int fspann_search_sweep_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev,
     SweepCall s;
     int rc = sweep_search_args(c, nq, q_dev, limits, nl, k, out_ids_dev, out_dist_dev, out_count_dev, s);
     if (rc || nq == 0) return rc;
-    if (c->sweep_nq != nq || c->sweep_bmax != s.bmax || c->sweep_nl != nl || c->sweep_k != k || !c->ws_sweep.p ||
-        c->ws_sweep.bytes < sweep_area_bytes(nq, s.nchunks, nl) || !search_area(c, nq, s.bmax, nullptr, nullptr, bad_dev, s.sa))
-        return fail(FSPANN_E_STATE, "no fspann_search_sweep_dev call of this size precedes");
-    if ((rc = sweep_area(c, nq, s.nchunks, nl, s.sw))) return rc;
-    s.scored = scored_dev ? scored_dev : s.sw.scored;
-    s.retried = retried_dev ? retried_dev : s.sw.retried;
+    const bool held = c->sweep_nq == nq && c->sweep_bmax == s.bmax && c->sweep_nl == nl && c->sweep_k == k;
+    if (!held) return fail(FSPANN_E_STATE, "no fspann_search_sweep_dev call of this size precedes");
+    if ((rc = sweep_bufs(c, true, nq, q_dev, q_dtype, nl, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev, bad_dev, retried_dev, s))) return rc;
+    const SearchBufs& b = s.b;
     return guarded([&]() -> int {
-        const size_t n4 = static_cast<size_t>(nq) * 4;
-        const int32_t bmax32 = static_cast<int32_t>(s.bmax);
-        FSP_HIP(hipStreamSynchronize(c->stream));
-        std::vector<int32_t> cnt(static_cast<size_t>(nq));
-        FSP_HIP(hipMemcpy(cnt.data(), s.sa.cnt, n4, hipMemcpyDeviceToHost));
+        std::vector<int32_t> cnt;
         bool any = false;
-        for (int64_t i = 0; i < nq && !any; i++) any = cnt[i] == kRouteUnmodelled;
+        if (int r = flagged_counts(c, b, cnt, &any)) return r;
         if (!any) return FSPANN_OK;
         std::vector<int32_t> ret(static_cast<size_t>(nq) * nl);
-        FSP_HIP(hipMemcpy(ret.data(), s.retried, n4 * nl, hipMemcpyDeviceToHost));
+        FSP_HIP(hipMemcpy(ret.data(), b.retried, ret.size() * 4, hipMemcpyDeviceToHost));
         auto picked = [&](int64_t i) { for (int j = 0; j < nl; j++) if (ret[static_cast<size_t>(j) * nq + i]) return true; return false; };
         std::vector<int64_t> g1, g2;                 // flagged in pass 1 (never picked), flagged in pass 2
         for (int64_t i = 0; i < nq; i++)
             if (cnt[i] == kRouteUnmodelled) (picked(i) ? g2 : g1).push_back(i);
-        const bool same = effective_probes(c, probe_override) == effective_probes(c, 10);
-        int64_t done = 0, left = 0, d1 = 0;
-        // scores the queries qs through the sweep: every plane (masked = false) or their retried planes up to their largest retried limit
-        auto rescore = [&](const std::vector<int64_t>& qs, bool masked) -> int {
-            if (qs.empty()) return FSPANN_OK;
-            std::vector<int32_t> l(qs.begin(), qs.end());
-            const int32_t n = static_cast<int32_t>(l.size());
-            FSP_HIP(hipMemcpy(s.sw.list, l.data(), l.size() * 4, hipMemcpyHostToDevice));
-            FSP_HIP(hipMemcpy(s.sw.count, &n, 4, hipMemcpyHostToDevice));
-            int r = sweep_clip(c, nq, s.sa.cnt, bmax32, masked ? s.sw.cap_q : nullptr, s.sw.clip);
-            if (r) return r;
-            r = sweep_refine<true>(c, s.sw, s.nchunks, c->store_dtype, q_dtype, nq, q_dev, c->d_store, s.bmax, s.sa.sel, s.lim, k, out_ids_dev, out_dist_dev,
-                                   out_count_dev, s.scored, masked ? s.retried : nullptr, s.sw.list, s.sw.count);
-            if (r) return r;
-            FSP_HIP(hipStreamSynchronize(c->stream));
-            return FSPANN_OK;
-        };
-        // pass 1's flagged queries: finished at Bmax with pass 1's probes and scored at every limit; the short planes go on to pass 2
-        int r = resolve_queries(c, g1, s.sa.codes, probe_override, bmax32, s.bmax, s.sa.sel, nullptr, s.sa.cnt, nullptr, nullptr, &d1, &left);
-        if (r) return r;
-        done += d1;
-        if ((r = rescore(g1, false))) return r;
-        std::vector<int64_t> again;
-        if (!g1.empty()) {
-            std::vector<int32_t> bad(static_cast<size_t>(nq)), oc(static_cast<size_t>(nq) * nl), sc(static_cast<size_t>(nq) * nl);
-            FSP_HIP(hipMemcpy(bad.data(), s.sa.bad, n4, hipMemcpyDeviceToHost));
-            FSP_HIP(hipMemcpy(oc.data(), out_count_dev, n4 * nl, hipMemcpyDeviceToHost));
-            FSP_HIP(hipMemcpy(sc.data(), s.scored, n4 * nl, hipMemcpyDeviceToHost));
-            FSP_HIP(hipMemcpy(cnt.data(), s.sa.cnt, n4, hipMemcpyDeviceToHost));
-            for (int64_t i : g1) {
-                FSP_HIP(hipMemcpy(s.sw.cnt1 + i, &cnt[i], 4, hipMemcpyHostToDevice));      // (the count pass 1 ended on)
-                int32_t cap = 0;
-                for (int j = 0; j < nl; j++) {
-                    const size_t pl = static_cast<size_t>(j) * nq + i;
-                    const int32_t one = (bad[i] == 0 && cnt[i] >= 0 && sc[pl] > 0 && (oc[pl] < k || static_cast<int64_t>(sc[pl]) < 10 * static_cast<int64_t>(k))) ? 1 : 0;
-                    if (one) {
-                        cap = s.lim.v[j];
-                        FSP_HIP(hipMemcpy(s.retried + pl, &one, 4, hipMemcpyHostToDevice));
-                    }
-                }
+        // pass 1's flagged queries are finished at Bmax and scored at every limit; the short planes go on to pass 2, whose queries are
+        // scored on their retried planes
+        int64_t done = 0;
+        int r = finish_flagged(
+            c, b, nl, probe_override, g1, g2, &done, [&](bool masked) { return sweep_score_list(c, s, masked); },
+            [&](int64_t i, int32_t count, int last) -> int {
+                const int32_t cap = last >= 0 ? s.lim.v[last] : 0;
+                FSP_HIP(hipMemcpy(s.sw.cnt1 + i, &count, 4, hipMemcpyHostToDevice));      // (the count pass 1 ended on)
                 FSP_HIP(hipMemcpy(s.sw.cap_q + i, &cap, 4, hipMemcpyHostToDevice));
-                if (cap > 0) again.push_back(i);
-            }
-        }
-        std::vector<int64_t> s2 = g2;
-        if (!again.empty() && !same) {
-            // their pass 2 on the device: Route with 10 probes over them; what it flags joins pass 2's flagged queries
-            std::vector<int32_t> l(again.begin(), again.end());
-            const int32_t n = static_cast<int32_t>(l.size());
-            FSP_HIP(hipMemcpy(s.sw.list, l.data(), l.size() * 4, hipMemcpyHostToDevice));
-            FSP_HIP(hipMemcpy(s.sw.count, &n, 4, hipMemcpyHostToDevice));
-            if ((r = route_list_dev(c, nq, s.sa.codes, 10, s.bmax, s.sa.sel, s.sa.cnt, s.sw.list, s.sw.count))) return r;
-            FSP_HIP(hipStreamSynchronize(c->stream));
-            FSP_HIP(hipMemcpy(cnt.data(), s.sa.cnt, n4, hipMemcpyDeviceToHost));
-            for (int64_t i : again)
-                if (cnt[i] == kRouteUnmodelled) g2.push_back(i);
-            std::sort(g2.begin(), g2.end());
-            s2.insert(s2.end(), again.begin(), again.end());
-            std::sort(s2.begin(), s2.end());
-        }
-        // pass 2's flagged queries: finished with 10 probes, then every query of a host-side pass 2 is scored on its retried planes
-        int64_t d2 = 0, left2 = 0;
-        if ((r = resolve_queries(c, g2, s.sa.codes, 10, bmax32, s.bmax, s.sa.sel, nullptr, s.sa.cnt, nullptr, nullptr, &d2, &left2))) return r;
-        done += d2;
-        if ((r = rescore(s2, true))) return r;
+                return FSPANN_OK;
+            });
+        if (r) return r;
+        const bool same = effective_probes(c, probe_override) == effective_probes(c, 10);
         if ((r = sweep_unique(c, nq, s, !same, unique_dev))) return r;
         FSP_HIP(hipStreamSynchronize(c->stream));
         if (resolved) *resolved = done;

@@ -23,6 +23,7 @@
 #include "refine_sweep.hip.h"
 #include "route.hip.h"
 #include "route_lazy.hip.h"
+#include "search_pick.hip.h"
 #include "tick.hip.h"
 #include "touch.hip.h"
 #include "../host/route_replay.hpp"

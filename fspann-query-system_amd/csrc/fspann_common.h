@@ -192,10 +192,11 @@ struct fspann_ctx {
     size_t rt_used = 0;
     int rt_every = 1, rt_seen = 0;       // events go on every rt_every-th dispatch
     bool rt_on = false;
-    fspann::DevBuf ws_search;        // codes / F_q ids / counts of fspann_search_store_dev
-    fspann::DevBuf ws_retry;         // pick list, its count, retried / scored of fspann_search_retry_dev (api_retry.hip.h)
-    fspann::DevBuf ws_fallback;      // fallback list, its count, member / fellback flags of fspann_search_fallback_dev (api_eval.hip.h)
-    fspann::DevBuf ws_sweep;         // keys, clipped counts, pick list and planes of the sweep calls (api_sweep.hip.h)
+    // work areas of the search calls, each laid out once by its struct's lay() (Carver, api_common.hip.h)
+    fspann::DevBuf ws_search;        // SearchArea: codes / F_q ids / counts / bad of fspann_search_store_dev (api_common.hip.h)
+    fspann::DevBuf ws_retry;         // RetryArea: pick list, retried / scored, the list's count of fspann_search_retry_dev (api_retry.hip.h)
+    fspann::DevBuf ws_fallback;      // FallbackArea: fallback list, member / fellback flags, the list's count of fspann_search_fallback_dev (api_eval.hip.h)
+    fspann::DevBuf ws_sweep;         // SweepArea: keys, clipped counts, pass 1's counts, caps, pick list and planes of the sweep calls (api_sweep.hip.h)
     int64_t sweep_nq = 0, sweep_bmax = 0;   // the last fspann_search_sweep_dev: what its finish call must repeat (0: none)
     int sweep_nl = 0, sweep_k = 0;
     struct LdsCeiling { const void* kernel; size_t bytes; };

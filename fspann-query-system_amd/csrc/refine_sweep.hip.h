@@ -171,56 +171,7 @@ __global__ __launch_bounds__(kSweepThreads) void refine_prefix_topk_kernel(const
 }
 
 // ---- the search sweep (fspann_search_sweep_dev) ----------------------------------------------------------------------------
-
-// QSI's retry predicate (QSI:159, 293, 444-447; retry_wanted of api_retry.hip.h) per (query, limit): retried [nl][nq]; cap_q [q] =
-// the query's largest retried limit (0: none); the queries with any retried limit are listed, ascending.  One workgroup, wave w owns
-// a contiguous slice of the batch (retry_pick_kernel's scheme).
-constexpr int kSweepPickThreads = 1024;
-__global__ __launch_bounds__(kSweepPickThreads) void sweep_pick_kernel(int64_t nq, int k, SweepLimits lim, const int32_t* __restrict__ bad,
-                                                                       const int32_t* __restrict__ route_cnt, const int32_t* __restrict__ out_count,
-                                                                       const int32_t* __restrict__ scored, int32_t* __restrict__ retried,
-                                                                       int32_t* __restrict__ cap_q, int32_t* __restrict__ list, int32_t* __restrict__ count) {
-    constexpr int nwv = kSweepPickThreads / 64;
-    __shared__ int s_base[nwv + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t seg = ((nq + nwv - 1) / nwv + 63) & ~int64_t(63);
-    const int64_t lo = min(nq, wave * seg), hi = min(nq, lo + seg);
-    int n = 0;
-    for (int64_t i0 = lo; i0 < hi; i0 += 64) {
-        const int64_t i = i0 + lane;
-        int32_t cap = 0;
-        if (i < hi) {
-            const bool live = bad[i] == 0 && route_cnt[i] >= 0;
-            for (int j = 0; j < lim.n; j++) {
-                const int64_t pl = static_cast<int64_t>(j) * nq + i;
-                const int32_t sc = scored[pl];
-                const bool p = live && sc > 0 && (out_count[pl] < k || static_cast<int64_t>(sc) < 10 * static_cast<int64_t>(k));
-                retried[pl] = p ? 1 : 0;
-                if (p) cap = lim.v[j];
-            }
-            cap_q[i] = cap;
-        }
-        n += __popcll(__ballot(cap > 0));
-    }
-    if (lane == 0) s_base[wave] = n;
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int w = 0; w < nwv; w++) { const int x = s_base[w]; s_base[w] = acc; acc += x; }
-        s_base[nwv] = acc;
-        *count = acc;
-    }
-    __syncthreads();
-    int at = s_base[wave];
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int64_t i0 = lo; i0 < hi && at < s_base[wave + 1]; i0 += 64) {
-        const int64_t i = i0 + lane;
-        const bool p = i < hi && cap_q[i] > 0;
-        const unsigned long long m = __ballot(p);
-        if (p) list[at + __popcll(m & lt)] = static_cast<int32_t>(i);
-        at += __popcll(m);
-    }
-}
+// (QSI's retry predicate per (query, limit) and the list of the queries with any retried limit: SweepRule, search_pick.hip.h)
 
 // unique [nl][nq] = |F_q| of the pass plane j ended on, as the search at limits[j] reports it: min(count, limits[j]); a count still
 // flagged (-1) is passed on.  pass2: the retried planes ended on pass 2 (cnt2), the others — and all of them when pass 2 did not

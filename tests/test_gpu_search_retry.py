@@ -157,6 +157,28 @@ def test_large_batch_scattered_short_queries(pkg, oracle):
     _check(got, ref, B)
 
 
+@pytest.fixture(scope="module")
+def pick_scene(oracle):
+    """One scene and one oracle search of 1 025 queries (a search is per query: a batch of the first nq is the first nq rows).
+    Seed 10, chosen with the oracle: query 0 is retried, queries 64 and 1 024 are, and every prefix below holds both kinds."""
+    sc = _scene(oracle, B=128, fail=0.15, store_frac=0.95, seed=10)
+    Q = sc["rng"].standard_normal((1025, 16)).astype(np.float32)
+    return sc, Q, sc["oracle"].search(Q.astype(np.float64), 10, probe_override=2)
+
+
+@pytest.mark.parametrize("nq", [1, 63, 65, 1024, 1025])
+def test_pick_list_at_the_slice_boundaries(pkg, pick_scene, nq):
+    """The pick kernel gives each of its 16 waves a slice of roundup64(ceil(nq / 16)) queries: one query; one partial wave; one wave
+    and one query of the next; 16 full slices of 64; slices of 128 with query 1 024 alone in the ninth."""
+    sc, Q, full = pick_scene
+    ref = {k: v[:nq] for k, v in full.items()}
+    r = ref["metrics"][:, 4]
+    assert r.all() if nq == 1 else 0 < r.sum() < nq, r.sum()
+    with _ctx(pkg, sc) as ctx:
+        got = _run(ctx, Q[:nq], 128, 10, 2)
+    _check(got, ref, 128)
+
+
 def _spread_inv(s):
     s = np.asarray(s).astype(np.uint32)
     return (s ^ (s >> 16)).view(np.int32)

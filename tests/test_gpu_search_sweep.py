@@ -174,6 +174,31 @@ def test_planes_equal_the_separate_searches_and_the_oracle(pkg, oracle):
         assert np.array_equal(od.cpu().numpy().view(np.uint64), got["dist"].view(np.uint64))
 
 
+@pytest.fixture(scope="module")
+def pick_scene(oracle):
+    """One scene and the oracle's two planes of 1 025 queries (a search is per query: a batch of the first nq is the first nq rows).
+    Seed 32, chosen with the oracle: at limits 256 and 300 some queries retry on a plane and some on none, in either prefix below,
+    queries 64 and 1 024 are listed, and hundreds of queries retry on one plane only."""
+    limits = [256, 300]
+    sc = _scene(oracle, seed=32)
+    Q, _ = _queries(sc, nq=1025)
+    return sc, Q, limits, _oracle_planes(sc, Q, limits, K)
+
+
+@pytest.mark.parametrize("nq", [65, 1025])
+def test_pick_list_at_the_slice_boundaries(pkg, pick_scene, nq):
+    """The pick kernel's 16 waves own slices of roundup64(ceil(nq / 16)) queries: one wave and one query of the next; slices of 128
+    with query 1 024 alone in the ninth.  Listed = retried on any plane."""
+    sc, Q, limits, full = pick_scene
+    refs = [{key: v[:nq] for key, v in r.items()} for r in full]
+    R = np.array([r["metrics"][:, 4] for r in refs])
+    assert 0 < R.max(0).sum() < nq and R.max(0)[-1] and (R[0] != R[1]).any()
+    with _ctx(pkg, sc) as ctx:
+        got = _sweep(ctx, Q[:nq], limits, K, -1)
+    for j, lim in enumerate(limits):
+        _check_oracle(got, j, refs[j], ("oracle", lim))
+
+
 def test_ten_probes_already(pkg, oracle):
     """probe_override = 10: pass 2 is not run, the short planes are still reported retried"""
     sc = _scene(oracle)

@@ -48,6 +48,9 @@ def test_list_mode_kernels_are_built_for_gfx950(pkg):
     for k in ("retry_pick_kernel", "route_probe_list_kernel", "route_select_lazy_list_kernel", "refine_stream_list_kernel",
               "refine_merge_list_kernel"):
         assert k in names, k
+    # one pick kernel, one instantiation per rule: the retry, the fallback, the retry among the fallen-back, the sweep
+    picks = [name for name in ks if "retry_pick_kernel" in name]
+    assert len(picks) == 4 and all(rule in " ".join(picks) for rule in ("RetryRule", "FallbackRule", "MemberRetryRule", "SweepRule")), picks
     for name, v in ks.items():
         if "list_kernel" in name or "retry_pick" in name:
             assert v.get("private_segment_fixed_size", 0) == 0, name

@@ -85,7 +85,7 @@ int fspann_eval_kvariants_dev(fspann_ctx* c, int64_t n, const void* base_dev, in
             else launch(eval_kvariants_kernel<TB, TQ, false>);
         };
         if constexpr (DtypeOf<TB>::finite) { if (same_bytes) go(tb); else go(DtypeTag<float>{}); }
-        else if constexpr (!std::is_same<TB, double>::value) go(DtypeTag<float>{});
+        else if constexpr (DtypeOf<TB>::id != FSPANN_F64) go(DtypeTag<float>{});
     });
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;

@@ -73,7 +73,7 @@ int nn1_dispatch(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype,
     int rc = FSPANN_OK;
     with_row_type(base_dtype, [&](auto tb) {
         using TB = typename decltype(tb)::type;
-        if constexpr (!std::is_same<TB, double>::value)
+        if constexpr (DtypeOf<TB>::id != FSPANN_F64)
             rc = nn1_run(c, n, static_cast<const TB*>(base_dev), nq, q_dev, q_dtype, dim, qsel, nsel, out_idx, out_d2, head);
     });
     return rc;

@@ -16,7 +16,7 @@ int gt_rows_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const floa
     double* dist = static_cast<double*>(c->ws_gt.p);
     // a lane reads its typed row 16 bytes at a time when every row starts on a 16-byte boundary and ends on one; fp32 rows: element loads
     auto dist_kernel = gt_dist_kernel<TB, false>;
-    if constexpr (!std::is_same<TB, float>::value)
+    if constexpr (DtypeOf<TB>::id != FSPANN_F32)
         if ((static_cast<int64_t>(dim) * static_cast<int64_t>(sizeof(TB))) % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0) dist_kernel = gt_dist_kernel<TB, true>;
     for (int64_t s = 0; s < nq; s += chunk) {
         const int64_t cq = std::min(chunk, nq - s);

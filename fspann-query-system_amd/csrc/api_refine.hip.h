@@ -31,7 +31,7 @@ struct ScanPlan {
 };
 template <typename TC, int DC, bool GATHER>
 ScanPlan scan_plan(const fspann_ctx* c, int64_t nq, const TC* cand, int nchunks) {
-    constexpr int VN = VecOf<TC>::N;
+    constexpr int VN = RowCodec<TC>::N;
     ScanPlan s{};
     s.vec = (c->cfg.dim % VN == 0) && ((reinterpret_cast<uintptr_t>(cand) & 15) == 0);
     s.lds = std::max<size_t>(static_cast<size_t>(kRefRows) * (s.vec ? DC + VN : DC + 1) * sizeof(TC), static_cast<size_t>(kRefRows) * 16);
@@ -112,7 +112,7 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
         if (timed) c->rt_used += 2;
         bool fixed = false;
         // fp32 queries over rows of at most four bytes at the default tile width (128 bytes; no hand-over kernel reads FSPANN_F64 rows)
-        if constexpr (std::is_same<TQ, float>::value && sizeof(TC) <= 4 && DC * sizeof(TC) == 128) {
+        if constexpr (DtypeOf<TQ>::id == FSPANN_F32 && sizeof(TC) <= 4 && DC * sizeof(TC) == 128) {
             if (c->refine_fix_dev && nchunks == 1) {
                 // the batch's Route ran with a hand-over buffer: the scan's workgroups finish its PENDING queries first (tick.hip.h)
                 auto hand_over = [&](auto fk) -> int {
@@ -458,7 +458,7 @@ int fspann_store_gather_dev(fspann_ctx* c, int64_t nq, const int32_t* sel_ids_de
     const unsigned grid = static_cast<unsigned>((rows + 7) / 8);
     with_row_type(c->store_dtype, [&](auto tc) {      // (a store has a row dtype: fspann_store_set / _attach_dev)
         using T = typename decltype(tc)::type;
-        const int vec_ok = (d % VecOf<T>::N == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
+        const int vec_ok = (d % RowCodec<T>::N == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
         hipLaunchKernelGGL(store_gather_kernel<T>, dim3(grid), dim3(256), 0, c->stream, static_cast<const T*>(c->d_store), d, sel_ids_dev, sel_count_dev, B, nq,
                            static_cast<T*>(cand_dev), vec_ok);
     });

@@ -130,7 +130,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         // FSPANN_REFINE_DC = 64 / 128 the plain scan would run first and read PENDING as "no rows")
         // (FSPANN_U8 rows: the U8 refine_stream_fix_kernel, 16 dims per 16-byte slot, always at its one tile width)
         // (FSPANN_F16 / FSPANN_BF16 rows: the same overload, 8 dims per slot; FSPANN_F8E4M3 and FSPANN_I8 rows: 16 dims per slot, like U8)
-        // (whole 16-byte slots of 16 / element size dims, refine.hip.h's VecOf<TC>::N; no hand-over kernel reads FSPANN_F64 rows)
+        // (whole 16-byte slots of 16 / element size dims, RowCodec<TC>::N; no hand-over kernel reads FSPANN_F64 rows)
         const bool rows_ok = is_row_dtype(rows_dtype) && rows_dtype != FSPANN_F64 && d % static_cast<int>(16 / dtype_size(rows_dtype)) == 0 &&
                              (rows_dtype != FSPANN_F32 || c->knob_refine_dc == 0 || c->knob_refine_dc == 32);
         const bool stream_ok = rows_ok &&

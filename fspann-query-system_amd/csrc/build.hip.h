@@ -21,42 +21,13 @@ constexpr int kRsRounds = 8;                                   // 64-item rounds
 constexpr int kRsTile = kRsThreads * kRsRounds;                // items per workgroup
 constexpr int kRsWaves = kRsThreads / 64;
 
-// Four consecutive elements of a row-only type (4-byte aligned for the byte types, 8-byte for the 16-bit ones), widened to fp32
-// exactly: every value of these types is a float.  uint8_t (FSPANN_U8, 0..255) and int8_t (FSPANN_I8, -128..127): a bit-field
-// extract (sign-extending for int8_t) and an integer conversion per element.  _Float16 (FSPANN_F16): v_cvt_f32_f16, subnormals,
-// infinities and NaN included.  fsp_bf16 (FSPANN_BF16): the pattern b becomes the float with the bits b << 16.  fsp_f8e4m3
-// (FSPANN_F8E4M3): the hardware conversion, two v_cvt_pk_f32_fp8 per dword.
-template <typename T> __device__ __forceinline__ float4 widen4(const T* __restrict__ in) {
-    if constexpr (std::is_same<T, uint8_t>::value) {
-        const uint32_t w = *reinterpret_cast<const uint32_t*>(in);
-        return make_float4(static_cast<float>(w & 0xFFu), static_cast<float>((w >> 8) & 0xFFu), static_cast<float>((w >> 16) & 0xFFu), static_cast<float>(w >> 24));
-    } else if constexpr (std::is_same<T, int8_t>::value) {
-        const uint32_t w = *reinterpret_cast<const uint32_t*>(in);
-        return make_float4(static_cast<float>(static_cast<int32_t>(w << 24) >> 24), static_cast<float>(static_cast<int32_t>(w << 16) >> 24),
-                           static_cast<float>(static_cast<int32_t>(w << 8) >> 24), static_cast<float>(static_cast<int32_t>(w) >> 24));
-    } else if constexpr (std::is_same<T, _Float16>::value) {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        const h4 w = *reinterpret_cast<const h4*>(in);
-        return make_float4(static_cast<float>(w[0]), static_cast<float>(w[1]), static_cast<float>(w[2]), static_cast<float>(w[3]));
-    } else if constexpr (std::is_same<T, fsp_bf16>::value) {
-        const uint2 w = *reinterpret_cast<const uint2*>(in);
-        return make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u));
-    } else {
-        static_assert(std::is_same<T, fsp_f8e4m3>::value, "widen4: uint8_t, int8_t, _Float16, fsp_bf16 or fsp_f8e4m3");
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const int w = *reinterpret_cast<const int*>(in);
-        const f2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
-        return make_float4(lo[0], lo[1], hi[0], hi[1]);
-    }
-}
-
 // Setup input of a row-only type: widened to fp32 on the device, four elements per thread (one load, one 16-byte store); the encode
 // kernels then see what an F32 build would have uploaded, and refuse a non-finite element as in an F32 build.
 template <typename T>
 __global__ __launch_bounds__(256) void build_widen_kernel(const T* __restrict__ in, int64_t n, float* __restrict__ out) {
     const int64_t i = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
     if (i + 4 <= n) {
-        *reinterpret_cast<float4*>(out + i) = widen4(in + i);
+        *reinterpret_cast<float4*>(out + i) = RowCodec<T>::quad_f32(in + i);
     } else {
         for (int64_t j = i; j < n; j++) out[j] = static_cast<float>(in[j]);
     }

@@ -1,6 +1,7 @@
 // dtypes.h — what the library knows about each FSPANN_* dtype of include/fspann.h, in ONE table, and the two dispatchers that
 // turn a dtype given at run time into a type tag.  Included from fspann_common.h behind the element types.  Every entry point
-// goes through here: a new row type adds a row to the table and touches no dispatch site.
+// goes through here: a new row type adds a row to the table and its RowCodec (row_codec.hip.h: how the kernels read an element; a
+// static_assert there asks for one per row), and touches no dispatch site and no kernel.
 #pragma once
 
 namespace fspann {

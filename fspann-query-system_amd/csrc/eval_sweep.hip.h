@@ -1,7 +1,7 @@
 // eval_sweep.hip.h — computeMetricsAtK (FSA:770-835) for EVERY k of kVariants from one result list, one launch
 // (fspann_eval_kvariants_dev, include/fspann_eval.h): runQueries' metric loop (FSA:684-692).  Row j of the outputs is what
 // gt_metrics_kernel (groundtruth.hip.h) writes for k = ks[j], bit for bit.
-// Included from fspann_api.hip behind groundtruth.hip.h (gt_u32x4, gt_piece_f32, kGtMaxK).
+// Included from fspann_api.hip behind groundtruth.hip.h (kGtMaxK).
 #pragma once
 
 namespace fspann {
@@ -72,13 +72,13 @@ __global__ __launch_bounds__(kEvalThreads) void eval_kvariants_kernel(const TB* 
             const TB* row = base + static_cast<int64_t>((r & 1) ? gi : ai) * d;
             if constexpr (kVec) {
                 constexpr int kPer = 16 / static_cast<int>(sizeof(TB));
-                const gt_u32x4* pieces = reinterpret_cast<const gt_u32x4*>(row);
+                const fsp_u32x4* pieces = reinterpret_cast<const fsp_u32x4*>(row);
                 for (int t0 = 0; t0 < d; t0 += kPer) {
-                    const gt_u32x4 piece = pieces[t0 / kPer];
+                    const fsp_u32x4 piece = pieces[t0 / kPer];
 #pragma unroll
                     for (int e = 0; e < kPer; e++) {
                         const double qv = s_q[t0 + e];
-                        const double dg = qv - static_cast<double>(gt_piece_f32<TB>(piece, e));
+                        const double dg = qv - static_cast<double>(RowCodec<TB>::piece_f32(piece, e));
                         const double pg = dg * dg;
                         s = s + pg;
                     }

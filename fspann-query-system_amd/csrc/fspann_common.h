@@ -52,8 +52,6 @@ struct fsp_bf16 {
     __host__ __device__ __forceinline__ explicit operator double() const { return static_cast<double>(static_cast<float>(*this)); }
 };
 static_assert(sizeof(fsp_bf16) == 2 && alignof(fsp_bf16) == 2, "a bf16 row element is two bytes");
-// an element is +-inf or NaN iff its exponent field is all ones
-__host__ __device__ __forceinline__ bool bf16_finite(fsp_bf16 x) { return (x.b & 0x7f80u) != 0x7f80u; }
 
 // One FSPANN_F8E4M3 row element: the OCP fp8 e4m3fn byte b = S EEEE MMM, bias 7 (E = 0: +-M/8 * 2^-6; else +-(1 + M/8) * 2^(E-7);
 // 0x7F / 0xFF NaN, no infinity, |x| <= 448).  A type of its own, so that an fp8 row is never taken for a uint8_t row or a flag
@@ -74,11 +72,10 @@ struct fsp_f8e4m3 {
     __host__ __device__ __forceinline__ explicit operator double() const { return static_cast<double>(static_cast<float>(*this)); }
 };
 static_assert(sizeof(fsp_f8e4m3) == 1 && alignof(fsp_f8e4m3) == 1, "an fp8 row element is one byte");
-// an element is NaN iff all seven bits under the sign are set (the format has no infinity)
-__host__ __device__ __forceinline__ bool f8e4m3_finite(fsp_f8e4m3 x) { return (x.b & 0x7fu) != 0x7fu; }
 
 }  // namespace fspann
 #include "dtypes.h"     // the table of the dtypes, their dispatchers and the refusal by name
+#include "row_codec.hip.h"   // one RowCodec per row of the table: what the kernels know about an element type
 namespace fspann {
 
 // ---- order-key bit budget (DESIGN.md "Java order key") ----------------------------

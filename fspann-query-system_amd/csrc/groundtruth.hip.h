@@ -25,34 +25,8 @@ constexpr int kGtRows = 256;       // base rows (= lanes) per workgroup
 constexpr int kGtSelThreads = 1024;
 constexpr int kGtMaxK = 1024;
 
-// A 16-byte piece of a row: four dwords, element e in the bits its little-endian position gives it (4 floats, 8 halves or
-// bfloat16, 16 bytes or fp8).
-typedef uint32_t gt_u32x4 __attribute__((ext_vector_type(4)));
-
-// Element e of a 16-byte piece (e is a constant after unrolling), widened EXACTLY to fp32 by the hardware's conversion of the
-// type: float the dword itself, _Float16 v_cvt_f32_f16 (the high half of a dword through SDWA WORD_1), fsp_bf16 the 16 bits moved to the top of a dword,
-// fsp_f8e4m3 one v_cvt_pk_f32_fp8 per pair, uint8_t v_cvt_f32_ubyte0..3, int8_t v_cvt_f32_i32 of the sign-extended byte (SDWA sext).
-// Every value of the six types is a float, so nothing rounds; kernels keep fp16 and fp32 denormals, so a subnormal half or
-// bfloat16 arrives as its value.
-template <typename TB> __device__ __forceinline__ float gt_piece_f32(gt_u32x4 v, int e) {
-    if constexpr (std::is_same<TB, float>::value) {
-        return __uint_as_float(v[e]);
-    } else if constexpr (std::is_same<TB, _Float16>::value) {
-        const uint32_t w = v[e >> 1];
-        return static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>((e & 1) ? (w >> 16) : (w & 0xffffu))));
-    } else if constexpr (std::is_same<TB, fsp_bf16>::value) {
-        const uint32_t w = v[e >> 1];
-        return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
-    } else if constexpr (std::is_same<TB, fsp_f8e4m3>::value) {
-        const int w = static_cast<int>(v[e >> 2]);
-        return (e & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true)[e & 1] : __builtin_amdgcn_cvt_pk_f32_fp8(w, false)[e & 1];
-    } else if constexpr (std::is_same<TB, uint8_t>::value) {
-        return static_cast<float>((v[e >> 2] >> (8 * (e & 3))) & 0xffu);
-    } else {
-        static_assert(std::is_same<TB, int8_t>::value, "ground truth rows: float, uint8_t, int8_t, _Float16, fsp_bf16 or fsp_f8e4m3");
-        return static_cast<float>(static_cast<int32_t>(v[e >> 2] << (24 - 8 * (e & 3))) >> 24);
-    }
-}
+// A row is read in 16-byte pieces of four dwords (fsp_u32x4), element e in the bits its little-endian position gives it (4 floats,
+// 8 halves or bfloat16, 16 bytes or fp8), and widened exactly to fp32 by the row type's codec (RowCodec<TB>::piece_f32).
 
 // dist[q][r] = sum_i (double)(q[q][i] - base[r][i])^2 for the queries [q0, q0 + kGtQT) of this tile, base rows of type TB
 // (fspann_groundtruth_dev: float; fspann_groundtruth_rows_dev / _store_dev: every row type): the element widened to the float
@@ -76,12 +50,12 @@ __global__ __launch_bounds__(kGtRows) void gt_dist_kernel(const TB* __restrict__
         const TB* row = base + r * d;
         if constexpr (kVec) {
             constexpr int kPer = 16 / static_cast<int>(sizeof(TB));
-            const gt_u32x4* pieces = reinterpret_cast<const gt_u32x4*>(row);
+            const fsp_u32x4* pieces = reinterpret_cast<const fsp_u32x4*>(row);
             for (int i0 = 0; i0 < d; i0 += kPer) {
-                const gt_u32x4 piece = pieces[i0 / kPer];
+                const fsp_u32x4 piece = pieces[i0 / kPer];
                 float v[kPer];
 #pragma unroll
-                for (int e = 0; e < kPer; e++) v[e] = gt_piece_f32<TB>(piece, e);
+                for (int e = 0; e < kPer; e++) v[e] = RowCodec<TB>::piece_f32(piece, e);
                 // Query by query (the sums of different queries do not meet, and each still takes its squares in dimension order):
                 // one query's kPer floats are one scalar load.  The empty asm makes query t's pointer depend on the sums of query
                 // t - 2, so its load is issued one query ahead and no earlier: left alone, the scheduler starts all kGtQT loads of

@@ -16,7 +16,6 @@ namespace fspann {
 
 typedef int gt8_i32x4 __attribute__((ext_vector_type(4)));
 typedef int gt8_i32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned gt8_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kGt8Rows = 128;        // base rows per workgroup: 4 waves x 32 (one MFMA tile column each)
 constexpr int kGt8Q = 128;           // queries per workgroup: 4 tiles of 32, walked in turn against the wave's 32 rows
@@ -38,13 +37,12 @@ constexpr int kGt8SelThreads = 1024;
 // is an integer in 0 .. d * 255^2 either way.
 template <typename TB, bool kAligned>
 __device__ __forceinline__ gt8_i32x4 gt8_frag(const TB* __restrict__ row, int k0, int d) {
-    static_assert(std::is_same<TB, uint8_t>::value || std::is_same<TB, int8_t>::value, "byte ground truth rows: uint8_t or int8_t");
-    constexpr unsigned kFlip = std::is_same<TB, uint8_t>::value ? 0x80u : 0u;      // per byte; ^ 0 compiles to nothing
-    gt8_u32x4 w = {0u, 0u, 0u, 0u};
+    constexpr unsigned kFlip = RowCodec<TB>::kToSigned;      // per byte; only the byte types (uint8_t, int8_t) have it
+    fsp_u32x4 w = {0u, 0u, 0u, 0u};
     if constexpr (kAligned) {       // (d >= 16 here; the load is made at a clamped address so that the K loop holds no branch)
-        w = *reinterpret_cast<const gt8_u32x4*>(row + min(k0, d - 16));
+        w = *reinterpret_cast<const fsp_u32x4*>(row + min(k0, d - 16));
         w ^= kFlip * 0x01010101u;
-        if (k0 >= d) w = gt8_u32x4{0u, 0u, 0u, 0u};
+        if (k0 >= d) w = fsp_u32x4{0u, 0u, 0u, 0u};
     } else {
 #pragma unroll
         for (int j = 0; j < 16; j++) {
@@ -95,8 +93,8 @@ __global__ __launch_bounds__(256) void gt8_dist_kernel(const TB* __restrict__ ba
         if (q0 >= nq) break;
         const TB* qrow = q + min(q0 + (lane & 31), nq - 1) * d;
         // |q'|^2 of this lane's 16 queries, four 16-byte loads (qn holds whole tiles of 32: entries >= nq are never used for a store)
-        const gt8_u32x4* qn4 = reinterpret_cast<const gt8_u32x4*>(qn + q0 + 4 * (lane >> 5));
-        gt8_u32x4 nqv[4];
+        const fsp_u32x4* qn4 = reinterpret_cast<const fsp_u32x4*>(qn + q0 + 4 * (lane >> 5));
+        fsp_u32x4 nqv[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) nqv[j] = qn4[2 * j];
         gt8_i32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -152,7 +150,7 @@ __global__ __launch_bounds__(kGt8SelThreads) void gt8_select_kernel(const unsign
     __shared__ unsigned sel_id[kGtMaxK];
     const int tid = threadIdx.x;
     const int64_t qi = blockIdx.x;
-    const gt8_u32x4* keys4 = reinterpret_cast<const gt8_u32x4*>(dist + qi * ld);
+    const fsp_u32x4* keys4 = reinterpret_cast<const fsp_u32x4*>(dist + qi * ld);
     const int64_t n4 = (n + 3) >> 2;
     const int kk = static_cast<int>(min(static_cast<int64_t>(k), n));
     if (tid == 0) { s_pk = 0u; s_pi = 0u; s_need = static_cast<unsigned>(kk); s_cnt = 0u; s_done = 0u; }
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(kGt8SelThreads) void gt8_select_kernel(const unsign
         const bool first = (p == 0) || (p == ndd);                 // no digit of this part chosen yet
         const int hs = first ? 0 : sh + 8;                         // (first: the prefix test is not made; keeps the shift below 32)
         for (int64_t i4 = tid; i4 < n4; i4 += kGt8SelThreads) {    // (lanes past the end have left: the ballots count the rest)
-            const gt8_u32x4 v = keys4[i4];
+            const fsp_u32x4 v = keys4[i4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int64_t i = 4 * i4 + j;
@@ -207,7 +205,7 @@ __global__ __launch_bounds__(kGt8SelThreads) void gt8_select_kernel(const unsign
     // (s_pk, s_pi) is the kk-th smallest composite: collect everything at or below it (exactly kk elements), then order them
     const unsigned tk = s_pk, ti = s_pi;
     for (int64_t i4 = tid; i4 < n4; i4 += kGt8SelThreads) {
-        const gt8_u32x4 v = keys4[i4];
+        const fsp_u32x4 v = keys4[i4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int64_t i = 4 * i4 + j;

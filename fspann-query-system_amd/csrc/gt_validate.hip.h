@@ -67,14 +67,14 @@ __global__ __launch_bounds__(kGtRows) void nn1_exact_kernel(const TB* __restrict
             if constexpr (kVec) {
                 constexpr int kPer = 16 / static_cast<int>(sizeof(TB));
                 constexpr int kSub = kPer < 8 ? kPer : 8;          // one query's kSub doubles are one scalar load (at most 16 dwords)
-                const gt_u32x4* pieces = reinterpret_cast<const gt_u32x4*>(row);
+                const fsp_u32x4* pieces = reinterpret_cast<const fsp_u32x4*>(row);
                 for (int i0 = 0; i0 < d; i0 += kPer) {
-                    const gt_u32x4 piece = pieces[i0 / kPer];
+                    const fsp_u32x4 piece = pieces[i0 / kPer];
 #pragma unroll
                     for (int s = 0; s < kPer; s += kSub) {
                         double v[kSub];
 #pragma unroll
-                        for (int e = 0; e < kSub; e++) v[e] = static_cast<double>(gt_piece_f32<TB>(piece, s + e));
+                        for (int e = 0; e < kSub; e++) v[e] = static_cast<double>(RowCodec<TB>::piece_f32(piece, s + e));
                         // query by query, the load of query t issued one query ahead and no earlier (gt_dist_kernel says why)
 #pragma unroll
                         for (int t = 0; t < kGtQT; t++) {

@@ -37,120 +37,6 @@ struct RefinePartial {  // one per (query, chunk, rank)
     int32_t id;
 };
 
-template <typename T> struct VecOf;
-// native clang vectors (plain SSA values: a HIP float4 staging array ends up in scratch)
-typedef float fsp_f32x4 __attribute__((ext_vector_type(4)));
-typedef double fsp_f64x2 __attribute__((ext_vector_type(2)));
-template <> struct VecOf<float> { using type = fsp_f32x4; static constexpr int N = 4; };
-template <> struct VecOf<double> { using type = fsp_f64x2; static constexpr int N = 2; };
-// FSPANN_U8 rows: a 16-byte slot is 16 elements, held as four dwords (byte e of the slot = bits [8 (e % 4), 8 (e % 4) + 8) of
-// dword e / 4); a row element is the integer 0..255, always finite.
-typedef uint32_t fsp_u32x4 __attribute__((ext_vector_type(4)));
-template <> struct VecOf<uint8_t> { using type = fsp_u32x4; static constexpr int N = 16; };
-template <typename T> struct RowIsBytes { static constexpr bool value = false; };
-template <> struct RowIsBytes<uint8_t> { static constexpr bool value = true; };
-// FSPANN_I8 rows: the same byte geometry, a row element is the two's-complement integer -128..127, always finite like a byte.  The
-// slot is held as two SIGNED qwords: a native vector like the others, and a type of its own, so that no overload takes it for an
-// unsigned byte slot (unsigned dwords), a bf16 slot (signed dwords) or an fp8 slot (unsigned qwords).
-typedef int64_t fsp_i8x16 __attribute__((ext_vector_type(2)));
-typedef int32_t fsp_i32x4 __attribute__((ext_vector_type(4)));
-template <> struct VecOf<int8_t> { using type = fsp_i8x16; static constexpr int N = 16; };
-template <> struct RowIsBytes<int8_t> { static constexpr bool value = true; };
-// FSPANN_F16 rows: a 16-byte slot is 8 IEEE binary16 elements (four dwords, two halves each); an element is the half widened
-// exactly (half -> float -> double: every finite half, subnormals included, is a double), and unlike a byte it can be +-inf or NaN.
-typedef _Float16 fsp_f16x8 __attribute__((ext_vector_type(8)));
-template <> struct VecOf<_Float16> { using type = fsp_f16x8; static constexpr int N = 8; };
-template <typename T> struct RowIsHalf { static constexpr bool value = false; };
-template <> struct RowIsHalf<_Float16> { static constexpr bool value = true; };
-// FSPANN_BF16 rows: the same 2-byte geometry (a 16-byte slot is 8 elements in four dwords, low element in the low 16 bits).  The
-// slot is held as four SIGNED dwords: a native vector like the others (a struct could not be a nontemporal load's result), and a
-// type of its own, so that no overload takes it for the unsigned dwords of a byte slot.  An element is the fp32 whose bit pattern
-// is the 16 bits shifted up, and can be +-inf or NaN.
-typedef int32_t fsp_bf16x8 __attribute__((ext_vector_type(4)));
-template <> struct VecOf<fsp_bf16> { using type = fsp_bf16x8; static constexpr int N = 8; };
-template <typename T> struct RowIsBf16 { static constexpr bool value = false; };
-template <> struct RowIsBf16<fsp_bf16> { static constexpr bool value = true; };
-// FSPANN_F8E4M3 rows: the byte geometry of FSPANN_U8 (a 16-byte slot is 16 elements, byte e of the slot = bits [8 (e % 4),
-// 8 (e % 4) + 8) of dword e / 4).  The slot is held as two unsigned qwords: a native vector like the others, and a type of its
-// own, so that no overload takes it for a byte slot (unsigned dwords) or a bf16 slot (signed dwords); sixteen separate bytes would
-// be the natural spelling, but a conditional load of such a vector is legalised byte by byte and ends in scratch.  An element is an
-// OCP e4m3fn value and, unlike a byte, can be NaN (0x7F / 0xFF; the format has no infinity).
-typedef uint64_t fsp_f8x16 __attribute__((ext_vector_type(2)));
-template <> struct VecOf<fsp_f8e4m3> { using type = fsp_f8x16; static constexpr int N = 16; };
-// every row type fills a 16-byte slot: what the host computes as 16 / element size (api_tick.hip.h) is VecOf<TC>::N
-#define FSPANN_SLOT_CHECK(ID, T, QUERY, FINITE, WORDS, USES, NOUN) static_assert(VecOf<T>::N == 16 / sizeof(T), #ID ": elements per 16-byte slot");
-FSPANN_DTYPE_TABLE(FSPANN_SLOT_CHECK)
-#undef FSPANN_SLOT_CHECK
-template <typename T> struct RowIsF8 { static constexpr bool value = false; };
-template <> struct RowIsF8<fsp_f8e4m3> { static constexpr bool value = true; };
-// Which hardware conversion widens an fp8 slot (both exact; a switch so that the two can be A/B-ed): 0 = v_cvt_pk_f32_fp8, one
-// instruction per two elements (the word of the dword through SDWA src0_sel:WORD_1); 1 = v_cvt_f32_fp8, one per element (the byte
-// through SDWA src0_sel:BYTE_n).
-#ifndef FSPANN_F8_WIDEN
-#define FSPANN_F8_WIDEN 0
-#endif
-
-template <typename T> __device__ __forceinline__ bool finite_t(T x) {
-    return fabs(static_cast<double>(x)) <= 1.79769313486231570815e+308;
-}
-
-__device__ __forceinline__ double vcomp(fsp_f32x4 v, int e) { return static_cast<double>(v[e]); }
-__device__ __forceinline__ double vcomp(fsp_f64x2 v, int e) { return v[e]; }
-// Exact widening of byte e of a slot (e is a constant after unrolling): a bit-field extract and v_cvt_f64_u32.  Measured against
-// v_cvt_f32_ubyte0..3 + v_cvt_f64_f32, against building 2^52 + byte in the mantissa and subtracting 2^52 (no conversion at all),
-// and against keeping the query's tile as fp64 in LDS instead of converting it per element: within 5 % of each other
-//  — every vector instruction of this loop issues at the same rate, so the plain expression stays.
-__device__ __forceinline__ double vcomp(fsp_u32x4 v, int e) { return static_cast<double>((v[e >> 2] >> (8 * (e & 3))) & 0xFFu); }
-// Exact widening of signed byte e of a slot (e is a constant after unrolling): the byte's sign is extended by a left shift to the
-// top of its dword and an arithmetic shift back (one v_bfe_i32; for the top byte the arithmetic shift alone), then v_cvt_f64_i32
-// — the instruction count of the unsigned byte above.
-__device__ __forceinline__ double vcomp(fsp_i8x16 v, int e) {
-    const int32_t w = __builtin_bit_cast(fsp_i32x4, v)[e >> 2];
-    return static_cast<double>(static_cast<int32_t>(static_cast<uint32_t>(w) << (24 - 8 * (e & 3))) >> 24);
-}
-// Exact widening of half e of a slot: v_cvt_f32_f16 (the high half of a dword through SDWA src0_sel:WORD_1, no shift), then
-// v_cvt_f64_f32.  Kernels keep fp16 denormals (float_denorm_mode_16_64 = 3), so a subnormal half arrives as its value.
-__device__ __forceinline__ double vcomp(fsp_f16x8 v, int e) { return static_cast<double>(static_cast<float>(v[e])); }
-// Exact widening of bf16 e of a slot (e is a constant after unrolling): the low element of a dword is dword << 16, the high one
-// dword & 0xffff0000, each taken as the bits of a float — one integer VALU op — then v_cvt_f64_f32.  No conversion that could
-// round; nothing depends on the fp16 denormal mode, but a bf16 subnormal is an fp32 subnormal and must survive v_cvt_f64_f32
-// (kernels keep fp32 denormals, float_denorm_mode_32 = 3).
-__device__ __forceinline__ float vcomp_f32(fsp_bf16x8 v, int e) {
-    const uint32_t w = static_cast<uint32_t>(v[e >> 1]);
-    return __uint_as_float((e & 1) ? (w & 0xffff0000u) : (w << 16));
-}
-__device__ __forceinline__ double vcomp(fsp_bf16x8 v, int e) { return static_cast<double>(vcomp_f32(v, e)); }
-// raw elements e and e + 1 both finite.  (b & 0x7f80) == 0x7f80 is +-inf or NaN, and that exponent field is the widened float's:
-// one v_cmp_class_f32 on the float the widening has made anyway, instead of a mask and a compare on the raw dword.
-__device__ __forceinline__ bool vpair_finite(fsp_bf16x8 v, int e) {
-    return __builtin_isfinite(vcomp_f32(v, e)) && __builtin_isfinite(vcomp_f32(v, e + 1));
-}
-// Exact widening of fp8 e of a slot (e is a constant after unrolling): the hardware's OCP e4m3fn conversion of dword e / 4 — every
-// e4m3 value, subnormals included, is a normal fp32, so nothing depends on a denormal mode — then v_cvt_f64_f32.  The two elements
-// of a pair (e, e + 1) come out of one v_cvt_pk_f32_fp8.
-__device__ __forceinline__ float vcomp_f32(fsp_f8x16 v, int e) {
-    const int w = static_cast<int>(__builtin_bit_cast(fsp_u32x4, v)[e >> 2]);
-#if FSPANN_F8_WIDEN == 0
-    return (e & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true)[e & 1] : __builtin_amdgcn_cvt_pk_f32_fp8(w, false)[e & 1];
-#else
-    switch (e & 3) {
-    case 0: return __builtin_amdgcn_cvt_f32_fp8(w, 0);
-    case 1: return __builtin_amdgcn_cvt_f32_fp8(w, 1);
-    case 2: return __builtin_amdgcn_cvt_f32_fp8(w, 2);
-    default: return __builtin_amdgcn_cvt_f32_fp8(w, 3);
-    }
-#endif
-}
-__device__ __forceinline__ double vcomp(fsp_f8x16 v, int e) { return static_cast<double>(vcomp_f32(v, e)); }
-// raw elements e and e + 1 both finite.  (b & 0x7f) == 0x7f is NaN and nothing else is non-finite, so the four bytes of a dword
-// are tested at once, with the dword's first pair: under the mask 0x7f7f7f7f adding 1 to every byte carries into its bit 7 iff its
-// seven bits were all ones, and never into the next byte — three integer operations per four elements, nothing for the second pair.
-__device__ __forceinline__ bool vpair_finite(fsp_f8x16 v, int e) {
-    if (e & 2) return true;
-    const uint32_t w = __builtin_bit_cast(fsp_u32x4, v)[e >> 2];
-    return (((w & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u) == 0;
-}
-
 constexpr int kRefFilterMaxK = 32;   // top-k via per-wave k-th-smallest filter up to this k
 
 // rank of (key, pos) among keys[0..n): #{j : key_j < key || (key_j == key && j < pos)}; keys are read two
@@ -533,8 +419,9 @@ __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, u
     const int d = a.d, nchunks = a.nchunks;
     const int32_t* __restrict__ cand_ids = a.cand_ids;
     const int32_t* __restrict__ cand_count = a.cand_count;
-    using V = typename VecOf<TC>::type;
-    constexpr int VN = VecOf<TC>::N;
+    using C = RowCodec<TC>;
+    using V = typename C::slot;
+    constexpr int VN = C::N;
     constexpr int PITCH = VEC ? DC + VN : DC + 1;   // elements per LDS row
     constexpr int VPR = DC / VN;                    // 16-byte vectors per row per tile
     // LDS budget: <= 40 KB per workgroup so that FOUR workgroups (all 1024 of a 1024-query batch) are resident per
@@ -630,9 +517,9 @@ __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, u
                     for (int e = 0; e < VN; e += 2) {
                         const double q0 = static_cast<double>(qrow[c0 + kk + e]);      // uniform address -> scalar load
                         const double q1 = static_cast<double>(qrow[c0 + kk + e + 1]);
-                        if constexpr (RowIsBf16<TC>::value || RowIsF8<TC>::value) ok = ok && vpair_finite(xv, e);   // the exponent fields of the two raw elements (fp8: their NaN patterns)
-                        else if constexpr (!RowIsBytes<TC>::value) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]);   // v_cmp_class on the raw element (a byte is always finite)
-                        const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   // exact widening
+                        if constexpr (C::slot_test == SlotTest::pair) ok = ok && C::pair_finite(xv, e);   // in the type's own granularity (a byte is always finite)
+                        else if constexpr (C::slot_test == SlotTest::element) ok = ok && C::slot_finite(xv, e) && C::slot_finite(xv, e + 1);
+                        const double x0 = C::wide(xv, e), x1 = C::wide(xv, e + 1);   // exact widening
                         const double d0 = q0 - x0;                               // QSI.java:368
                         const double p0 = d0 * d0;
                         s = s + p0;                                              // QSI.java:369 (in order)
@@ -644,7 +531,7 @@ __device__ __forceinline__ void refine_scan_block(const RefineArgs<TC, TQ>& a, u
             } else {
                 for (int kk = 0; kk < dc; kk++) {
                     const TC x = myrow[kk];
-                    ok = ok && finite_t(x);
+                    ok = ok && fabs(static_cast<double>(x)) <= 1.79769313486231570815e+308;   // finite, asked of the widened value: any row type
                     const double dd = static_cast<double>(qrow[c0 + kk]) - static_cast<double>(x);
                     const double sq = dd * dd;
                     s = s + sq;
@@ -700,8 +587,9 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     static_assert(!(kKeys && (kMulti || FixFn::enabled)), "keys: one unit per chunk, no hand-over");
     static_assert(!(kMulti && (GATHER || FixFn::enabled)), "runs of chunks: dense blocks, no hand-over");
     static_assert(!(kList && (kMulti || FixFn::enabled)), "list mode: one partial list per chunk, no hand-over");
-    using V = typename VecOf<TC>::type;
-    constexpr int VN = VecOf<TC>::N;
+    using C = RowCodec<TC>;
+    using V = typename C::slot;
+    constexpr int VN = C::N;
     constexpr int PITCH = DC + VN;
     constexpr int VPR = DC / VN;
     // fp32 rows against an fp32 query: |q - x| < 2^129, so the fp64 sum of squares cannot overflow, and a NaN or an infinity
@@ -716,8 +604,7 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
     // against an fp64 query every raw element's exponent field is tested ((b & 0x7f80) == 0x7f80 is +-inf or NaN).
     // fp8 rows (FSPANN_F8E4M3) are one byte but NOT always finite: 0x7F / 0xFF are NaN (no infinity, |x| <= 448).  Against an fp32
     // query the sum tells (a NaN reaches it, |q - x| < 2^129 cannot overflow); against an fp64 query every element is tested.
-    constexpr bool kByteRows = RowIsBytes<TC>::value;
-    constexpr bool kSumTellsFinite = ((sizeof(TC) == 4 || kByteRows || RowIsHalf<TC>::value || RowIsBf16<TC>::value || RowIsF8<TC>::value) && sizeof(TQ) == 4);
+    constexpr bool kSumTellsFinite = DtypeOf<TC>::id != FSPANN_F64 && DtypeOf<TQ>::id == FSPANN_F32;
     const TC* __restrict__ cand = a.cand;
     const int64_t store_n = a.store_n, B = a.B;
     const int d = a.d, nchunks = a.nchunks;
@@ -918,9 +805,9 @@ __device__ __forceinline__ void refine_stream_run(const RefineArgs<TC, TQ>& a, u
                     _Pragma("unroll") for (int e = 0; e < VN; e += 2) {                                             \
                         const double q0 = static_cast<double>(qrow[(C0) + kk + e]);      /* uniform address -> scalar load */ \
                         const double q1 = static_cast<double>(qrow[(C0) + kk + e + 1]);                             \
-                        if constexpr (!kSumTellsFinite && (RowIsBf16<TC>::value || RowIsF8<TC>::value)) ok = ok && vpair_finite(xv, e); \
-                        else if constexpr (!kSumTellsFinite && !kByteRows) ok = ok && __builtin_isfinite(xv[e]) && __builtin_isfinite(xv[e + 1]); \
-                        const double x0 = vcomp(xv, e), x1 = vcomp(xv, e + 1);   /* exact widening */                \
+                        if constexpr (!kSumTellsFinite && C::slot_test == SlotTest::pair) ok = ok && C::pair_finite(xv, e); \
+                        else if constexpr (!kSumTellsFinite && C::slot_test == SlotTest::element) ok = ok && C::slot_finite(xv, e) && C::slot_finite(xv, e + 1); \
+                        const double x0 = C::wide(xv, e), x1 = C::wide(xv, e + 1);   /* exact widening */            \
                         const double d0 = q0 - x0;                               /* QSI.java:368 */                  \
                         const double p0 = d0 * d0;                                                                  \
                         s = s + p0;                                              /* QSI.java:369 (in order) */       \
@@ -1132,8 +1019,8 @@ __global__ __launch_bounds__(256) void store_gather_kernel(const T* __restrict__
     const T* src = store + static_cast<int64_t>(id) * d;
     T* dst = out + row * d;
     if (vec_ok) {
-        using V = typename VecOf<T>::type;
-        constexpr int VN = VecOf<T>::N;
+        using V = typename RowCodec<T>::slot;
+        constexpr int VN = RowCodec<T>::N;
         const int nv = d / VN;
         for (int i = lane; i < nv; i += 32) reinterpret_cast<V*>(dst)[i] = reinterpret_cast<const V*>(src)[i];
     } else {

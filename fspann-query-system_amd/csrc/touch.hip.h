@@ -14,11 +14,6 @@ constexpr int kTouchThreads = 256;
 constexpr int64_t kTouchTile = int64_t(kTouchThreads) * 16;   // handles per tile: one 16-byte load per thread
 constexpr int kTouchScanThreads = 1024;
 
-// an element of a row is finite (FSPANN_BF16 / FSPANN_F8E4M3: tested on its bits, like the float it widens to)
-template <typename T> __device__ __forceinline__ bool touch_finite(T x) { return __builtin_isfinite(x); }
-__device__ __forceinline__ bool touch_finite(fsp_bf16 x) { return bf16_finite(x); }
-__device__ __forceinline__ bool touch_finite(fsp_f8e4m3 x) { return f8e4m3_finite(x); }
-
 // 1 per store row whose dim values are all finite — Refine's `ok` for a store row (QSI.isValid, QSI:407-413).  One wave per row.
 template <typename T>
 __global__ __launch_bounds__(kTouchThreads) void touch_store_valid_kernel(const T* __restrict__ store, int64_t n, int d, uint8_t* __restrict__ ok) {
@@ -27,7 +22,7 @@ __global__ __launch_bounds__(kTouchThreads) void touch_store_valid_kernel(const 
     if (row >= n) return;
     const T* r = store + row * d;
     bool bad = false;
-    for (int i = lane; i < d; i += 64) bad = bad || !touch_finite(r[i]);
+    for (int i = lane; i < d; i += 64) bad = bad || !RowCodec<T>::finite(r[i]);
     const bool any_bad = __any(bad);
     if (lane == 0) ok[row] = any_bad ? 0 : 1;
 }
@@ -83,8 +78,8 @@ __global__ __launch_bounds__(kTouchThreads) void touch_mark_rows_kernel(const TQ
         if (id < 0 || id >= n_set) continue;          // (wave-uniform) not a handle of this index: nothing to mark
         const TC* r = rows + (qi * B + j) * d;
         bool bad = false;
-        if constexpr (!std::is_same<TC, uint8_t>::value && !std::is_same<TC, int8_t>::value)  // (FSPANN_U8 / FSPANN_I8 rows: a byte is always finite; F16 / BF16 / F8E4M3 rows are tested like floats)
-            for (int i = lane; i < d; i += 64) bad = bad || !touch_finite(r[i]);
+        if constexpr (!RowCodec<TC>::always_finite)      // (a byte is never read a second time)
+            for (int i = lane; i < d; i += 64) bad = bad || !RowCodec<TC>::finite(r[i]);
         const bool any_bad = __any(bad);
         if (lane == 0 && !any_bad) set[id] = 1;
     }

@@ -40,6 +40,16 @@ int upload_index(fspann_ctx* c) {
                        ? fail(FSPANN_E_ARG, "table %d: id handle %lld out of range [0,%lld)", bad_td.load(), bad_id.load(), (long long)c->n_ids)
                        : fail(FSPANN_E_ARG, "table %d holds id handle %lld twice", bad_td.load(), bad_id.load());
     }
+    // Key ranges must ascend over a table's partitions, as GreedyPartitioner cuts them (sorted keys; equal and overlapping ranges
+    // are fine): the reference's findNearestPartition is a binary search and means nothing else, and the probe's directory and
+    // G-ary search (route.hip.h, route_probe_table) find its centre only then.
+    for (int td = 0; td < TD; td++) {
+        const auto& mn = c->h_min[td]; const auto& mx = c->h_max[td];
+        for (size_t i = 0; i < mn.size(); i++)
+            if (!(mn[i] >= 0 && mn[i] <= mx[i] && (i == 0 || (mn[i] >= mn[i - 1] && mx[i] >= mx[i - 1]))))
+                return fail(FSPANN_E_ARG, "table %d: key range of partition %lld does not ascend (minKey %lld, maxKey %lld)", td, (long long)i,
+                            (long long)mn[i], (long long)mx[i]);
+    }
     c->h_tables.assign(TD, RouteTable{});
     int64_t parts = 0, offs = 0, ids = 0;
     for (int td = 0; td < TD; td++) {
@@ -57,19 +67,12 @@ int upload_index(fspann_ctx* c) {
     c->total_ids = ids;
     free_devt(c->d_tables); free_devt(c->d_recs); free_devt(c->d_ids); free_devt(c->d_dir);
     // Radix directory of the probe (route.hip.h, route_probe_table): for every table and every value p of the key's top
-    // dir_bits bits, the first partition with maxKey >= p << s and the first with minKey >= p << s.  It needs what the
-    // reference's own binary search needs, key ranges in ascending order; an imported index without that keeps the plain search.
+    // dir_bits bits, the first partition with maxKey >= p << s and the first with minKey >= p << s (key ranges ascend: checked above).
     std::vector<int2> dir;
     c->dir_bits = 0;
     {
         int maxp = 0;
-        bool mono = true;
-        for (int td = 0; td < TD && mono; td++) {
-            const auto& mn = c->h_min[td]; const auto& mx = c->h_max[td];
-            maxp = std::max<int>(maxp, static_cast<int>(mn.size()));
-            for (size_t i = 0; i < mn.size() && mono; i++)
-                mono = mn[i] >= 0 && mn[i] <= mx[i] && (i == 0 || (mn[i] >= mn[i - 1] && mx[i] >= mx[i - 1]));
-        }
+        for (int td = 0; td < TD; td++) maxp = std::max<int>(maxp, static_cast<int>(c->h_min[td].size()));
         int bits = 1;
         while (bits < 16 && (4 << bits) < maxp) bits++;      // about four partitions per directory entry
         // ... and up to six bits more while the whole directory stays within 64 MB: keys are skewed (the most popular 12-bit prefix of
@@ -82,7 +85,7 @@ int upload_index(fspann_ctx* c) {
         }
         bits = std::min(20, std::max(1, bits + extra));
         const size_t D = size_t(1) << bits;
-        if (mono && maxp > 0 && static_cast<size_t>(TD) * (D + 1) < (size_t(1) << 30)) {
+        if (maxp > 0 && static_cast<size_t>(TD) * (D + 1) < (size_t(1) << 30)) {
             dir.resize(static_cast<size_t>(TD) * (D + 1));
             const int sh = 63 - bits;
             for (int td = 0; td < TD; td++) {

@@ -308,7 +308,7 @@ __device__ __forceinline__ int route_probe_table(const RouteParams& prm, bool ac
     int loA = 0, hiA = act ? tb.nparts : 0, loE = 0, hiE = hiA;
     if (prm.dir && act) {
         // radix directory on the key's top bits: ONE dependent load instead of the first rounds of the search.  Keys are
-        // monotone over the partitions (checked when the directory is built), so for a query key with prefix p
+        // monotone over the partitions (fspann_finalize refuses a table where they are not), so for a query key with prefix p
         // a lies in [A[p], A[p+1]] and e in [E[p], E[p+1]], and the predicate holds at the upper ends (or they are nparts).
         const int2* dd = prm.dir + tb.dir_base + (qKey >> (63 - prm.dir_bits));
         const int2 d0 = dd[0], d1 = dd[1];

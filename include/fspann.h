@@ -156,7 +156,13 @@ int fspann_get_gfunctions(fspann_ctx* ctx, double* alpha, double* r, double* ome
 
 /* One (t,d) table of GreedyPartitioner.Partition (idx/GreedyPartitioner.java:13-32) as SoA:
  * min_key/max_key[n_parts], rep[n_parts][W] (W = ceil(m*lambda/64) BitSet words, bit i ->
- * word i/64 bit i%64), id_off[n_parts+1], ids[id_off[n_parts]] in partition order.          */
+ * word i/64 bit i%64), id_off[n_parts+1], ids[id_off[n_parts]] in partition order.
+ * A partition holds 0 to block_size ids (an empty one still has its key range and rep), a table may have no partitions
+ * (it is skipped, PIS:638) and need not hold every id.  Key ranges must ASCEND over a table's partitions, which is what
+ * GreedyPartitioner produces (sorted keys): 0 <= min_key[p] <= max_key[p], min_key[p] >= min_key[p-1] and
+ * max_key[p] >= max_key[p-1]; equal and overlapping ranges are fine.  findNearestPartition (GreedyPartitioner.java:101-124)
+ * is a binary search over them and means nothing else; fspann_finalize (and so fspann_index_load) refuses a table that
+ * breaks this with FSPANN_E_ARG, naming the table and the first offending partition.                                    */
 int fspann_set_index(fspann_ctx* ctx, int td, int64_t n_parts, const int64_t* min_key, const int64_t* max_key,
                      const uint64_t* rep, const int64_t* id_off, const int32_t* ids);
 

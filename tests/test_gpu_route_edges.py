@@ -263,7 +263,7 @@ def test_bounded_select_many_collisions_hands_back(pkg, oracle):
 @pytest.mark.parametrize("block_size", [16, 100, 128])
 def test_bounded_select_other_block_sizes(pkg, oracle, block_size):
     """The reference's block size is the constant 64 (PIS:92); the library takes others.  Partitions that are not one
-    wave wide go through the whole-partition path of the bounded select: compared with the full select."""
+    wave wide go through the whole-partition path of the bounded select: compared with the full select, and with the oracle."""
     sc = make_scene(oracle, n=20000, d=16, T=6, D=1, m=12, lam=2, B=200, seed=31 + block_size)
     p = sc["params"]
     codes = sc["oracle"].encode(sc["rng"].standard_normal((20, 16)))
@@ -282,6 +282,11 @@ def test_bounded_select_other_block_sizes(pkg, oracle, block_size):
             assert info["lazy"] and info["overflowed"] == 0
             assert np.array_equal(lazy["count"], full["count"])
             assert np.array_equal(lazy["ids"], full["ids"]) and np.array_equal(lazy["score"], full["score"])
+        # ... and both with the oracle over the same cut (tests/index_shapes.py): what the two selects share is held to it too
+        import index_shapes as ish
+        o, codes_h = sc["oracle"], sc["oracle"].encode(sc["X64"])
+        o2 = ish.second_oracle(sc, [ish.recut(o, codes_h, td, ish.uniform(p["n"], block_size)) for td in range(o.TD)])
+        ish.compare_selects(ctx, o2, codes, limits=(None, 200, 33), bounded=(200, 33), must_be_bounded=True)
 
 
 def test_bounded_select_hands_back_large_queries(pkg, oracle, monkeypatch):

@@ -1,5 +1,5 @@
 """ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
-include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h).
+include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h, include/fspann_narrow.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -87,7 +87,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -249,6 +249,20 @@ _SIGS_SWEEP = {
 }
 
 
+class Fit(C.Structure):
+    """fspann_fit of include/fspann_narrow.h"""
+    _fields_ = [("fits", C.c_uint32), ("narrowest", C.c_int32), ("first_misfit", C.c_int64 * 8), ("nonfinite", C.c_int64)]
+
+
+# include/fspann_narrow.h: which row types hold fp32 / fp64 rows exactly, the rows re-packed, a store narrowed in place (a table of
+# its own: those above stay as they are)
+_SIGS_NARROW = {
+    "fspann_rows_fit_dev": (_i, [_vp, _i64, _vp, _i, _i, C.c_uint32, _vp, C.POINTER(Fit)]),
+    "fspann_rows_narrow_dev": (_i, [_vp, _i64, _vp, _i, _i, _vp, _i, _i64p]),
+    "fspann_store_fit": (_i, [_vp, C.c_uint32, C.POINTER(Fit)]),
+    "fspann_store_narrow": (_i, [_vp, C.c_uint32, C.POINTER(_i)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
@@ -259,7 +273,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -301,3 +315,8 @@ def plan_symbols():
 def sweep_symbols():
     """the entry points of include/fspann_sweep.h"""
     return sorted(_SIGS_SWEEP)
+
+
+def narrow_symbols():
+    """the entry points of include/fspann_narrow.h"""
+    return sorted(_SIGS_NARROW)

@@ -359,7 +359,7 @@ void fspann_ctx_destroy(fspann_ctx* c) {
     free_devt(c->d_java_hash); free_devt(c->d_unmodelled);
     if (uint32_t* db = c->d_deleted_bits.exchange(nullptr)) (void)hipFree(db);
     if (uint8_t* ts = c->d_touch.exchange(nullptr)) (void)hipFree(ts);
-    free_dev(c->store_ok.p); free_dev(c->ws_touch.p);
+    free_dev(c->store_ok.p); free_dev(c->ws_touch.p); free_dev(c->ws_narrow.p);
     if (c->store_owned) free_dev(c->d_store);
     free_dev(c->ws_tickfix.p); free_dev(c->d_fixparams); free_dev(c->ws_gt.p); free_dev(c->bld_codes.p);
     free_dev(c->ws_route.p); free_dev(c->ws_refine.p); free_dev(c->ws_probe.p); free_dev(c->ws_ovf.p); free_dev(c->ws_search.p); free_dev(c->ws_retry.p); free_dev(c->ws_fallback.p); free_dev(c->ws_sweep.p); free_devt(c->d_inv); free_devt(c->d_ids_bk); free_devt(c->d_bin16);

@@ -19,6 +19,7 @@
 #include "groundtruth_u8.hip.h"
 #include "gt_validate.hip.h"
 #include "hostpipe.hip.h"
+#include "narrow.hip.h"
 #include "refine.hip.h"
 #include "refine_sweep.hip.h"
 #include "route.hip.h"
@@ -45,3 +46,4 @@
 #include "api_eval.hip.h"
 #include "api_gt_validate.hip.h"
 #include "api_sweep.hip.h"
+#include "api_narrow.hip.h"

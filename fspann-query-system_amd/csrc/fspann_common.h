@@ -234,6 +234,7 @@ struct fspann_ctx {
     unsigned store_ok_gen = 0;       // store_gen that store_ok was computed for (0: none)
     fspann::DevBuf store_ok;         // per store row: 1 = all dim values finite (api_touch.hip.h, computed at the first mark)
     fspann::DevBuf ws_touch;         // tile counts / offsets / total / handles of fspann_touch_count / _drain
+    fspann::DevBuf ws_narrow;        // FitResult / NarrowResult of the fit and narrow passes (api_narrow.hip.h)
 
     // scratch arenas (grown on demand, reused across calls)
     fspann::DevBuf ws_route;   // global hash/sort fallback for the route kernel

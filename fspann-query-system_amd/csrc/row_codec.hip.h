@@ -14,6 +14,10 @@
 //   quad_f32(in)         four consecutive elements (4-byte aligned for the byte types, 8-byte for the 16-bit ones) widened exactly to
 //                      fp32: Setup's input of a row-only type
 //   finite(x)          one raw element is finite
+//   fits(x)            the inverse direction (narrow.hip.h; every type but double): the fp32 or fp64 value x IS a value of T — nothing
+//                      is ever rounded, shifted or scaled.  The rule per type is engine._typed_rows' on the host; an fp64 x fits iff it
+//                      is a float and that float fits (every value of a narrower type is a float)
+//   narrow(x)          the element of a value that fits (a NaN becomes some NaN of T; of a value that does not fit: unspecified)
 //   slot_test          the granularity in which the Refine scan, which walks a slot two elements at a time, asks it for finiteness:
 //                      SlotTest::element  slot_finite(slot, e), one raw element (the scan: ok && slot_finite(e) && slot_finite(e + 1));
 //                      SlotTest::pair     pair_finite(slot, e), elements e and e + 1 (the scan: ok && pair_finite(e));
@@ -55,6 +59,9 @@ template <typename T, typename Slot> struct ByteRowCodec : RowCodecOf<T, Slot> {
 template <> struct RowCodec<float> : NativeRowCodec<float, fsp_f32x4> {
     static __device__ __forceinline__ double wide(slot v, int e) { return static_cast<double>(v[e]); }
     static __device__ __forceinline__ float piece_f32(fsp_u32x4 p, int e) { return __uint_as_float(p[e]); }
+    // an fp64 value is a float iff it survives the round trip by value (+-inf does; a NaN stays a NaN)
+    static __device__ __forceinline__ bool fits(double x) { return static_cast<double>(static_cast<float>(x)) == x || x != x; }
+    static __device__ __forceinline__ float narrow(double x) { return static_cast<float>(x); }
 };
 
 // FSPANN_F64: the element itself.  No kernel reads fp64 rows as fp32 pieces, and Setup takes them as they are.
@@ -76,6 +83,12 @@ template <> struct RowCodec<uint8_t> : ByteRowCodec<uint8_t, fsp_u32x4> {
         const uint32_t w = *reinterpret_cast<const uint32_t*>(in);
         return make_float4(static_cast<float>(w & 0xFFu), static_cast<float>((w >> 8) & 0xFFu), static_cast<float>((w >> 16) & 0xFFu), static_cast<float>(w >> 24));
     }
+    // In 0..255 (a NaN is not; -0.0 is, and narrows to 0: no result depends on that sign), and an integer: it
+    // survives v_cvt_i32_f32 and the way back.
+    static __device__ __forceinline__ bool fits(float x) { return x >= 0.0f && x <= 255.0f && static_cast<float>(static_cast<int32_t>(x)) == x; }
+    static __device__ __forceinline__ uint8_t narrow(float x) { return static_cast<uint8_t>(static_cast<int32_t>(x)); }
+    static __device__ __forceinline__ bool fits(double x) { return RowCodec<float>::fits(x) && fits(static_cast<float>(x)); }
+    static __device__ __forceinline__ uint8_t narrow(double x) { return narrow(static_cast<float>(x)); }
     // the byte ground truth's matrix cores take SIGNED bytes: x ^ 0x80 = x - 128 (groundtruth_u8.hip.h)
     static constexpr unsigned kToSigned = 0x80u;
 };
@@ -97,6 +110,11 @@ template <> struct RowCodec<int8_t> : ByteRowCodec<int8_t, fsp_u64x2> {
                            static_cast<float>(static_cast<int32_t>(w << 8) >> 24), static_cast<float>(static_cast<int32_t>(w) >> 24));
     }
     static constexpr unsigned kToSigned = 0u;      // already signed; ^ 0 compiles to nothing
+    // an integer in -128..127 (the test of FSPANN_U8 over another range)
+    static __device__ __forceinline__ bool fits(float x) { return x >= -128.0f && x <= 127.0f && static_cast<float>(static_cast<int32_t>(x)) == x; }
+    static __device__ __forceinline__ int8_t narrow(float x) { return static_cast<int8_t>(static_cast<int32_t>(x)); }
+    static __device__ __forceinline__ bool fits(double x) { return RowCodec<float>::fits(x) && fits(static_cast<float>(x)); }
+    static __device__ __forceinline__ int8_t narrow(double x) { return narrow(static_cast<float>(x)); }
 };
 
 // FSPANN_F16: a 16-byte slot is 8 IEEE binary16 elements (four dwords, two halves each, low element in the low 16 bits).  An
@@ -116,6 +134,12 @@ template <> struct RowCodec<_Float16> : NativeRowCodec<_Float16, fsp_f16x8> {
         const h4 w = *reinterpret_cast<const h4*>(in);
         return make_float4(static_cast<float>(w[0]), static_cast<float>(w[1]), static_cast<float>(w[2]), static_cast<float>(w[3]));
     }
+    // the round trip by value (v_cvt_f16_f32 and back): whichever way the conversion rounds, it gives x back iff x is a half;
+    // 65520 becomes +inf and does not fit, +-inf and NaN do
+    static __device__ __forceinline__ bool fits(float x) { return static_cast<float>(static_cast<_Float16>(x)) == x || x != x; }
+    static __device__ __forceinline__ _Float16 narrow(float x) { return static_cast<_Float16>(x); }
+    static __device__ __forceinline__ bool fits(double x) { return RowCodec<float>::fits(x) && fits(static_cast<float>(x)); }
+    static __device__ __forceinline__ _Float16 narrow(double x) { return narrow(static_cast<float>(x)); }
 };
 
 // FSPANN_BF16: the 2-byte geometry of FSPANN_F16.  An element is the fp32 whose bit pattern is the 16 bits shifted up, and can be
@@ -137,6 +161,16 @@ template <> struct RowCodec<fsp_bf16> : RowCodecOf<fsp_bf16, fsp_u32x4> {
     // of a mask and a compare on the raw dword.
     static __device__ __forceinline__ bool pair_finite(slot v, int e) { return __builtin_isfinite(piece_f32(v, e)) && __builtin_isfinite(piece_f32(v, e + 1)); }
     static constexpr SlotTest slot_test = SlotTest::pair;
+    // the low 16 bits of the fp32 pattern are zero; a NaN fits whatever its payload
+    static __device__ __forceinline__ bool fits(float x) { return (__float_as_uint(x) & 0xffffu) == 0 || x != x; }
+    // the upper 16 bits; a NaN whose payload sat in the low bits only stays a NaN (the wrapper's rule)
+    static __device__ __forceinline__ fsp_bf16 narrow(float x) {
+        uint32_t hi = __float_as_uint(x) >> 16;
+        if (x != x && (hi & 0x7fu) == 0) hi |= 0x40u;
+        return fsp_bf16{static_cast<uint16_t>(hi)};
+    }
+    static __device__ __forceinline__ bool fits(double x) { return RowCodec<float>::fits(x) && fits(static_cast<float>(x)); }
+    static __device__ __forceinline__ fsp_bf16 narrow(double x) { return narrow(static_cast<float>(x)); }
 };
 
 // FSPANN_F8E4M3: the byte geometry of FSPANN_U8.  An element is an OCP e4m3fn value and, unlike a byte, can be NaN (0x7F / 0xFF;
@@ -187,6 +221,26 @@ template <> struct RowCodec<fsp_f8e4m3> : RowCodecOf<fsp_f8e4m3, fsp_u64x2> {
         return (((w & 0x7f7f7f7fu) + 0x01010101u) & 0x80808080u) == 0;
     }
     static constexpr SlotTest slot_test = SlotTest::pair;
+    // u = |x| * 2^9 as an integer (the scaling is exact; |x| <= 448 keeps it below 2^18): x is an e4m3 value iff t is that integer and
+    // has at most four significant bits, i.e. nothing below the three bits under its top bit h.  NaN fits, +-inf does not (the
+    // format has none).  Spelled out in integers, not through the hardware's rounding conversion: the rule is the wrapper's.
+    static __device__ __forceinline__ bool fits(float x) {
+        const float a = __builtin_fabsf(x);
+        if (!(a <= 448.0f)) return x != x;
+        const float t = a * 512.0f;
+        const uint32_t u = static_cast<uint32_t>(t);
+        const int h = 31 - __builtin_clz(u | 8u);          // >= 3
+        return static_cast<float>(u) == t && (u & ((1u << (h - 3)) - 1u)) == 0;
+    }
+    // u < 8: a subnormal (or zero), E = 0 and M = u; else E = h - 2 and M = the three bits under the top one.  -0.0 keeps its sign.
+    static __device__ __forceinline__ fsp_f8e4m3 narrow(float x) {
+        const uint32_t u = static_cast<uint32_t>(__builtin_fabsf(x) * 512.0f);
+        const int h = 31 - __builtin_clz(u | 8u);
+        const uint32_t mag = u < 8u ? u : (static_cast<uint32_t>(h - 2) << 3) | ((u >> (h - 3)) & 7u);
+        return fsp_f8e4m3{static_cast<uint8_t>(x != x ? 0x7fu : mag | ((__float_as_uint(x) >> 24) & 0x80u))};
+    }
+    static __device__ __forceinline__ bool fits(double x) { return RowCodec<float>::fits(x) && fits(static_cast<float>(x)); }
+    static __device__ __forceinline__ fsp_f8e4m3 narrow(double x) { return narrow(static_cast<float>(x)); }
 };
 
 // every row of the table has its codec, and every codec fills a 16-byte slot

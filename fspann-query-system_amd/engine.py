@@ -592,6 +592,69 @@ class FspannContext:
         N.check(self.L.fspann_store_attach_dev(self._h, int(n), ptr, dtype))
         self._store_n = int(n)
 
+    # -- lossless narrowing on the device (include/fspann_narrow.h) -----------------------
+    @staticmethod
+    def _allowed(allowed):
+        """`allowed` of the narrowing calls as the C mask: None = every type, an int as it is, else an iterable of FSPANN_* codes"""
+        if allowed is None:
+            return 0
+        if isinstance(allowed, (int, np.integer)):
+            return int(allowed)
+        return sum({1 << int(t) for t in allowed})
+
+    @staticmethod
+    def _kept(code):
+        """what store_dtype reports for an FSPANN_* code: the numpy dtype, or the package's marker where numpy has none"""
+        return {N.F32: np.dtype(np.float32), N.F64: np.dtype(np.float64), N.U8: np.dtype(np.uint8), N.I8: np.dtype(np.int8),
+                N.F16: np.dtype(np.float16), N.BF16: bfloat16, N.F8E4M3: float8_e4m3fn}[code]
+
+    @staticmethod
+    def _fit_dict(f):
+        return dict(fits=int(f.fits), narrowest=int(f.narrowest), first_misfit=np.array(f.first_misfit[:7], np.int64), nonfinite=int(f.nonfinite))
+
+    def rows_fit_dev(self, n, rows_ptr, dtype, dim, allowed=0, row_fits_ptr=0) -> N.Fit:
+        f = N.Fit()
+        N.check(self.L.fspann_rows_fit_dev(self._h, n, rows_ptr, dtype, dim, allowed, row_fits_ptr or None, C.byref(f)))
+        return f
+
+    def rows_narrow_dev(self, n, src_ptr, src_dtype, dim, dst_ptr, dst_dtype) -> None:
+        """src [n][dim] re-packed as the narrower dst_dtype, both in device memory; FspannArgumentError when an element is not a value of it"""
+        N.check(self.L.fspann_rows_narrow_dev(self._h, n, src_ptr, src_dtype, dim, dst_ptr, dst_dtype, None))
+
+    def rows_fit(self, rows, allowed=None):
+        """Which row types hold the fp32 or fp64 array rows [n][dim] exactly, decided on the device: dict(fits = mask of
+        1 << FSPANN_x, narrowest = the FSPANN_* code the order of include/fspann_narrow.h picks among fits & allowed, first_misfit
+        [7] = per code the flat index of the first element that is not a value of it or -1, nonfinite, row_fits [n] = the mask per row)."""
+        v = np.ascontiguousarray(rows)
+        if v.dtype not in (np.float32, np.float64):
+            v = v.astype(np.float64)
+        if v.ndim != 2:
+            raise N.FspannArgumentError("rows_fit: rows are a 2-D array [n][dim]")
+        with self._Dev(self) as dv:
+            rf = dv.new(v.shape[0], np.uint8)
+            f = self.rows_fit_dev(v.shape[0], dv.up(v), _dt(v), v.shape[1], self._allowed(allowed), rf)
+            return dict(self._fit_dict(f), row_fits=dv.down(rf))
+
+    def store_fit(self, allowed=None):
+        """rows_fit over the resident store (no row mask)"""
+        f = N.Fit()
+        N.check(self.L.fspann_store_fit(self._h, self._allowed(allowed), C.byref(f)))
+        return self._fit_dict(f)
+
+    def store_narrow(self, allowed=None):
+        """Re-pack the resident store, in HBM, as the narrowest allowed row type that holds every element exactly (nothing is ever
+        rounded; when nothing narrower fits the store stays as it is).  Returns what store_dtype then reports: a numpy dtype, or the
+        package's marker."""
+        code = C.c_int(-1)
+        N.check(self.L.fspann_store_narrow(self._h, self._allowed(allowed), C.byref(code)))
+        self.store_dtype = self._kept(code.value)
+        return self.store_dtype
+
+    def store_set_narrowest(self, vectors, allowed=None):
+        """store_set(vectors) as they are (fp32 or fp64), then store_narrow(allowed): the caller need not know what the data holds"""
+        self.store_set(vectors)
+        return self.store_narrow(allowed)
+
     def hbm_read_peak(self, nbytes=1 << 32, reps=5) -> float:
         """GB/s of a pure-load kernel over `nbytes` of HBM on this device (bench.py roofline.peak_measured)."""
         v = C.c_double(0.0)

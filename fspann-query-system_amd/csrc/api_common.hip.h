@@ -1,4 +1,4 @@
-// api_common.hip.h — helpers shared by every entry point of include/fspann.h: sizes, the pinned block, guarded(), the context checks
+// api_common.hip.h — helpers shared by every entry point of include/fspann.h: sizes, guarded(), the context checks, the work areas
 // Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
 
@@ -38,22 +38,6 @@ template <typename T> void free_devt(T*& p) {
     p = nullptr;
 }
 
-constexpr size_t kPinBytes = size_t(1) << 20;
-// the context's pinned block (allocated at the first small host-pointer call; false: none, the general path runs)
-bool pin_block(fspann_ctx* c) {
-    if (!c->h_pin) {
-        if (hipHostMalloc(&c->h_pin, kPinBytes, hipHostMallocDefault) != hipSuccess) { c->h_pin = nullptr; (void)hipGetLastError(); }
-        else if (hipHostGetDevicePointer(&c->d_pin, c->h_pin, 0) != hipSuccess) { c->d_pin = nullptr; (void)hipGetLastError(); }
-    }
-    return c->h_pin != nullptr;
-}
-// Calls of a handful of queries (QueryService.search is one token per call, ForwardSecureANNSystem.java:636): the kernels read their
-// arguments from the pinned block and write their results into it THROUGH THE BUS — no copy command either way, one launch sequence and
-// one synchronisation (a copy command costs ~8 us of the stream's time whatever its size; a few KB written by the kernel itself cost
-// less).  More queries than this go through the block with one copy each way: thousands of scattered 4-byte stores over PCIe do not.
-constexpr int64_t kZeroCopyMaxQ = 4;
-bool zero_copy_ok(fspann_ctx* c, int64_t nq) { return nq <= kZeroCopyMaxQ && c->knob_zero_copy && pin_block(c) && c->d_pin != nullptr; }
-
 int resolve_unmodelled(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int probe_override, int32_t limit, int64_t cap, int32_t* ids_dev,
                        int32_t* score_dev, int32_t* count_dev, int32_t* kept_dev, int32_t* raw_dev, int64_t* resolved_out, int64_t* left_out);   // api_ext.hip.h
 
@@ -92,7 +76,34 @@ inline fspann_ctx* index_owner(fspann_ctx* c) { return c->share_parent ? c->shar
         if ((c)->share_children.load() > 0) return fail(FSPANN_E_STATE, "the index is shared with %d clone(s): destroy them first", (c)->share_children.load()); \
     } while (0)
 
+// One Refine job on the device: what the entry point or internal caller builds once and every layer down to the launch and the
+// touched-record mark reads.  gather: the rows are the resident store's, row j of query qi is rows[cand_ids[qi * B + j]]; else
+// dense blocks [nq][B][dim].  qlist / qcount (device, optional): over the queries qlist[0 .. *qcount) only, each at its own index.
+struct RefineJob {
+    const void* q; int q_dtype;
+    const void* rows; int row_dtype; bool gather;
+    int64_t nq, B;
+    const int32_t *cand_ids, *cand_count;
+    int k;
+    int32_t* out_ids; double* out_dist; int32_t *out_count, *scored;
+    const int32_t *qlist = nullptr, *qcount = nullptr;
+};
+// ... over the context's resident store
+RefineJob store_job(const fspann_ctx* c, const void* q, int q_dtype, int64_t nq, int64_t B, const int32_t* cand_ids, const int32_t* cand_count, int k, int32_t* out_ids,
+                    double* out_dist, int32_t* out_count, int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
+    return {q, q_dtype, c->d_store, c->store_dtype, true, nq, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount};
+}
 
+// The one dispatch over (query dtype, row dtype) of a scan: f(query type tag, row type tag) -> int, or the refusal.
+template <class F> int with_refine_types(int q_dtype, int row_dtype, F&& f) {
+    int rc = FSPANN_OK;
+    bool launched = false;
+    with_query_type(q_dtype, [&](auto tq) { launched = with_row_type(row_dtype, [&](auto tc) { rc = f(tq, tc); }); });
+    if (launched) return rc;
+    if ((rc = refuse_row_only(q_dtype, "q_dtype"))) return rc;
+    if (!is_query_dtype(q_dtype)) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
+    return fail(FSPANN_E_ARG, "unknown dtype");
+}
 
 // Work areas.  A Carver hands out 256-byte-rounded pieces of a buffer in order; over a null base it only adds up the size.  An area
 // is a struct of pointers with ONE description of its layout, lay(base, dims...), which carves its pieces and returns its size.

@@ -96,7 +96,6 @@ int launch_encode(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_d
     return FSPANN_OK;
 }
 
-
 }  // namespace
 
 extern "C" {
@@ -124,44 +123,24 @@ int fspann_encode(fspann_ctx* c, int64_t nq, const void* q, int dtype, uint64_t*
     if (int rc = refuse_row_only(dtype, "dtype")) return rc;
     if (dtype != FSPANN_F32 && dtype != FSPANN_F64) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     const size_t esz = dtype == FSPANN_F64 ? 8 : 4;
-    const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * esz;
-    const size_t cb = static_cast<size_t>(nq) * c->TD * c->W * 8;
+    const size_t cb = static_cast<size_t>(nq) * c->TD * c->W * 8, bb = static_cast<size_t>(nq) * 4;
     const size_t hb = hashes ? static_cast<size_t>(nq) * c->P_total * 4 : 0;
     return guarded([&]() -> int {
+    // a handful of queries (QueryTokenFactory.create is one vector per call): through the mapped pinned block, no copy commands
+    EncodeIo io(q, static_cast<size_t>(nq) * c->cfg.dim * esz, cb, bb, hb);
+    io.choose(c, nq, EncodeIo::policy);
+    std::vector<int32_t> bad_direct(io.t == Transport::Direct ? static_cast<size_t>(nq) : 0);
+    io.out(EncodeIo::Codes, codes, cb); io.out(EncodeIo::Bad, io.t == Transport::Direct ? bad_direct.data() : nullptr, bb); io.out(EncodeIo::Hashes, hashes, hb);
     int rc;
-    {   // a handful of queries (QueryTokenFactory.create is one vector per call): through the mapped pinned block, no copy commands
-        auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
-        const size_t o_c = al(qb), o_b = o_c + al(cb), o_h = o_b + al(static_cast<size_t>(nq) * 4), tot = o_h + al(hb);
-        if (tot <= kPinBytes && zero_copy_ok(c, nq)) {
-            unsigned char* hp = static_cast<unsigned char*>(c->h_pin), *dp = static_cast<unsigned char*>(c->d_pin);
-            std::memcpy(hp, q, qb);
-            rc = fspann_encode_dev(c, nq, dp, dtype, reinterpret_cast<uint64_t*>(dp + o_c), hashes ? reinterpret_cast<int32_t*>(dp + o_h) : nullptr,
-                                   reinterpret_cast<int32_t*>(dp + o_b));
-            if (rc) return rc;
-            FSP_HIP(hipStreamSynchronize(c->stream));
-            const int32_t* bad = reinterpret_cast<const int32_t*>(hp + o_b);
-            for (int64_t i = 0; i < nq; i++)
-                if (bad[i]) return fail(FSPANN_E_ARG, "Vector contains NaN/Inf (query %lld)", (long long)i);  // Coding.java:360
-            std::memcpy(codes, hp + o_c, cb);
-            if (hashes) std::memcpy(hashes, hp + o_h, hb);
-            return FSPANN_OK;
-        }
-    }
-    if ((rc = ensure(c, c->ws_io[0], qb))) return rc;
-    if ((rc = ensure(c, c->ws_io[1], cb))) return rc;
-    if ((rc = ensure(c, c->ws_io[2], static_cast<size_t>(nq) * 4))) return rc;
-    if (hashes && (rc = ensure(c, c->ws_io[3], hb))) return rc;
-    FSP_HIP(hipMemcpyAsync(c->ws_io[0].p, q, qb, hipMemcpyHostToDevice, c->stream));
-    rc = fspann_encode_dev(c, nq, c->ws_io[0].p, dtype, static_cast<uint64_t*>(c->ws_io[1].p),
-                           hashes ? static_cast<int32_t*>(c->ws_io[3].p) : nullptr, static_cast<int32_t*>(c->ws_io[2].p));
-    if (rc) return rc;
-    std::vector<int32_t> bad(static_cast<size_t>(nq));
-    FSP_HIP(hipMemcpyAsync(codes, c->ws_io[1].p, cb, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipMemcpyAsync(bad.data(), c->ws_io[2].p, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost, c->stream));
-    if (hashes) FSP_HIP(hipMemcpyAsync(hashes, c->ws_io[3].p, hb, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = io.begin(c)) || (rc = io.send(c))) return rc;
+    rc = fspann_encode_dev(c, nq, io.dev_up<void>(c, 0), dtype, io.dev_down<uint64_t>(c, EncodeIo::Codes), io.dev_down<int32_t>(c, EncodeIo::Hashes),
+                           io.dev_down<int32_t>(c, EncodeIo::Bad));
+    if (rc || (rc = io.fetch(c))) return rc;
     FSP_HIP(hipStreamSynchronize(c->stream));
+    const int32_t* bad = static_cast<const int32_t*>(io.landed(c, EncodeIo::Bad));
     for (int64_t i = 0; i < nq; i++)
         if (bad[i]) return fail(FSPANN_E_ARG, "Vector contains NaN/Inf (query %lld)", (long long)i);  // Coding.java:360
+    io.unpack(c);
     return FSPANN_OK;
     });
 }
@@ -183,6 +162,5 @@ int64_t fspann_last_encode_rechecked(fspann_ctx* c) {
         hipMemcpy(&n, c->ws_fix.p, 8, hipMemcpyDeviceToHost) != hipSuccess) return FSPANN_E_DEVICE;
     return static_cast<int64_t>(n);
 }
-
 
 }  // extern "C"

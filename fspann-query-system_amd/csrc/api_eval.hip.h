@@ -35,11 +35,11 @@ int fallback_probes(const fspann_ctx* c, int probe_override) {
 int search_list_dev(fspann_ctx* c, const SearchBufs& s, int probes, const int32_t* list, const int32_t* count, const int32_t* member) {
     int rc;
     if ((rc = route_list_dev(c, s.nq, s.sa.codes, probes, s.B, s.sa.sel, s.sa.cnt, list, count))) return rc;
-    if ((rc = refine_store_list(c, s.nq, s.q, s.q_dtype, s.B, s.sa.sel, s.sa.cnt, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, list, count))) return rc;
+    if ((rc = refine_store_list(c, s, list, count))) return rc;
     if ((rc = launch_pick(c, s.nq, MemberRetryRule{pick_in(s), member, s.retried}, s.list, s.count))) return rc;
     if (effective_probes(c, probes) == effective_probes(c, 10)) return FSPANN_OK;
     if ((rc = route_list_dev(c, s.nq, s.sa.codes, 10, s.B, s.sa.sel, s.sa.cnt, s.list, s.count))) return rc;
-    return refine_store_list(c, s.nq, s.q, s.q_dtype, s.B, s.sa.sel, s.sa.cnt, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, s.list, s.count);
+    return refine_store_list(c, s, s.list, s.count);
 }
 
 }  // namespace

@@ -173,11 +173,11 @@ int fspann_set_deleted(fspann_ctx* c, const int32_t* handles, int64_t n, int fla
         }
         // On THIS context's stream, then waited for: Route calls enqueued (on any context of the family) after this call
         // returns see the change; calls already in flight see the old or the new flag — as a JVM query racing a delete does.
-        int rc = ensure(c, c->ws_io[6], static_cast<size_t>(n) * 4);
+        int rc = ensure(c, c->ws_io[kIoHandles], static_cast<size_t>(n) * 4);
         if (rc) return rc;
-        FSP_HIP(hipMemcpyAsync(c->ws_io[6].p, handles, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, c->stream));
+        FSP_HIP(hipMemcpyAsync(c->ws_io[kIoHandles].p, handles, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(set_deleted_bits_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, c->stream,
-                           static_cast<const int32_t*>(c->ws_io[6].p), n, flag ? 1 : 0, bits);
+                           static_cast<const int32_t*>(c->ws_io[kIoHandles].p), n, flag ? 1 : 0, bits);
         FSP_HIP(hipGetLastError());
         FSP_HIP(hipStreamSynchronize(c->stream));
         return FSPANN_OK;

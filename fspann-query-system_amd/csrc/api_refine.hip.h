@@ -43,18 +43,40 @@ ScanPlan scan_plan(const fspann_ctx* c, int64_t nq, const TC* cand, int nchunks)
     return s;
 }
 
+// One way to launch a scan or merge kernel of kRefRows threads.  may_time — the non-listed scan and stream dispatches, the hand-over
+// and the running top-k among them; never a listed dispatch or a merge: start/stop events attached to this very dispatch when it
+// is the rt_every-th one seen while scan timing is on and events are left (fspann_refine_timing_begin).
+template <class K, class... A>
+int launch_refine_kernel(fspann_ctx* c, bool may_time, K kern, unsigned grid, size_t lds, A... args) {
+    if (may_time && c->rt_on && (c->rt_seen++ % c->rt_every) == 0 && c->rt_used + 2 <= c->rt_events.size()) {
+        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, c->rt_events[c->rt_used], c->rt_events[c->rt_used + 1], 0, args...);
+        c->rt_used += 2;
+    } else {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, args...);
+    }
+    return FSPANN_OK;
+}
+// ... of a kernel whose launch can need more than the default 64 KB of LDS: its ceiling raised to `ceiling` first where that is beyond
+// them (the stream kernels never do: a 128-byte tile plus its 16-byte pad over kRefRows rows is 36 KB)
+template <class K, class... A>
+int launch_refine_kernel_lds(fspann_ctx* c, bool may_time, K kern, unsigned grid, size_t lds, size_t ceiling, A... args) {
+    if (ceiling > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, ceiling)) return rc;
+    return launch_refine_kernel(c, may_time, kern, grid, lds, args...);
+}
+
 template <typename TC, typename TQ, int DC, bool GATHER>
-int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids,
-                     const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
-                     int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
+int launch_refine_dc(fspann_ctx* c, const RefineJob& j) {
     constexpr bool kStreamTile = DC * sizeof(TC) == 128;
+    // fp32 queries over rows of at most four bytes at the default tile width (128 bytes; no hand-over kernel reads FSPANN_F64 rows)
+    constexpr bool kHandOver = DtypeOf<TQ>::id == FSPANN_F32 && sizeof(TC) <= 4 && kStreamTile;
     // qlist / qcount (device, the retry pass of fspann_search_retry_dev): only the queries qlist[0 .. *qcount) are scored, each at its
     // own index; the launches are sized for nq and their workgroups past the count leave at once.  One partial list per chunk
     // (no running top-k), no hand-over, no kernel-attached timing.
-    const bool listed = qlist != nullptr;
-    const int d = c->cfg.dim;
-    const int nchunks = static_cast<int>((B + kRefRows - 1) / kRefRows);
-    const ScanPlan sp = scan_plan<TC, DC, GATHER>(c, nq, cand, nchunks);
+    const bool listed = j.qlist != nullptr;
+    const int64_t nq = j.nq;
+    const int k = j.k;
+    const int nchunks = static_cast<int>((j.B + kRefRows - 1) / kRefRows);
+    const ScanPlan sp = scan_plan<TC, DC, GATHER>(c, nq, static_cast<const TC*>(j.rows), nchunks);
     const size_t lds = sp.lds;
     RefinePartial* partial = nullptr;
     int32_t* pcnt = nullptr;
@@ -78,90 +100,51 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
         partial = static_cast<RefinePartial*>(c->ws_refine.p);
         pcnt = reinterpret_cast<int32_t*>(static_cast<char*>(c->ws_refine.p) + ((pb + 15) & ~size_t(15)));
     }
-    const bool vec = sp.vec;
-    const unsigned grid = sp.grid;
-    const RefineArgs<TC, TQ> ra{q, cand, GATHER ? c->store_n : 0, B, d, cand_ids, cand_count, k, nchunks, out_ids, out_dist, out_count, scored, partial, pcnt, npieces, cpp, c->dbg_route};
-    auto launch = [&](auto kern) -> int {
-        if (lds > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, lds)) return rc;
-        if (c->rt_on && (c->rt_seen++ % c->rt_every) == 0 && c->rt_used + 2 <= c->rt_events.size()) {   // start/stop events attached to this very dispatch
-            hipExtLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, c->rt_events[c->rt_used], c->rt_events[c->rt_used + 1], 0, ra);
-            c->rt_used += 2;
-        } else {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, ra);
+    const RefineArgs<TC, TQ> ra{static_cast<const TQ*>(j.q), static_cast<const TC*>(j.rows), GATHER ? c->store_n : 0, j.B, c->cfg.dim, j.cand_ids, j.cand_count, k, nchunks,
+                                j.out_ids, j.out_dist, j.out_count, j.scored, partial, pcnt, npieces, cpp, c->dbg_route};
+    // The kernel of this scan.  As a stream: stream_wgs workgroups per CU, each walking several (query, chunk) units with the loads
+    // of the next tile in flight across unit boundaries (refine_stream_run); else one workgroup per (query, chunk).  Hand-over: the
+    // batch's Route ran with a hand-over buffer, the scan's workgroups finish its PENDING queries first (tick.hip.h).
+    enum class Scan { ListStream, ListChunks, HandOver, Runs, Stream, Chunks };
+    const bool stream = kStreamTile && sp.stream;
+    const Scan scan = listed ? (stream ? Scan::ListStream : Scan::ListChunks)
+                      : !stream ? Scan::Chunks
+                      : (kHandOver && c->refine_fix_dev && nchunks == 1) ? Scan::HandOver
+                      : npieces > 0 ? Scan::Runs : Scan::Stream;
+    const unsigned sgrid = sp.sgrid(nq * nlists);
+    int rc = FSPANN_OK;
+    if (scan == Scan::ListStream) {
+        if constexpr (kStreamTile) rc = launch_refine_kernel(c, false, refine_stream_list_kernel<TC, TQ, DC, GATHER>, sgrid, lds, ra, j.qlist, j.qcount);
+    } else if (scan == Scan::ListChunks) {
+        rc = sp.vec ? launch_refine_kernel_lds(c, false, refine_scan_list_kernel<TC, TQ, DC, true, GATHER>, sp.grid, lds, lds, ra, j.qlist, j.qcount)
+                    : launch_refine_kernel_lds(c, false, refine_scan_list_kernel<TC, TQ, DC, false, GATHER>, sp.grid, lds, lds, ra, j.qlist, j.qcount);
+    } else if (scan == Scan::HandOver) {
+        if constexpr (kHandOver) {
+            rc = launch_refine_kernel_lds(c, true, refine_stream_fix_kernel<TC, GATHER>, sgrid, std::max(lds, c->refine_fix_lds), 159 * 1024, ra, nq,
+                                          static_cast<const RouteParams*>(c->refine_fix_dev));
+            if (!rc) c->refine_fix_used = true;
         }
-        return FSPANN_OK;
-    };
-    int lrc = FSPANN_OK;
-    bool streamed = false;
-    if (listed) {
-        if constexpr (kStreamTile) if (sp.stream) {
-            hipLaunchKernelGGL((refine_stream_list_kernel<TC, TQ, DC, GATHER>), dim3(sp.sgrid(nq * nchunks)), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
-            streamed = true;
-        }
-        if (!streamed) {
-            auto kern = vec ? refine_scan_list_kernel<TC, TQ, DC, true, GATHER> : refine_scan_list_kernel<TC, TQ, DC, false, GATHER>;
-            if (lds > 64 * 1024) if (int rc = raise_lds_ceiling(c, kern, lds)) return rc;
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kRefRows), lds, c->stream, ra, qlist, qcount);
-        }
-    } else if constexpr (kStreamTile) if (sp.stream) {
-        // the scan as a stream: stream_wgs workgroups per CU, each walking several (query, chunk) units with the loads
-        // of the next tile in flight across unit boundaries (refine_stream_run)
-        const unsigned sgrid = sp.sgrid(nq * nlists);
-        const bool timed = c->rt_on && (c->rt_seen++ % c->rt_every) == 0 && c->rt_used + 2 <= c->rt_events.size();
-        hipEvent_t ev0 = timed ? c->rt_events[c->rt_used] : nullptr, ev1 = timed ? c->rt_events[c->rt_used + 1] : nullptr;
-        if (timed) c->rt_used += 2;
-        bool fixed = false;
-        // fp32 queries over rows of at most four bytes at the default tile width (128 bytes; no hand-over kernel reads FSPANN_F64 rows)
-        if constexpr (DtypeOf<TQ>::id == FSPANN_F32 && sizeof(TC) <= 4 && DC * sizeof(TC) == 128) {
-            if (c->refine_fix_dev && nchunks == 1) {
-                // the batch's Route ran with a hand-over buffer: the scan's workgroups finish its PENDING queries first (tick.hip.h)
-                auto hand_over = [&](auto fk) -> int {
-                    const size_t flds = std::max(lds, c->refine_fix_lds);
-                    if (int rc = raise_lds_ceiling(c, fk, 159 * 1024)) return rc;
-                    if (timed) hipExtLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ev0, ev1, 0, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
-                    else hipLaunchKernelGGL(fk, dim3(sgrid), dim3(kRefRows), flds, c->stream, ra, nq, static_cast<const RouteParams*>(c->refine_fix_dev));
-                    return FSPANN_OK;
-                };
-                auto fk = refine_stream_fix_kernel<TC, GATHER>;
-                if ((lrc = hand_over(fk))) return lrc;
-                fixed = true;
-                c->refine_fix_used = true;
-            }
-        }
-        if (!fixed) {
-            if constexpr (!GATHER) {
-                if (npieces > 0) {
-                    auto kern = refine_stream_kernel<TC, TQ, DC, false, true>;
-                    if (timed) hipExtLaunchKernelGGL(kern, dim3(sgrid), dim3(kRefRows), lds, c->stream, ev0, ev1, 0, ra, nq);
-                    else hipLaunchKernelGGL(kern, dim3(sgrid), dim3(kRefRows), lds, c->stream, ra, nq);
-                    fixed = true;
-                }
-            }
-        }
-        if (!fixed) {
-            auto kern = refine_stream_kernel<TC, TQ, DC, GATHER>;
-            if (timed) hipExtLaunchKernelGGL(kern, dim3(sgrid), dim3(kRefRows), lds, c->stream, ev0, ev1, 0, ra, nq);
-            else hipLaunchKernelGGL(kern, dim3(sgrid), dim3(kRefRows), lds, c->stream, ra, nq);
-        }
-        streamed = true;
+    } else if (scan == Scan::Runs) {
+        if constexpr (kStreamTile && !GATHER) rc = launch_refine_kernel(c, true, refine_stream_kernel<TC, TQ, DC, false, true>, sgrid, lds, ra, nq);
+    } else if (scan == Scan::Stream) {
+        if constexpr (kStreamTile) rc = launch_refine_kernel(c, true, refine_stream_kernel<TC, TQ, DC, GATHER>, sgrid, lds, ra, nq);
+    } else {
+        rc = sp.vec ? launch_refine_kernel_lds(c, true, refine_scan_kernel<TC, TQ, DC, true, GATHER>, sp.grid, lds, lds, ra)
+                    : launch_refine_kernel_lds(c, true, refine_scan_kernel<TC, TQ, DC, false, GATHER>, sp.grid, lds, lds, ra);
     }
-    if (!listed && !streamed) lrc = vec ? launch(refine_scan_kernel<TC, TQ, DC, true, GATHER>) : launch(refine_scan_kernel<TC, TQ, DC, false, GATHER>);
-    if (lrc) return lrc;
+    if (rc) return rc;
     FSP_HIP(hipGetLastError());
-    if (npieces > 0 && !streamed) return fail(FSPANN_E_STATE, "refine: the running top-k was planned but the streaming scan did not run");
+    if (npieces > 0 && !stream) return fail(FSPANN_E_STATE, "refine: the running top-k was planned but the streaming scan did not run");
     if (nlists > 1) {
         // the merge of a query's partial lists (one per run, or per chunk), all their keys in LDS when they fit (two workgroups per CU
         // at least); over the listed queries when there is a list
         const size_t mlds = static_cast<size_t>(nlists) * k * 8 + static_cast<size_t>(nlists) * 4 + 16;
         const bool in_lds = mlds <= 72 * 1024;
-        auto merge = [&](auto mk, auto... list) -> int {
-            if (in_lds && mlds > 64 * 1024) if (int rc = raise_lds_ceiling(c, mk, 72 * 1024)) return rc;
-            hipLaunchKernelGGL(mk, dim3(static_cast<unsigned>(nq)), dim3(256), in_lds ? mlds : static_cast<size_t>(nlists) * 4 + 16, c->stream, partial, pcnt, nlists, k,
-                               out_ids, out_dist, out_count, scored, list...);
-            return FSPANN_OK;
+        auto merge = [&](auto mk, auto... list) {
+            return launch_refine_kernel_lds(c, false, mk, static_cast<unsigned>(nq), in_lds ? mlds : static_cast<size_t>(nlists) * 4 + 16, in_lds ? 72 * 1024 : 0, partial, pcnt,
+                                            nlists, k, j.out_ids, j.out_dist, j.out_count, j.scored, list...);
         };
-        int rc;
-        if (listed) rc = in_lds ? merge(refine_merge_list_kernel<true>, qlist, qcount) : merge(refine_merge_list_kernel<false>, qlist, qcount);
+        if (listed) rc = in_lds ? merge(refine_merge_list_kernel<true>, j.qlist, j.qcount) : merge(refine_merge_list_kernel<false>, j.qlist, j.qcount);
         else rc = in_lds ? merge(refine_merge_kernel<true>) : merge(refine_merge_kernel<false>);
         if (rc) return rc;
         FSP_HIP(hipGetLastError());
@@ -169,45 +152,51 @@ int launch_refine_dc(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int
     return FSPANN_OK;
 }
 
-template <typename TC, typename TQ, bool GATHER>
-int launch_refine_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids,
-                    const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
-                    int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
-    int rc = with_tile_width<TC>(c, [&](auto dc) {
-        return launch_refine_dc<TC, TQ, decltype(dc)::value, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount);
+// The one way from a job to its scan: (query dtype, row dtype, gather or dense) -> the tile width -> the launch, and the
+// touched-record set (api_touch.hip.h) behind it: the rows this launch scores (nothing while tracking is off).
+int refine_run(fspann_ctx* c, const RefineJob& j) {
+    return with_refine_types(j.q_dtype, j.row_dtype, [&](auto tq, auto tc) -> int {
+        using TQ = typename decltype(tq)::type;
+        using TC = typename decltype(tc)::type;
+        auto run = [&](auto gather) -> int {
+            constexpr bool GATHER = decltype(gather)::value;
+            int rc = with_tile_width<TC>(c, [&](auto dc) { return launch_refine_dc<TC, TQ, decltype(dc)::value, GATHER>(c, j); });
+            return rc ? rc : touch_mark<TC, TQ, GATHER>(c, j);
+        };
+        return j.gather ? run(std::true_type{}) : run(std::false_type{});
     });
-    if (rc) return rc;
-    // the touched-record set (api_touch.hip.h): the rows this launch scores, marked behind it (nothing while tracking is off)
-    return touch_mark<TC, TQ, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, qlist, qcount);
 }
 
-// The one way from (row dtype, query dtype) to the scan: rows at `rows` (dense blocks, or GATHER: the resident store), over every
-// query or (qlist / qcount, device; the retry pass and its host finish) over the queries qlist[0 .. *qcount) only.
-template <bool GATHER>
-int refine_typed(fspann_ctx* c, int row_dtype, int q_dtype, int64_t nq, const void* q_dev, const void* rows, int64_t B, const int32_t* cand_ids_dev,
-                 const int32_t* cand_count_dev, int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev,
-                 const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
-    int rc = FSPANN_OK;
-    bool launched = false;
-    with_query_type(q_dtype, [&](auto tq) {
-        launched = with_row_type(row_dtype, [&](auto tc) {
-            using TQ = typename decltype(tq)::type;
-            using TC = typename decltype(tc)::type;
-            rc = launch_refine_t<TC, TQ, GATHER>(c, nq, static_cast<const TQ*>(q_dev), static_cast<const TC*>(rows), B, cand_ids_dev, cand_count_dev, k, out_ids_dev,
-                                                 out_dist_dev, out_count_dev, scored_dev, qlist, qcount);
-        });
-    });
-    if (launched) return rc;
-    if ((rc = refuse_row_only(q_dtype, "q_dtype"))) return rc;
-    if (!is_query_dtype(q_dtype)) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
-    return fail(FSPANN_E_ARG, "unknown dtype");
+// The argument checks of the four Refine calls (ok: every buffer the call needs is there); the caller returns on rc or nq == 0.
+int check_refine_args(int64_t nq, int64_t B, int k, bool ok) {
+    if (nq < 0 || B <= 0) return fail(FSPANN_E_ARG, "nq < 0 or B <= 0");
+    if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");  // QueryTokenFactory.java:65
+    if (nq > 0 && !ok) return fail(FSPANN_E_NULL, "refine buffer is null");
+    return FSPANN_OK;
 }
 
-// fspann_refine_store_dev over the queries qlist[0 .. *qcount) only (device list; the retry pass and its host finish).
-int refine_store_list(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype, int64_t B, const int32_t* cand_ids_dev, const int32_t* cand_count_dev,
-                      int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev, const int32_t* qlist, const int32_t* qcount) {
-    return refine_typed<true>(c, c->store_dtype, q_dtype, nq, q_dev, c->d_store, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev,
-                              qlist, qcount);
+// fspann_refine / fspann_refine_store behind their checks: j holds the caller's HOST pointers (gather: no rows); staged, then the
+// _dev twin over the device addresses, then every output handed back.
+// Small calls: query, ids and counts go up in ONE pinned block and every output comes down in one (the candidate rows keep
+// their own copy straight from the caller's buffer): three transfers and one synchronisation instead of eight and one.  A handful
+// of queries: query, ids and counts are read from the mapped pinned block and the results written into it by the kernel itself.
+int refine_staged(fspann_ctx* c, const RefineJob& j, StagePolicy policy) {
+    const size_t nq = static_cast<size_t>(j.nq), d = c->cfg.dim, nb = nq * 4, ob_i = nq * j.k * 4, ob_d = nq * j.k * 8;
+    RefineIo io(j.q, nq * d * dtype_size(j.q_dtype), j.rows, j.gather ? 0 : nq * j.B * d * dtype_size(j.row_dtype), j.cand_ids, nq * j.B * 4, j.cand_count, nb, ob_d, ob_i);
+    io.choose(c, j.nq, policy);
+    io.outputs(j.out_ids, ob_i, j.out_dist, ob_d, j.out_count, j.scored, nb);
+    int rc;
+    if ((rc = io.begin(c)) || (rc = io.send(c))) return rc;
+    const void* q_d = io.dev_up<void>(c, RefineIo::Q);
+    const int32_t *ids_d = io.dev_up<int32_t>(c, RefineIo::CandIds), *cnt_d = io.dev_up<int32_t>(c, RefineIo::CandCount);
+    int32_t *oi = io.dev_down<int32_t>(c, RefineIo::Ids), *oc = io.dev_down<int32_t>(c, RefineIo::Counts);
+    double* od = io.dev_down<double>(c, RefineIo::Dist);
+    rc = j.gather ? fspann_refine_store_dev(c, j.nq, q_d, j.q_dtype, j.B, ids_d, cnt_d, j.k, oi, od, oc, oc + nq)
+                  : fspann_refine_dev(c, j.nq, q_d, j.q_dtype, io.dev_up<void>(c, RefineIo::Rows), j.row_dtype, j.B, ids_d, cnt_d, j.k, oi, od, oc, oc + nq);
+    if (rc || (rc = io.fetch(c))) return rc;
+    FSP_HIP(hipStreamSynchronize(c->stream));
+    io.unpack(c);
+    return FSPANN_OK;
 }
 
 }  // namespace
@@ -219,90 +208,21 @@ int fspann_refine_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
                       int64_t B, const int32_t* cand_ids_dev, const int32_t* cand_count_dev, int k, int32_t* out_ids_dev,
                       double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev) {
     CHECK_CTX(c);
-    if (nq < 0 || B <= 0) return fail(FSPANN_E_ARG, "nq < 0 or B <= 0");
-    if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");  // QueryTokenFactory.java:65
-    if (nq == 0) return FSPANN_OK;
-    if (!q_dev || !cand_dev || !cand_ids_dev || !cand_count_dev || !out_ids_dev || !out_dist_dev || !out_count_dev)
-        return fail(FSPANN_E_NULL, "refine buffer is null");
-    return refine_typed<false>(c, cand_dtype, q_dtype, nq, q_dev, cand_dev, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev);
+    int rc = check_refine_args(nq, B, k, q_dev && cand_dev && cand_ids_dev && cand_count_dev && out_ids_dev && out_dist_dev && out_count_dev);
+    if (rc || nq == 0) return rc;
+    return refine_run(c, {q_dev, q_dtype, cand_dev, cand_dtype, false, nq, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev});
 }
 
 int fspann_refine(fspann_ctx* c, int64_t nq, const void* q, const void* cand, int dtype, int64_t B,
                   const int32_t* cand_ids, const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist,
                   int32_t* out_count, int32_t* scored) {
     CHECK_CTX(c);
-    if (nq < 0 || B <= 0) return fail(FSPANN_E_ARG, "nq < 0 or B <= 0");
-    if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
-    if (nq == 0) return FSPANN_OK;
-    if (!q || !cand || !cand_ids || !cand_count || !out_ids || !out_dist || !out_count) return fail(FSPANN_E_NULL, "refine buffer is null");
+    int rc = check_refine_args(nq, B, k, q && cand && cand_ids && cand_count && out_ids && out_dist && out_count);
+    if (rc || nq == 0) return rc;
     if (const DtypeInfo* di = dtype_info(dtype); di && di->rows_noun)
         return fail(FSPANN_E_ARG, "dtype %s: fspann_refine has one dtype for query and rows, and a query is FSPANN_F32 or FSPANN_F64 (%s: fspann_refine_dev)", di->name, di->rows_noun);
     if (!is_query_dtype(dtype)) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
-    const size_t esz = dtype_size(dtype);
-    const int d = c->cfg.dim;
-    const size_t qb = static_cast<size_t>(nq) * d * esz, cb = static_cast<size_t>(nq) * B * d * esz;
-    const size_t ib = static_cast<size_t>(nq) * B * 4, nb = static_cast<size_t>(nq) * 4;
-    const size_t ob_i = static_cast<size_t>(nq) * k * 4, ob_d = static_cast<size_t>(nq) * k * 8;
-    int rc;
-    // Small calls: query, ids and counts go up in ONE pinned block and every output comes down in one (the candidate rows keep
-    // their own copy straight from the caller's buffer): three transfers and one synchronisation instead of eight and one.
-    {
-        auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
-        const size_t up = al(qb) + al(ib) + al(nb), down = al(ob_d) + al(ob_i) + al(2 * nb);
-        if (std::max(up, down) <= kPinBytes && pin_block(c)) {
-            unsigned char* hp = static_cast<unsigned char*>(c->h_pin);
-            // a handful of queries: query, ids and counts are read from the mapped pinned block and the results written into it by the
-            // kernel itself (zero_copy_ok); the rows always travel by a copy command (a workgroup reading 256 KB over the bus is slow)
-            // (short lists only: with thousands of candidate ids every chunk's workgroup would fetch its ids over the bus first — SIFT_P4_FAST,
-            // B = 8 000: 439 against 405 us per call)
-            const bool zc = up <= 8192 && al(up) + down <= kPinBytes && zero_copy_ok(c, nq);
-            if (!zc) {
-                if ((rc = ensure(c, c->ws_io[0], up))) return rc;
-                if ((rc = ensure(c, c->ws_io[4], down))) return rc;
-            }
-            if ((rc = ensure(c, c->ws_io[1], cb))) return rc;
-            unsigned char* du = zc ? static_cast<unsigned char*>(c->d_pin) : static_cast<unsigned char*>(c->ws_io[0].p);
-            unsigned char* dd = zc ? static_cast<unsigned char*>(c->d_pin) + al(up) : static_cast<unsigned char*>(c->ws_io[4].p);
-            unsigned char* hres = zc ? hp + al(up) : hp;
-            std::memcpy(hp, q, qb);
-            std::memcpy(hp + al(qb), cand_ids, ib);
-            std::memcpy(hp + al(qb) + al(ib), cand_count, nb);
-            if (!zc) FSP_HIP(hipMemcpyAsync(du, hp, up, hipMemcpyHostToDevice, c->stream));
-            FSP_HIP(hipMemcpyAsync(c->ws_io[1].p, cand, cb, hipMemcpyHostToDevice, c->stream));
-            int32_t* cnt_out = reinterpret_cast<int32_t*>(dd + al(ob_d) + al(ob_i));
-            rc = fspann_refine_dev(c, nq, du, dtype, c->ws_io[1].p, dtype, B, reinterpret_cast<int32_t*>(du + al(qb)),
-                                   reinterpret_cast<int32_t*>(du + al(qb) + al(ib)), k, reinterpret_cast<int32_t*>(dd + al(ob_d)),
-                                   reinterpret_cast<double*>(dd), cnt_out, cnt_out + nq);
-            if (rc) return rc;
-            if (!zc) FSP_HIP(hipMemcpyAsync(hp, dd, down, hipMemcpyDeviceToHost, c->stream));   // (stream order: the way up has been read by then)
-            FSP_HIP(hipStreamSynchronize(c->stream));
-            std::memcpy(out_dist, hres, ob_d);
-            std::memcpy(out_ids, hres + al(ob_d), ob_i);
-            std::memcpy(out_count, hres + al(ob_d) + al(ob_i), nb);
-            if (scored) std::memcpy(scored, hres + al(ob_d) + al(ob_i) + nb, nb);
-            return FSPANN_OK;
-        }
-    }
-    if ((rc = ensure(c, c->ws_io[0], qb))) return rc;
-    if ((rc = ensure(c, c->ws_io[1], cb))) return rc;
-    if ((rc = ensure(c, c->ws_io[2], ib))) return rc;
-    if ((rc = ensure(c, c->ws_io[3], nb * 3))) return rc;
-    if ((rc = ensure(c, c->ws_io[4], ob_i))) return rc;
-    if ((rc = ensure(c, c->ws_io[5], ob_d))) return rc;
-    int32_t* cnts = static_cast<int32_t*>(c->ws_io[3].p);
-    FSP_HIP(hipMemcpyAsync(c->ws_io[0].p, q, qb, hipMemcpyHostToDevice, c->stream));
-    FSP_HIP(hipMemcpyAsync(c->ws_io[1].p, cand, cb, hipMemcpyHostToDevice, c->stream));
-    FSP_HIP(hipMemcpyAsync(c->ws_io[2].p, cand_ids, ib, hipMemcpyHostToDevice, c->stream));
-    FSP_HIP(hipMemcpyAsync(cnts, cand_count, nb, hipMemcpyHostToDevice, c->stream));
-    rc = fspann_refine_dev(c, nq, c->ws_io[0].p, dtype, c->ws_io[1].p, dtype, B, static_cast<int32_t*>(c->ws_io[2].p), cnts, k,
-                           static_cast<int32_t*>(c->ws_io[4].p), static_cast<double*>(c->ws_io[5].p), cnts + nq, cnts + 2 * nq);
-    if (rc) return rc;
-    FSP_HIP(hipMemcpyAsync(out_ids, c->ws_io[4].p, ob_i, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipMemcpyAsync(out_dist, c->ws_io[5].p, ob_d, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipMemcpyAsync(out_count, cnts + nq, nb, hipMemcpyDeviceToHost, c->stream));
-    if (scored) FSP_HIP(hipMemcpyAsync(scored, cnts + 2 * nq, nb, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipStreamSynchronize(c->stream));
-    return FSPANN_OK;
+    return refine_staged(c, {q, dtype, cand, dtype, false, nq, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored}, RefineIo::policy);
 }
 
 void* fspann_host_buffer(fspann_ctx* c, size_t bytes) {
@@ -373,47 +293,22 @@ int fspann_refine_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
                             double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev) {
     CHECK_CTX(c);
     if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-    if (nq < 0 || B <= 0) return fail(FSPANN_E_ARG, "nq < 0 or B <= 0");
-    if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");  // QueryTokenFactory.java:65
-    if (nq == 0) return FSPANN_OK;
-    if (!q_dev || !cand_ids_dev || !cand_count_dev || !out_ids_dev || !out_dist_dev || !out_count_dev)
-        return fail(FSPANN_E_NULL, "refine buffer is null");
-    return refine_typed<true>(c, c->store_dtype, q_dtype, nq, q_dev, c->d_store, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev);
+    int rc = check_refine_args(nq, B, k, q_dev && cand_ids_dev && cand_count_dev && out_ids_dev && out_dist_dev && out_count_dev);
+    if (rc || nq == 0) return rc;
+    return refine_run(c, store_job(c, q_dev, q_dtype, nq, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev));
 }
 
+// (no pinned or mapped transport: one copy command per argument)
 int fspann_refine_store(fspann_ctx* c, int64_t nq, const void* q, int q_dtype, int64_t B, const int32_t* cand_ids,
                         const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
                         int32_t* scored) {
     CHECK_CTX(c);
     if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-    if (nq < 0 || B <= 0) return fail(FSPANN_E_ARG, "nq < 0 or B <= 0");
-    if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
-    if (nq == 0) return FSPANN_OK;
-    if (!q || !cand_ids || !cand_count || !out_ids || !out_dist || !out_count) return fail(FSPANN_E_NULL, "refine buffer is null");
-    if (int rc = refuse_row_only(q_dtype, "q_dtype")) return rc;
+    int rc = check_refine_args(nq, B, k, q && cand_ids && cand_count && out_ids && out_dist && out_count);
+    if (rc || nq == 0) return rc;
+    if ((rc = refuse_row_only(q_dtype, "q_dtype"))) return rc;
     if (!is_query_dtype(q_dtype)) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
-    const size_t qb = static_cast<size_t>(nq) * c->cfg.dim * dtype_size(q_dtype);
-    const size_t ib = static_cast<size_t>(nq) * B * 4, nb = static_cast<size_t>(nq) * 4;
-    const size_t ob_i = static_cast<size_t>(nq) * k * 4, ob_d = static_cast<size_t>(nq) * k * 8;
-    int rc;
-    if ((rc = ensure(c, c->ws_io[0], qb))) return rc;
-    if ((rc = ensure(c, c->ws_io[2], ib))) return rc;
-    if ((rc = ensure(c, c->ws_io[3], nb * 3))) return rc;
-    if ((rc = ensure(c, c->ws_io[4], ob_i))) return rc;
-    if ((rc = ensure(c, c->ws_io[5], ob_d))) return rc;
-    int32_t* cnts = static_cast<int32_t*>(c->ws_io[3].p);
-    FSP_HIP(hipMemcpyAsync(c->ws_io[0].p, q, qb, hipMemcpyHostToDevice, c->stream));
-    FSP_HIP(hipMemcpyAsync(c->ws_io[2].p, cand_ids, ib, hipMemcpyHostToDevice, c->stream));
-    FSP_HIP(hipMemcpyAsync(cnts, cand_count, nb, hipMemcpyHostToDevice, c->stream));
-    rc = fspann_refine_store_dev(c, nq, c->ws_io[0].p, q_dtype, B, static_cast<int32_t*>(c->ws_io[2].p), cnts, k,
-                                 static_cast<int32_t*>(c->ws_io[4].p), static_cast<double*>(c->ws_io[5].p), cnts + nq, cnts + 2 * nq);
-    if (rc) return rc;
-    FSP_HIP(hipMemcpyAsync(out_ids, c->ws_io[4].p, ob_i, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipMemcpyAsync(out_dist, c->ws_io[5].p, ob_d, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipMemcpyAsync(out_count, cnts + nq, nb, hipMemcpyDeviceToHost, c->stream));
-    if (scored) FSP_HIP(hipMemcpyAsync(scored, cnts + 2 * nq, nb, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipStreamSynchronize(c->stream));
-    return FSPANN_OK;
+    return refine_staged(c, {q, q_dtype, nullptr, c->store_dtype, true, nq, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored}, RefineIo::store_policy);
 }
 
 // QueryServiceImpl.search for a batch, all three stages in stream order with one call: TokenGen codes (encode),
@@ -499,6 +394,5 @@ int fspann_refine_timing_end(fspann_ctx* c, int* launches, double* total_ms) {
     c->rt_used = 0;
     return FSPANN_OK;
 }
-
 
 }  // extern "C"

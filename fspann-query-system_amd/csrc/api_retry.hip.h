@@ -60,6 +60,10 @@ int retry_bufs(fspann_ctx* c, const char* precedes, int64_t nq, const void* q_de
 }
 
 PickIn pick_in(const SearchBufs& s) { return {s.sa.bad, s.sa.cnt, s.out_count, s.scored, s.k}; }
+// the list-mode Refine of a search over the store: the queries list[0 .. *count) only, in place
+int refine_store_list(fspann_ctx* c, const SearchBufs& s, const int32_t* list, const int32_t* count) {
+    return refine_run(c, store_job(c, s.q, s.q_dtype, s.nq, s.B, s.sa.sel, s.sa.cnt, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, list, count));
+}
 
 // QSI.search with its adaptive retry, in stream order: pass 1 is fspann_search_store_dev with the caller's probes; the pick; pass 2
 // with 10 probes (QSI:333) over the listed queries only, in place.  Pass 1 at 10 effective probes already is what pass 2 would
@@ -71,7 +75,7 @@ int search_retry_passes(fspann_ctx* c, const SearchBufs& s, int probe_override) 
     if ((rc = launch_pick(c, s.nq, RetryRule{pick_in(s), s.retried}, s.list, s.count))) return rc;
     if (effective_probes(c, probe_override) == effective_probes(c, 10)) return FSPANN_OK;
     if ((rc = route_list_dev(c, s.nq, s.sa.codes, 10, s.B, s.sa.sel, s.sa.cnt, s.list, s.count))) return rc;
-    return refine_store_list(c, s.nq, s.q, s.q_dtype, s.B, s.sa.sel, s.sa.cnt, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, s.list, s.count);
+    return refine_store_list(c, s, s.list, s.count);
 }
 
 // First step of a finish call: the stream synchronised, the Route counts on the host; *any = one of them is flagged.
@@ -159,7 +163,7 @@ int finish_flagged(fspann_ctx* c, const SearchBufs& s, int nl, int probe_overrid
 int finish_flagged(fspann_ctx* c, const SearchBufs& s, int probe_override, std::vector<int64_t> g1, std::vector<int64_t> g2, int64_t* done) {
     return finish_flagged(
         c, s, 1, probe_override, std::move(g1), std::move(g2), done,
-        [&](bool) { return refine_store_list(c, s.nq, s.q, s.q_dtype, s.B, s.sa.sel, s.sa.cnt, s.k, s.out_ids, s.out_dist, s.out_count, s.scored, s.list, s.count); },
+        [&](bool) { return refine_store_list(c, s, s.list, s.count); },
         [](int64_t, int32_t, int) { return FSPANN_OK; });
 }
 
@@ -226,10 +230,9 @@ int pipeline_retry(fspann_pipeline* p, fspann_pipeline::Slot& s) {
     }
     FSP_HIP(hipMemcpyAsync(s.ids_dev, s.ids_pin, static_cast<size_t>(nq) * B * 4, hipMemcpyHostToDevice, c->stream));
     FSP_HIP(hipMemcpyAsync(s.kcnt_dev, s.kcnt_pin, static_cast<size_t>(nq) * 4, hipMemcpyHostToDevice, c->stream));
-    rc = launch_refine_t<float, float, false>(c, nq, static_cast<const float*>(s.q_dev), cand_dev, B, static_cast<const int32_t*>(s.ids_dev),
-                                              static_cast<const int32_t*>(s.kcnt_dev), p->k, static_cast<int32_t*>(s.oi_dev), static_cast<double*>(s.od_dev),
-                                              static_cast<int32_t*>(s.oc_dev), static_cast<int32_t*>(s.sc_dev), static_cast<const int32_t*>(s.list_dev),
-                                              static_cast<const int32_t*>(s.lcnt_dev));
+    rc = refine_run(c, {s.q_dev, FSPANN_F32, cand_dev, FSPANN_F32, false, nq, B, static_cast<const int32_t*>(s.ids_dev), static_cast<const int32_t*>(s.kcnt_dev), p->k,
+                        static_cast<int32_t*>(s.oi_dev), static_cast<double*>(s.od_dev), static_cast<int32_t*>(s.oc_dev), static_cast<int32_t*>(s.sc_dev),
+                        static_cast<const int32_t*>(s.list_dev), static_cast<const int32_t*>(s.lcnt_dev)});
     s.t_retry_ms = now_ms() - t0;
     return rc;
 }

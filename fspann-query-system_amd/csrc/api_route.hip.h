@@ -133,7 +133,6 @@ int plan_route(fspann_ctx* c, int probe_override, int64_t nq, int32_t limit, Rou
     return FSPANN_OK;
 }
 
-
 }  // namespace
 
 extern "C" {
@@ -163,9 +162,7 @@ int fspann_route_plan_info(fspann_ctx* c, int probe_override, int32_t limit, int
     return kFields;
 }
 
-
 }  // extern "C"
-
 
 namespace {
 
@@ -349,92 +346,48 @@ int fspann_route(fspann_ctx* c, int64_t nq, const uint64_t* codes, int probe_ove
     if (nq == 0) return FSPANN_OK;
     if (!codes) return fail(FSPANN_E_STATE, "MSANNP violation: QueryToken missing BitSet codes");
     if (!ids || !count) return fail(FSPANN_E_NULL, "output buffer is null");
-    const size_t cb = static_cast<size_t>(nq) * c->TD * c->W * 8;
-    const size_t ob = static_cast<size_t>(nq) * cap * 4;
-    int rc;
+    const size_t ob = static_cast<size_t>(nq) * cap * 4, nb = static_cast<size_t>(nq) * 4;
     // Small calls (QueryService.search is one token per call, ForwardSecureANNSystem.java:636): codes go up and lists, scores and
-    // counts come down through ONE pinned block — one asynchronous copy each way and one synchronisation, where the general path
-    // below pays a synchronous pageable copy per argument and a separate look at the counts (bench.py operator_surface).
-    const size_t ob_a = (ob + 15) & ~size_t(15), cnt_a = (static_cast<size_t>(nq) * 12 + 15) & ~size_t(15);
-    if (std::max(cb, 2 * ob_a + cnt_a) <= kPinBytes && pin_block(c)) {
-        unsigned char* hp = static_cast<unsigned char*>(c->h_pin);
-        const size_t cb_a = (cb + 15) & ~size_t(15);
-        // a handful of queries: the kernels read the codes from the mapped pinned block and write lists and counts into it (no copy
-        // commands: zero_copy_ok); else one copy each way through device buffers
-        const bool zc = cb_a + 2 * ob_a + cnt_a <= kPinBytes && zero_copy_ok(c, nq);
-        if (!zc) {
-            if ((rc = ensure(c, c->ws_io[0], cb))) return rc;
-            if ((rc = ensure(c, c->ws_io[1], 2 * ob_a + cnt_a))) return rc;       // ids | scores | count, kept, rawSeen: one block
-        }
-        unsigned char* hres = zc ? hp + cb_a : hp;                                  // where the results end up on the host
-        unsigned char* dv = zc ? static_cast<unsigned char*>(c->d_pin) + cb_a : static_cast<unsigned char*>(c->ws_io[1].p);
-        const uint64_t* codes_d = zc ? static_cast<const uint64_t*>(c->d_pin) : static_cast<const uint64_t*>(c->ws_io[0].p);
-        int32_t* ids_d = reinterpret_cast<int32_t*>(dv), *sc_d = reinterpret_cast<int32_t*>(dv + ob_a), *cnt_d = reinterpret_cast<int32_t*>(dv + 2 * ob_a);
-        std::memcpy(hp, codes, cb);
-        if (!zc) FSP_HIP(hipMemcpyAsync(c->ws_io[0].p, hp, cb, hipMemcpyHostToDevice, c->stream));
+    // counts come down through ONE pinned block — one asynchronous copy each way and one synchronisation, where the Direct transport
+    // pays a synchronous pageable copy per argument and a separate look at the counts (bench.py operator_surface).  A handful of
+    // queries: the kernels read the codes from the mapped pinned block and write lists and counts into it (no copy commands).
+    RouteIo io(codes, static_cast<size_t>(nq) * c->TD * c->W * 8, ob, 3 * nb);
+    io.choose(c, nq, RouteIo::policy);
+    io.out(RouteIo::Ids, ids, ob); io.out(RouteIo::Scores, score, ob);
+    io.out(RouteIo::Counts, count, nb); io.out(RouteIo::Counts, kept, nb, nb); io.out(RouteIo::Counts, raw_seen, nb, 2 * nb);
+    int rc;
+    if ((rc = io.begin(c)) || (rc = io.send(c))) return rc;
+    const uint64_t* codes_d = io.dev_up<const uint64_t>(c, 0);
+    int32_t *ids_d = io.dev_down<int32_t>(c, RouteIo::Ids), *sc_d = io.dev_down<int32_t>(c, RouteIo::Scores), *cnt_d = io.dev_down<int32_t>(c, RouteIo::Counts);
+    int32_t *kept_d = kept ? cnt_d + nq : nullptr, *raw_d = raw_seen ? cnt_d + 2 * nq : nullptr;
+    // a query whose HashMap would have treeified a bin (count = -1) is finished by the literal JDK model on the host (rare path)
+    auto resolve = [&]() { return guarded([&]() -> int { return resolve_unmodelled(c, nq, codes_d, probe_override, limit, cap, ids_d, sc_d, cnt_d, kept_d, raw_d, nullptr, nullptr); }); };
+    if (io.t == Transport::Direct) {
+        if ((rc = fspann_route_dev(c, nq, codes_d, probe_override, limit, cap, ids_d, sc_d, cnt_d, kept_d, raw_d)) || (rc = resolve()) || (rc = io.fetch(c))) return rc;
+        FSP_HIP(hipStreamSynchronize(c->stream));
+    } else {
+        const bool zc = io.t == Transport::Mapped;
+        const int32_t* cnt_h = static_cast<const int32_t*>(io.landed(c, RouteIo::Counts));
         RoutePlan def_pl;
         RouteParams def_p{};
         bool deferred = false;
-        rc = route_dev_impl(c, nq, codes_d, probe_override, limit, cap, ids_d, sc_d, cnt_d,
-                            kept ? cnt_d + nq : nullptr, raw_seen ? cnt_d + 2 * nq : nullptr, zc ? &def_pl : nullptr, zc ? &def_p : nullptr, zc ? &deferred : nullptr);
+        rc = route_dev_impl(c, nq, codes_d, probe_override, limit, cap, ids_d, sc_d, cnt_d, kept_d, raw_d, zc ? &def_pl : nullptr, zc ? &def_p : nullptr, zc ? &deferred : nullptr);
         if (rc) return rc;
         if (deferred) {
             // zero-copy call, bounded select: the counts are readable right after the synchronisation — the launch for handed-over queries
             // is issued only if one of them says PENDING (it was ~5 us of every call, for a list that is almost always empty)
             FSP_HIP(hipStreamSynchronize(c->stream));
-            const int32_t* cnt_p = reinterpret_cast<const int32_t*>(hres + 2 * ob_a);
-            bool pending = false;
-            for (int64_t i = 0; i < nq; i++) pending = pending || cnt_p[i] == kRoutePending;
-            if (pending && (rc = launch_full_select(c, def_pl, def_p))) return rc;
+            if (std::any_of(cnt_h, cnt_h + nq, [](int32_t v) { return v == kRoutePending; }) && (rc = launch_full_select(c, def_pl, def_p))) return rc;
         }
         for (int pass = 0; pass < 2; pass++) {
-            if (!zc) FSP_HIP(hipMemcpyAsync(hp, dv, 2 * ob_a + cnt_a, hipMemcpyDeviceToHost, c->stream));
+            if ((rc = io.fetch(c))) return rc;
             FSP_HIP(hipStreamSynchronize(c->stream));
-            const int32_t* cnt_h = reinterpret_cast<const int32_t*>(hres + 2 * ob_a);
-            bool flagged = false;
-            for (int64_t i = 0; i < nq; i++) flagged = flagged || cnt_h[i] < 0;
-            if (!flagged || pass == 1) break;
-            // (rare) a bestScore map treeified a bin: finished by the literal JDK model on the host, then fetched again
-            rc = guarded([&]() -> int {
-                return resolve_unmodelled(c, nq, codes_d, probe_override, limit, cap, ids_d, sc_d, cnt_d,
-                                          kept ? cnt_d + nq : nullptr, raw_seen ? cnt_d + 2 * nq : nullptr, nullptr, nullptr);
-            });
-            if (rc) return rc;
+            // (rare) a bestScore map treeified a bin: finished by the host model, then fetched again
+            if (pass == 1 || std::none_of(cnt_h, cnt_h + nq, [](int32_t v) { return v < 0; })) break;
+            if ((rc = resolve())) return rc;
         }
-        const int32_t* cnt_h = reinterpret_cast<const int32_t*>(hres + 2 * ob_a);
-        std::memcpy(ids, hres, ob);
-        if (score) std::memcpy(score, hres + ob_a, ob);
-        std::memcpy(count, cnt_h, static_cast<size_t>(nq) * 4);
-        if (kept) std::memcpy(kept, cnt_h + nq, static_cast<size_t>(nq) * 4);
-        if (raw_seen) std::memcpy(raw_seen, cnt_h + 2 * nq, static_cast<size_t>(nq) * 4);
-        for (int64_t i = 0; i < nq; i++)
-            if (count[i] < 0)
-                return fail(FSPANN_E_STATE, "query %lld: a treeified HashMap bin of bestScore orders different ids with equal String.hashCode by "
-                            "String.compareTo, which the library cannot evaluate for non-decimal ids: not modelled, its count is -1", (long long)i);
-        return FSPANN_OK;
+        io.unpack(c);
     }
-    if ((rc = ensure(c, c->ws_io[0], cb))) return rc;
-    if ((rc = ensure(c, c->ws_io[1], ob))) return rc;
-    if ((rc = ensure(c, c->ws_io[2], ob))) return rc;
-    if ((rc = ensure(c, c->ws_io[3], static_cast<size_t>(nq) * 12))) return rc;
-    int32_t* cnt = static_cast<int32_t*>(c->ws_io[3].p);
-    FSP_HIP(hipMemcpyAsync(c->ws_io[0].p, codes, cb, hipMemcpyHostToDevice, c->stream));
-    rc = fspann_route_dev(c, nq, static_cast<const uint64_t*>(c->ws_io[0].p), probe_override, limit, cap,
-                          static_cast<int32_t*>(c->ws_io[1].p), static_cast<int32_t*>(c->ws_io[2].p), cnt, kept ? cnt + nq : nullptr,
-                          raw_seen ? cnt + 2 * nq : nullptr);
-    if (rc) return rc;
-    // a query whose HashMap would have treeified a bin (count = -1) is finished by the literal JDK model on the host (rare path)
-    rc = guarded([&]() -> int {
-        return resolve_unmodelled(c, nq, static_cast<const uint64_t*>(c->ws_io[0].p), probe_override, limit, cap, static_cast<int32_t*>(c->ws_io[1].p),
-                                  static_cast<int32_t*>(c->ws_io[2].p), cnt, kept ? cnt + nq : nullptr, raw_seen ? cnt + 2 * nq : nullptr, nullptr, nullptr);
-    });
-    if (rc) return rc;
-    FSP_HIP(hipMemcpyAsync(ids, c->ws_io[1].p, ob, hipMemcpyDeviceToHost, c->stream));
-    if (score) FSP_HIP(hipMemcpyAsync(score, c->ws_io[2].p, ob, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipMemcpyAsync(count, cnt, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost, c->stream));
-    if (kept) FSP_HIP(hipMemcpyAsync(kept, cnt + nq, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost, c->stream));
-    if (raw_seen) FSP_HIP(hipMemcpyAsync(raw_seen, cnt + 2 * nq, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToHost, c->stream));
-    FSP_HIP(hipStreamSynchronize(c->stream));
     // all outputs are in place; what is still flagged could not be finished by the host model either: a treeified bin holds
     // different ids with EQUAL String.hashCode and the ids are not decimal ordinals, so their String.compareTo order is unknown here
     for (int64_t i = 0; i < nq; i++)
@@ -487,6 +440,5 @@ int fspann_debug_route_stamps(fspann_ctx* c, void* dev_ptr) {
     return FSPANN_OK;
 }
 #endif
-
 
 }  // extern "C"

@@ -41,60 +41,47 @@ int sweep_check(const int64_t* limits, int nl, int k, SweepLimits& lim) {
     return FSPANN_OK;
 }
 
-// The scan with the key epilogue under launch_refine_dc's plan (scan_plan), without partial lists, hand-over or kernel-attached
-// timing, and the touched-record set behind it: the rows this scan scores (the clipped counts).  B = the row pitch (stride); nchunks
-// covers the largest limit only.
+// The scan of job j (counts: the clipped counts; no outputs) with the key epilogue under launch_refine_dc's plan (scan_plan), without
+// partial lists, hand-over or kernel-attached timing, and the touched-record set behind it: the rows this scan scores.  j.B = the
+// row pitch (stride); nchunks covers the largest limit only.
 template <typename TC, typename TQ, bool GATHER>
-int launch_refine_keys_t(fspann_ctx* c, int64_t nq, const TQ* q, const TC* cand, int64_t B, const int32_t* cand_ids, const int32_t* cand_count, int nchunks,
-                         uint64_t* keys, const int32_t* qlist, const int32_t* qcount) {
+int launch_refine_keys_t(fspann_ctx* c, const RefineJob& j, int nchunks, uint64_t* keys) {
     int rc = with_tile_width<TC>(c, [&](auto dc) -> int {
         constexpr int DC = decltype(dc)::value;
-        const ScanPlan sp = scan_plan<TC, DC, GATHER>(c, nq, cand, nchunks);
-        const RefineArgs<TC, TQ> ra{q, cand, GATHER ? c->store_n : 0, B, c->cfg.dim, cand_ids, cand_count, 0, nchunks, nullptr, nullptr, nullptr, nullptr,
-                                    reinterpret_cast<RefinePartial*>(keys), nullptr, 0, 0, c->dbg_route};
+        const ScanPlan sp = scan_plan<TC, DC, GATHER>(c, j.nq, static_cast<const TC*>(j.rows), nchunks);
+        const RefineArgs<TC, TQ> ra{static_cast<const TQ*>(j.q), static_cast<const TC*>(j.rows), GATHER ? c->store_n : 0, j.B, c->cfg.dim, j.cand_ids, j.cand_count, 0, nchunks,
+                                    nullptr, nullptr, nullptr, nullptr, reinterpret_cast<RefinePartial*>(keys), nullptr, 0, 0, c->dbg_route};
+        int r = FSPANN_OK;
         bool streamed = false;
         if constexpr (DC * sizeof(TC) == 128) if (sp.stream) {
-            auto kern = qlist ? refine_stream_keys_kernel<TC, TQ, DC, GATHER, true> : refine_stream_keys_kernel<TC, TQ, DC, GATHER, false>;
-            hipLaunchKernelGGL(kern, dim3(sp.sgrid(nq * nchunks)), dim3(kRefRows), sp.lds, c->stream, ra, nq, qlist, qcount);
+            const unsigned sgrid = sp.sgrid(j.nq * nchunks);
+            r = j.qlist ? launch_refine_kernel(c, false, refine_stream_keys_kernel<TC, TQ, DC, GATHER, true>, sgrid, sp.lds, ra, j.nq, j.qlist, j.qcount)
+                        : launch_refine_kernel(c, false, refine_stream_keys_kernel<TC, TQ, DC, GATHER, false>, sgrid, sp.lds, ra, j.nq, j.qlist, j.qcount);
             streamed = true;
         }
-        if (!streamed) {
-            auto kern = sp.vec ? refine_scan_keys_kernel<TC, TQ, DC, true, GATHER> : refine_scan_keys_kernel<TC, TQ, DC, false, GATHER>;
-            if (sp.lds > 64 * 1024) if (int r = raise_lds_ceiling(c, kern, sp.lds)) return r;
-            hipLaunchKernelGGL(kern, dim3(sp.grid), dim3(kRefRows), sp.lds, c->stream, ra, qlist, qcount);
-        }
+        if (!streamed)
+            r = sp.vec ? launch_refine_kernel_lds(c, false, refine_scan_keys_kernel<TC, TQ, DC, true, GATHER>, sp.grid, sp.lds, sp.lds, ra, j.qlist, j.qcount)
+                       : launch_refine_kernel_lds(c, false, refine_scan_keys_kernel<TC, TQ, DC, false, GATHER>, sp.grid, sp.lds, sp.lds, ra, j.qlist, j.qcount);
+        if (r) return r;
         FSP_HIP(hipGetLastError());
         return FSPANN_OK;
     });
-    if (rc) return rc;
-    return touch_mark<TC, TQ, GATHER>(c, nq, q, cand, B, cand_ids, cand_count, qlist, qcount);
+    return rc ? rc : touch_mark<TC, TQ, GATHER>(c, j);
 }
 
-// One sweep refine: the key scan over the rows at `rows` (dense blocks, or GATHER: the resident store) with the clipped counts
-// `clip`, then the prefix top-k with its snapshots.  qlist / qcount (device): over the queries qlist[0 .. *qcount) only; take
-// (device, [nl][nq]): only the planes it marks are written.
-template <bool GATHER>
-int sweep_refine(fspann_ctx* c, const SweepArea& sw, int nchunks, int row_dtype, int q_dtype, int64_t nq, const void* q_dev, const void* rows, int64_t stride,
-                 const int32_t* cand_ids_dev, const SweepLimits& lim, int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev,
-                 int32_t* scored_dev, const int32_t* take, const int32_t* qlist, const int32_t* qcount) {
-    int rc = FSPANN_OK;
-    bool launched = false;
-    with_query_type(q_dtype, [&](auto tq) {
-        launched = with_row_type(row_dtype, [&](auto tc) {
-            using TQ = typename decltype(tq)::type;
-            using TC = typename decltype(tc)::type;
-            rc = launch_refine_keys_t<TC, TQ, GATHER>(c, nq, static_cast<const TQ*>(q_dev), static_cast<const TC*>(rows), stride, cand_ids_dev, sw.clip, nchunks,
-                                                      sw.keys, qlist, qcount);
-        });
+// One sweep refine: the key scan of job j (rows dense, or the resident store; its counts are replaced by the clipped counts
+// sw.clip, j.B is the stride), then the prefix top-k with its snapshots into j's outputs.  take (device, [nl][nq]): only the planes
+// it marks are written.
+int sweep_refine(fspann_ctx* c, const SweepArea& sw, int nchunks, RefineJob j, const SweepLimits& lim, const int32_t* take) {
+    j.cand_count = sw.clip;
+    int rc = with_refine_types(j.q_dtype, j.row_dtype, [&](auto tq, auto tc) -> int {
+        using TQ = typename decltype(tq)::type;
+        using TC = typename decltype(tc)::type;
+        return j.gather ? launch_refine_keys_t<TC, TQ, true>(c, j, nchunks, sw.keys) : launch_refine_keys_t<TC, TQ, false>(c, j, nchunks, sw.keys);
     });
-    if (!launched) {
-        if ((rc = refuse_row_only(q_dtype, "q_dtype"))) return rc;
-        if (!is_query_dtype(q_dtype)) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
-        return fail(FSPANN_E_ARG, "unknown dtype");
-    }
     if (rc) return rc;
-    hipLaunchKernelGGL(refine_prefix_topk_kernel, dim3(static_cast<unsigned>(nq)), dim3(kSweepThreads), static_cast<size_t>(k) * 32, c->stream, sw.keys, sw.kpitch,
-                       cand_ids_dev, stride, sw.clip, lim, k, nq, out_ids_dev, out_dist_dev, out_count_dev, scored_dev, take, qlist, qcount);
+    hipLaunchKernelGGL(refine_prefix_topk_kernel, dim3(static_cast<unsigned>(j.nq)), dim3(kSweepThreads), static_cast<size_t>(j.k) * 32, c->stream, sw.keys, sw.kpitch,
+                       j.cand_ids, j.B, sw.clip, lim, j.k, j.nq, j.out_ids, j.out_dist, j.out_count, j.scored, take, j.qlist, j.qcount);
     FSP_HIP(hipGetLastError());
     return FSPANN_OK;
 }
@@ -122,8 +109,8 @@ int refine_sweep_call(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype,
     SweepArea sw;
     if ((rc = area_grow(c, c->ws_sweep, sw, nq, nchunks, nl))) return rc;
     if ((rc = sweep_clip(c, nq, cand_count_dev, static_cast<int32_t>(bmax), nullptr, sw.clip))) return rc;
-    return sweep_refine<GATHER>(c, sw, nchunks, row_dtype, q_dtype, nq, q_dev, rows, stride, cand_ids_dev, lim, k, out_ids_dev, out_dist_dev, out_count_dev,
-                                scored_dev, nullptr, nullptr, nullptr);
+    return sweep_refine(c, sw, nchunks, {q_dev, q_dtype, rows, row_dtype, GATHER, nq, stride, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev},
+                        lim, nullptr);
 }
 
 // What a search sweep call and its finish call share: the checked arguments, the sweep's work area, and the buffers of the search
@@ -170,8 +157,8 @@ int sweep_bufs(fspann_ctx* c, bool held, int64_t nq, const void* q_dev, int q_dt
 int sweep_score_list(fspann_ctx* c, const SweepCall& s, bool masked) {
     const SearchBufs& b = s.b;
     if (int rc = sweep_clip(c, b.nq, b.sa.cnt, static_cast<int32_t>(s.bmax), masked ? s.sw.cap_q : nullptr, s.sw.clip)) return rc;
-    return sweep_refine<true>(c, s.sw, s.nchunks, c->store_dtype, b.q_dtype, b.nq, b.q, c->d_store, s.bmax, b.sa.sel, s.lim, b.k, b.out_ids, b.out_dist, b.out_count,
-                              b.scored, masked ? b.retried : nullptr, b.list, b.count);
+    return sweep_refine(c, s.sw, s.nchunks, store_job(c, b.q, b.q_dtype, b.nq, s.bmax, b.sa.sel, b.sa.cnt, b.k, b.out_ids, b.out_dist, b.out_count, b.scored, b.list, b.count),
+                        s.lim, masked ? b.retried : nullptr);
 }
 
 int sweep_unique(fspann_ctx* c, int64_t nq, const SweepCall& s, bool pass2, int32_t* unique_dev) {
@@ -219,8 +206,8 @@ int fspann_search_sweep_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
     if ((rc = fspann_route_dev(c, nq, b.sa.codes, probe_override, bmax32, s.bmax, b.sa.sel, nullptr, b.sa.cnt, nullptr, nullptr))) return rc;
     FSP_HIP(hipMemcpyAsync(s.sw.cnt1, b.sa.cnt, static_cast<size_t>(nq) * 4, hipMemcpyDeviceToDevice, c->stream));
     if ((rc = sweep_clip(c, nq, b.sa.cnt, bmax32, nullptr, s.sw.clip))) return rc;
-    if ((rc = sweep_refine<true>(c, s.sw, s.nchunks, c->store_dtype, q_dtype, nq, q_dev, c->d_store, s.bmax, b.sa.sel, s.lim, k, out_ids_dev, out_dist_dev,
-                                 out_count_dev, b.scored, nullptr, nullptr, nullptr))) return rc;
+    if ((rc = sweep_refine(c, s.sw, s.nchunks, store_job(c, q_dev, q_dtype, nq, s.bmax, b.sa.sel, b.sa.cnt, k, out_ids_dev, out_dist_dev, out_count_dev, b.scored), s.lim,
+                           nullptr))) return rc;
     // QSI's retry predicate per (query, limit); the queries with any retried limit are listed
     if ((rc = launch_pick(c, nq, SweepRule{pick_in(b), s.lim, nq, b.retried, s.sw.cap_q}, b.list, b.count))) return rc;
     c->sweep_nq = nq; c->sweep_bmax = s.bmax; c->sweep_nl = nl; c->sweep_k = k;

@@ -260,10 +260,8 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         if ((rc = gather ? launch(tick_kernel<true>) : launch(tick_kernel<false>))) return rc;
         // the refine role's rows, from F_q as the tick leaves it (PENDING queries finished); the stand-alone paths above mark
         // inside their refine calls
-        if (F && (rc = gather ? touch_mark<float, float, true>(c, t->nq_refine, static_cast<const float*>(t->ref_q_dev), static_cast<const float*>(rows),
-                                                                t->ref_B, t->ref_ids_dev, t->ref_count_dev)
-                              : touch_mark<float, float, false>(c, t->nq_refine, static_cast<const float*>(t->ref_q_dev), static_cast<const float*>(rows),
-                                                                 t->ref_B, t->ref_ids_dev, t->ref_count_dev))) return rc;
+        const RefineJob tj{t->ref_q_dev, FSPANN_F32, rows, FSPANN_F32, gather, t->nq_refine, t->ref_B, t->ref_ids_dev, t->ref_count_dev, t->k, nullptr, nullptr, nullptr, nullptr};
+        if (F && (rc = gather ? touch_mark<float, float, true>(c, tj) : touch_mark<float, float, false>(c, tj))) return rc;
     }
     if (R && !t->route_handover_dev) {
         // no buffer travels with the batch: queries the bounded select handed over are finished now (normally none)

@@ -54,11 +54,13 @@ int touch_store_ok(fspann_ctx* c) {
     return FSPANN_OK;
 }
 
-// Marks the rows a Refine launch scores (its own arguments; GATHER: rows from the resident store by id, else the caller's rows),
-// enqueued behind it on c's stream.  Tracking off: nothing is launched.
+// Marks the rows a Refine job scores (GATHER: rows from the resident store by id, else the job's rows), enqueued behind it on c's
+// stream.  Tracking off: nothing is launched.
 template <typename TC, typename TQ, bool GATHER>
-int touch_mark(fspann_ctx* c, int64_t nq, const TQ* q, const TC* rows, int64_t B, const int32_t* ids, const int32_t* cnt,
-               const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
+int touch_mark(fspann_ctx* c, const RefineJob& j) {
+    const int64_t nq = j.nq, B = j.B;
+    const TQ* q = static_cast<const TQ*>(j.q);
+    const int32_t *ids = j.cand_ids, *cnt = j.cand_count, *qlist = j.qlist, *qcount = j.qcount;
     fspann_ctx* o = index_owner(c);
     if (!o->touch_on.load(std::memory_order_acquire) || nq <= 0) return FSPANN_OK;
     uint8_t* set = o->d_touch.load(std::memory_order_acquire);
@@ -72,7 +74,7 @@ int touch_mark(fspann_ctx* c, int64_t nq, const TQ* q, const TC* rows, int64_t B
         hipLaunchKernelGGL(touch_mark_store_kernel<TQ>, dim3(grid), dim3(kTouchThreads), 0, c->stream, q, d, ids, cnt, B, qlist, qcount,
                            static_cast<const uint8_t*>(c->store_ok.p), c->store_n, set, n_set);
     } else {
-        hipLaunchKernelGGL((touch_mark_rows_kernel<TQ, TC>), dim3(grid), dim3(kTouchThreads), 0, c->stream, q, d, rows, ids, cnt, B, qlist, qcount,
+        hipLaunchKernelGGL((touch_mark_rows_kernel<TQ, TC>), dim3(grid), dim3(kTouchThreads), 0, c->stream, q, d, static_cast<const TC*>(j.rows), ids, cnt, B, qlist, qcount,
                            set, n_set);
     }
     FSP_HIP(hipGetLastError());

@@ -31,6 +31,7 @@
 
 
 // The entry points, by stage (one translation unit: the kernels above are templates shared by several of them).
+#include "host_staging.h"
 #include "api_common.hip.h"
 #include "api_touch.hip.h"
 #include "api_encode.hip.h"

@@ -101,6 +101,15 @@ struct DevBuf {
     unsigned gen = 0;   // bumped by every (re)allocation: "same address" does not mean "same contents"
 };
 
+// fspann_ctx::ws_io by what each host-pointer call keeps in a slot on its Direct transport (host_staging.h lays the calls out; a Block
+// call sends its way up through its first slot and fetches its way down from the slot marked so)
+enum IoSlot : int {
+    kIoEncQ = 0, kIoEncCodes = 1, kIoEncBad = 2, kIoEncHashes = 3,
+    kIoRouteCodes = 0, kIoRouteIds = 1 /* Block: down */, kIoRouteScores = 2, kIoRouteCounts = 3,
+    kIoRefQ = 0, kIoRefRows = 1, kIoRefIds = 2, kIoRefCounts = 3 /* in | count | scored */, kIoRefOutIds = 4 /* Block: down */, kIoRefOutDist = 5,
+    kIoHandles = 6      // fspann_set_deleted's handles (api_ext.hip.h)
+};
+
 }  // namespace fspann
 
 // The opaque context of include/fspann.h.
@@ -247,7 +256,7 @@ struct fspann_ctx {
     std::vector<unsigned char> h_fixparams;   // ... and what each slot holds
     unsigned fix_valid = 0;
     int fix_next = 0;
-    fspann::DevBuf ws_io[8];   // staging for the host-pointer entry points
+    fspann::DevBuf ws_io[8];   // staging for the host-pointer entry points (IoSlot)
     void* h_pin = nullptr;     // pinned host block (kPinBytes) for the small transfers of the host-pointer entry points: one H2D and one D2H
     void* d_pin = nullptr;     // the same block as the device sees it (mapped host memory): kernels of the tiniest calls read and write it directly
     void* h_rows = nullptr;    // fspann_host_buffer: pinned host memory the adapter packs decrypted rows into (grown on demand)

@@ -27,7 +27,7 @@ KS = (1, 10, 33)
 SIZES = (300, 3000, 40000)
 BUILD_ROUTES = ("build_index", "append", "import", "load")
 INT32_MAX = 2**31 - 1
-ZERO_COPY_MAX_Q = 4                          # api_common.hip.h: kZeroCopyMaxQ
+ZERO_COPY_MAX_Q = 4                          # host_staging.h: kZeroCopyMaxQ
 
 # T x D in {4, 8, 16}, m * lambda <= 28, B in {64, 256, 300, 1000}.  "spec" is 16 x 1 with 5 probes and blocks of 64: the
 # shape-specialised bounded select.

@@ -1,5 +1,6 @@
 """ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
-include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h, include/fspann_narrow.h).
+include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h, include/fspann_narrow.h,
+include/fspann_route_recall.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -87,7 +88,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -264,6 +265,14 @@ _SIGS_NARROW = {
 }
 
 
+# include/fspann_route_recall.h: the rank of the ground truth in a candidate list and the recall ceilings it implies (a table of its
+# own: those above stay as they are)
+_SIGS_ROUTE_RECALL = {
+    "fspann_gt_rank_dev": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp]),
+    "fspann_recall_ceiling_dev": (_i, [_vp, _i64, _vp, _i64, C.POINTER(_i32), _i, _i64p, _i, _vp, _vp]),
+}
+
+
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
     global _LIB
@@ -273,7 +282,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -320,3 +329,8 @@ def sweep_symbols():
 def narrow_symbols():
     """the entry points of include/fspann_narrow.h"""
     return sorted(_SIGS_NARROW)
+
+
+def route_recall_symbols():
+    """the entry points of include/fspann_route_recall.h"""
+    return sorted(_SIGS_ROUTE_RECALL)

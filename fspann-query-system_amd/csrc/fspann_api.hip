@@ -24,6 +24,7 @@
 #include "refine_sweep.hip.h"
 #include "route.hip.h"
 #include "route_lazy.hip.h"
+#include "route_recall.hip.h"
 #include "search_pick.hip.h"
 #include "tick.hip.h"
 #include "touch.hip.h"
@@ -48,3 +49,4 @@
 #include "api_gt_validate.hip.h"
 #include "api_sweep.hip.h"
 #include "api_narrow.hip.h"
+#include "api_route_recall.hip.h"

@@ -967,7 +967,7 @@ class FspannContext:
             v = self.gt_validate_store_dev(qq.shape[0], qd, qcode, gd, g.shape[0], g.shape[1], sample_size, tolerance)
         return self._validation_dict(v, tolerance)
 
-    def run_queries(self, q, k_variants, gt_ids=None, probe_override=-1, B=None, validate=None):
+    def run_queries(self, q, k_variants, gt_ids=None, probe_override=-1, B=None, validate=None, attribution=False):
         """ForwardSecureANNSystem.runQueries (FSA:622-748) for a batch over the resident store: one search at K = max(k_variants) with
         its adaptive retry and the empty-result fallback (search_fallback_dev + its finish call), the ground truth over the store
         (groundtruth_store_dev) unless gt_ids [nq][>= K] is given, and recall / ratio / candidate ratio at every k of k_variants
@@ -977,7 +977,13 @@ class FspannContext:
         an invalid result raises FspannStateError with its message (IllegalStateException, FSA:2185), a valid one is returned as
         gt_validation.  validate=None (the default): no validation, the same launches and the same keys as before.
         Returns dict(ids, dist, count, scored, sel_count, bad, retried, fellback, resolved, gt_ids, recall, ratio, cand_ratio), the
-        last three float64 [nk][nq].  (plus gt_validation when it ran)"""
+        last three float64 [nk][nq].  (plus gt_validation when it ran)
+        attribution=True adds where the recall was lost (route_recall's pass, taken at the probes of each query's LAST pass: 10 if it
+        retried, else max(2 base, 4) if it fell back, else the caller's effective probes — at most three groups, one full-list Route
+        each): last_probes [nq], gt_rank [nq][K] (the rank of each true neighbour in that pass's full candidate list, -1: Route never
+        offered it), route_ceiling and limit_ceiling float64 [nk][nq] (the recall Route's list allows at all, and within its first B
+        entries), true_nn_rank = gt_rank[:, 0] and true_nn_seen.  A bad (non-finite) query is not routed: its ranks are -1 and its
+        ceilings 0.  attribution=False (the default): the launches and the keys above."""
         code = C.c_int(0)
         store = self.L.fspann_store_dev_ptr(self._h, C.byref(code))
         if not store:
@@ -1021,6 +1027,8 @@ class FspannContext:
                        cand_ratio=dv.down(cr))
             if validation is not None:
                 out["gt_validation"] = validation
+            if attribution:
+                self._attribute(dv, out, qq, gd, gs, ks, B, probe_override)
             return out
 
     @staticmethod
@@ -1130,6 +1138,121 @@ class FspannContext:
                        bad=dv.down(bad), resolved=resolved, gt_ids=dv.down(gd), recall=dv.down(rec), ratio=dv.down(rat), cand_ratio=dv.down(cr))
             out["would_fall_back"] = (out["count"] == 0) & (out["bad"][None, :] == 0)
             return out
+
+    # -- recall attribution (include/fspann_route_recall.h) -----------------------------------
+    def gt_rank_dev(self, nq, list_ids_ptr, list_score_ptr, list_stride, list_count_ptr, gt_ptr, gt_stride, kg, rank_ptr, gt_score_ptr=0):
+        """rank [nq][kg]: the position of every ground-truth id among the first min(list_count, list_stride) entries of its query's
+        list (-1: not there; -2: list_count -1, a flagged query nobody resolved), and gt_score [nq][kg] = list_score at that position
+        (-1 where rank < 0) when both score pointers are given.  One pass over the list, stream order."""
+        N.check(self.L.fspann_gt_rank_dev(self._h, nq, list_ids_ptr, list_score_ptr or None, list_stride, list_count_ptr or None, gt_ptr,
+                                          gt_stride, kg, rank_ptr, gt_score_ptr or None))
+
+    def recall_ceiling_dev(self, nq, rank_ptr, rank_stride, ks, limits, hits_ptr, ceiling_ptr=0):
+        """hits / ceiling [nl + 1][nk][nq] from rank [nq][rank_stride]: plane l counts the first ks[j] ranks in [0, limits[l]), the
+        last plane those >= 0 (Route's own ceiling); ceiling = hits / ks[j].  ks (at most 64) and limits (ascending, at most 16, may
+        be empty) are host sequences."""
+        kk = [int(x) for x in ks]
+        arr = (C.c_int32 * max(1, len(kk)))(*kk)
+        lim, nl = self._limits(limits)
+        N.check(self.L.fspann_recall_ceiling_dev(self._h, nq, rank_ptr, rank_stride, arr, len(kk), lim, nl, hits_ptr, ceiling_ptr or None))
+
+    def _route_rank(self, dv, nq, qd, gd, gs, K, probe_override, rank, gscore=0):
+        """One encode and one full-list Route (limit INT32_MAX, score and kept requested) of the device queries qd at probe_override,
+        the flagged queries finished by the host model, then the rank of the ground truth gd [nq][gs] in that list into rank [nq][K].
+        Returns (kept pointer, resolved)."""
+        cap = max(1, self.route_max_candidates(probe_override))
+        codes = dv.new((nq, self.TD, self.W), np.uint64)
+        ids, score = dv.new((nq, cap), np.int32), dv.new((nq, cap), np.int32)
+        cnt, kept = dv.new((nq,), np.int32), dv.new((nq,), np.int32)
+        self.encode_dev(nq, qd, N.F32, codes)
+        rargs = (nq, codes, probe_override, N.INT32_MAX, cap, ids, score, cnt, kept, 0)
+        self.route_dev(*rargs)
+        resolved = self.route_resolve_dev(*rargs)
+        self.gt_rank_dev(nq, ids, score if gscore else 0, cap, cnt, gd, gs, K, rank, gscore)
+        return kept, resolved
+
+    def _attribution_args(self, what, q, k_variants, gt_ids):
+        """store pointer and dtype, ks, queries as fp32 and the caller's ground truth of an attribution call, checked"""
+        code = C.c_int(0)
+        store = self.L.fspann_store_dev_ptr(self._h, C.byref(code))
+        if not store:
+            raise N.FspannStateError("plaintext store not set")
+        if code.value == N.F64:
+            raise N.FspannArgumentError(what + " over an FSPANN_F64 store: the reference's ground truth reads floats")
+        ks = [int(x) for x in k_variants]
+        if not ks:
+            raise N.FspannArgumentError("k_variants is empty")
+        qq = _c(q, np.float32).reshape(-1, self.cfg.dim)
+        g = None
+        if gt_ids is not None:
+            g = _c(gt_ids, np.int32)
+            if g.ndim != 2 or g.shape[0] != qq.shape[0] or g.shape[1] < max(ks):
+                raise N.FspannArgumentError("gt_ids must be [nq][>= max(k_variants)]")
+        return ks, qq, g
+
+    def route_recall(self, q, k_variants, limits=(), gt_ids=None, probe_override=-1):
+        """Where recall is lost, without one Refine: the rank of every true neighbour in Route's full candidate list
+        (lookupCandidatesWithScores' order; the rank of an id is the refinement limit at which the search starts to score it) and the
+        recall ceilings the ranks imply — Route's own (the id is in the list at all: probes and tables) and the ceiling at every
+        refinement limit of limits (the id is among the first B entries: refinementLimit).  One encode, one Route at limit INT32_MAX
+        with score and kept requested, the flagged queries finished by the host model (never -2 here), the ground truth over the
+        store at K = max(k_variants) (groundtruth_store_dev) unless gt_ids [nq][>= K] is given, then gt_rank_dev and
+        recall_ceiling_dev.  No candidate row is read.  An FSPANN_F64 store is refused as run_queries refuses it, a non-finite query
+        as encode() refuses it.
+        Returns dict(gt_ids, rank, gt_score [nq][K]; kept [nq]; hits int32, ceiling float64 [nl + 1][nk][nq], plane l at limits[l], the
+        last plane Route's own; route_ceiling [nk][nq] = that last plane; true_nn_rank = rank[:, 0], true_nn_seen; resolved) — what
+        the reference's lastTrueNNRank / lastTrueNNSeen columns (FSA:740-741) were declared for and never assigned."""
+        ks, qq, g = self._attribution_args("route_recall", q, k_variants, gt_ids)
+        if not np.isfinite(qq).all():
+            raise N.FspannArgumentError("Vector contains NaN/Inf")      # (what encode() says: Coding.java:360)
+        ll = [int(x) for x in limits]
+        K, nk, nl, nq = max(ks), len(ks), len(ll), qq.shape[0]
+        with self._Dev(self) as dv:
+            qd = dv.up(qq)
+            if g is None:
+                gd, gs = dv.new((nq, K), np.int32), K
+                self.groundtruth_store_dev(nq, qd, K, gd)
+            else:
+                gd, gs = dv.up(g), g.shape[1]
+            rank, gscore = dv.new((nq, K), np.int32), dv.new((nq, K), np.int32)
+            kept, resolved = self._route_rank(dv, nq, qd, gd, gs, K, probe_override, rank, gscore)
+            hits, ceil = dv.new((nl + 1, nk, nq), np.int32), dv.new((nl + 1, nk, nq), np.float64)
+            self.recall_ceiling_dev(nq, rank, K, ks, ll, hits, ceil)
+            out = dict(gt_ids=dv.down(gd)[:, :K].copy(), rank=dv.down(rank), gt_score=dv.down(gscore), kept=dv.down(kept), hits=dv.down(hits),
+                       ceiling=dv.down(ceil), resolved=resolved)
+        out["route_ceiling"] = out["ceiling"][nl]
+        out["true_nn_rank"] = out["rank"][:, 0].copy()
+        out["true_nn_seen"] = out["true_nn_rank"] >= 0
+        return out
+
+    def _last_probes(self, probe_override, retried, fellback):
+        """The probes of each query's last pass in run_queries (the rule of fspann_eval.h for whose rows a query keeps): 10 if it
+        retried, else max(2 base, 4) if it fell back (FSA:640, 668-673), else the caller's effective probes."""
+        po = probe_override if probe_override >= 0 else self.cfg.probe_override
+        base = po if po >= 0 else self.cfg.default_probes
+        F = min(max(2 * base, 4), N.INT32_MAX)
+        return np.where(retried != 0, 10, np.where(fellback != 0, F, self.effective_probes(probe_override))).astype(np.int32)
+
+    def _attribute(self, dv, out, qq, gd, gs, ks, B, probe_override):
+        """run_queries(attribution=True): the ranks of the ground truth in the full list of each query's last pass.  The batch splits
+        by the probes of that pass into at most three groups, one full-list Route each."""
+        K, nq = max(ks), qq.shape[0]
+        last = self._last_probes(probe_override, out["retried"], out["fellback"])
+        gt = dv.down(gd)
+        rank = np.full((nq, K), -1, np.int32)
+        good = out["bad"] == 0              # a non-finite query was never coded or searched: its ranks stay -1, its ceilings 0
+        for p in np.unique(last[good]):
+            sel = np.flatnonzero((last == p) & good)
+            qd, gsel = dv.up(np.ascontiguousarray(qq[sel])), dv.up(np.ascontiguousarray(gt[sel]))
+            r = dv.new((len(sel), K), np.int32)
+            self._route_rank(dv, len(sel), qd, gsel, gs, K, int(p), r)
+            rank[sel] = dv.down(r)
+        rd = dv.up(rank)
+        ceil_hits, ceil = dv.new((2, len(ks), nq), np.int32), dv.new((2, len(ks), nq), np.float64)
+        self.recall_ceiling_dev(nq, rd, K, ks, [B], ceil_hits, ceil)
+        c = dv.down(ceil)
+        out.update(last_probes=last, gt_rank=rank, limit_ceiling=c[0], route_ceiling=c[1], true_nn_rank=rank[:, 0].copy(),
+                   true_nn_seen=rank[:, 0] >= 0)
 
     def _groundtruth_host(self, b, qq, k, run):
         """base b and queries qq (host arrays as they go to the device) -> ids, d2 of the device call `run`"""

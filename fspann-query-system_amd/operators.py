@@ -487,13 +487,27 @@ class QueryServiceImpl:
         self.index, self.cryptoService, self.keyService, self.tokenFactory, self.cfg = index, cryptoService, keyService, tf, cfg
         self._refineOverride = None
         self.reencTracker = None
+        self._trueNearestId: Optional[str] = None
         self._clear()
 
-    def _clear(self):
+    def _clear(self):  # QSI:382-393 clearLastMetrics
         self.lastCandTotal = self.lastCandKept = self.lastCandDecrypted = self.lastReturned = 0
         self.lastCandIds: List[str] = []
         self.lastUniqueCandidates = 0
         self.touchedThisSession = set()
+        self.lastTrueNNRank, self.lastTrueNNSeen = -1, False
+
+    def _attribute(self, codes, probe):
+        """lastTrueNNRank / lastTrueNNSeen of a pass at `probe`: the position of trueNearestId in the score-sorted
+        lookupCandidatesWithScores list of that pass (one extra full-list Route; nothing happens while no id is set)."""
+        self.lastTrueNNRank, self.lastTrueNNSeen = -1, False
+        h = self.index._handle.get(self._trueNearestId)
+        if self._trueNearestId is None or h is None:
+            return
+        res = self.index.ctx.route(codes[None], probe_override=probe, limit=N.INT32_MAX)
+        at = np.flatnonzero(res["ids"][0, :int(res["count"][0])] == h)
+        if at.size:
+            self.lastTrueNNRank, self.lastTrueNNSeen = int(at[0]), True
 
     def search(self, token: Optional[QueryToken]) -> List[QueryResult]:
         return self.searchBatch([token])[0]
@@ -504,6 +518,13 @@ class QueryServiceImpl:
 
     # single-token path = literal control flow of the reference
     def _search_one(self, token):
+        self._lastPass = None
+        out = self._search_passes(token)
+        if self._trueNearestId is not None and self._lastPass is not None:
+            self._attribute(*self._lastPass)                                 # once per search: the list of its LAST pass
+        return out
+
+    def _search_passes(self, token):
         if token is None:
             return []
         self._clear()
@@ -524,6 +545,7 @@ class QueryServiceImpl:
                 runtimeLimit = self.getEffectiveRefinementLimit(self.cfg.refinementLimit)
                 ids, _score, kept = idx._route(codes, runtimeLimit)           # stage A + A.5 on the GPU
                 idx._lastTouched = ids
+                self._lastPass = (codes, idx._probeOverride)
                 self.lastCandTotal, self.lastCandKept = idx.getLastRawCandidateCount(), kept
                 if kept == 0:
                     return []
@@ -591,7 +613,7 @@ class QueryServiceImpl:
             if c is None:
                 continue
             qvecs[i], codes[i] = qv, c
-        metrics = {i: dict(total=0, kept=0, decrypted=0, returned=0, unique=0, ids=[], touched=set()) for i in range(n)}
+        metrics = {i: dict(total=0, kept=0, decrypted=0, returned=0, unique=0, ids=[], touched=set(), probe=None) for i in range(n)}
         active = sorted(qvecs)
         probe = idx._probeOverride
         limit = self.getEffectiveRefinementLimit(self.cfg.refinementLimit)
@@ -603,7 +625,7 @@ class QueryServiceImpl:
                 rows_all, rids_all = {}, {}
                 for i, (ids, _score, kept, raw) in zip(active, routed):
                     m = metrics[i]
-                    m["total"], m["kept"], m["unique"] = raw, kept, len(ids)
+                    m["total"], m["kept"], m["unique"], m["probe"] = raw, kept, len(ids), probe
                     rows, rids = [], []
                     for cid in ids:                                                           # stage B host part (QSI:238-271)
                         try:
@@ -653,6 +675,8 @@ class QueryServiceImpl:
             self.lastCandTotal, self.lastCandKept, self.lastCandDecrypted = m["total"], m["kept"], m["decrypted"]
             self.lastReturned, self.lastCandIds, self.lastUniqueCandidates = m["returned"], m["ids"], m["unique"]
             self.touchedThisSession = set(m["touched"])
+            if self._trueNearestId is not None and m["probe"] is not None:
+                self._attribute(codes[last], m["probe"])
         return results
 
     # metrics / overrides (QSI:417-474)
@@ -662,6 +686,23 @@ class QueryServiceImpl:
     def getLastReturned(self): return self.lastReturned
     def getLastFinalResultIds(self): return list(self.lastCandIds)
     def getLastUniqueCandidates(self): return self.lastUniqueCandidates
+    def clearLastMetrics(self): self._clear()
+
+    def setTrueNearestId(self, id):
+        """QSI:422-423.  The reference declares trueNearestId, lastTrueNNRank and lastTrueNNSeen, resets the latter two in
+        clearLastMetrics and exports them as profiler columns (QSI:63-65, 391-392, 438-442; FSA:651-658, 740-741) but never
+        computes them: its columns are always -1 / false.  Here, once an id is set (None: unset, the default), every search
+        fills them from the full lookupCandidatesWithScores list of its last pass — the rank is the id's position in that
+        score-sorted list, at the cost of one extra full-list Route per search."""
+        self._trueNearestId = id
+
+    def getLastTrueNNRank(self):
+        """QSI:438-440: -1 while no id is set (the reference's constant answer) or when Route never offered the id"""
+        return self.lastTrueNNRank
+
+    def wasLastTrueNNSeen(self):
+        """QSI:441-443"""
+        return self.lastTrueNNSeen
     def setRefinementLimit(self, limit): self._refineOverride = int(limit)
     def clearRefinementLimit(self): self._refineOverride = None
     def getEffectiveRefinementLimit(self, defaultLimit):

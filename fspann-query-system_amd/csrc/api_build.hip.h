@@ -76,10 +76,10 @@ extern "C" {
 int fspann_build_index(fspann_ctx* c, int64_t n, const void* vectors, int dtype, const int32_t* order) {
     CHECK_CTX(c);
     CHECK_UNSHARED(c);
-    if (!c->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
+    if (!c->fam->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
     if (!vectors) return fail(FSPANN_E_NULL, "vector cannot be null");
     if (n <= 0) return fail(FSPANN_E_ARG, "n <= 0");
-    if (c->n_ids < n) return fail(FSPANN_E_STATE, "set id metadata for at least n handles first");
+    if (c->fam->n_ids < n) return fail(FSPANN_E_STATE, "set id metadata for at least n handles first");
     if (!is_row_dtype(dtype)) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     return guarded([&]() -> int {
         int rc = build_begin_impl(c, n);
@@ -94,7 +94,7 @@ int fspann_build_index(fspann_ctx* c, int64_t n, const void* vectors, int dtype,
 int fspann_build_begin(fspann_ctx* c, int64_t n_total) {
     CHECK_CTX(c);
     CHECK_UNSHARED(c);
-    if (!c->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
+    if (!c->fam->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
     if (n_total <= 0 || n_total >= (1LL << 31)) return fail(FSPANN_E_ARG, "n_hint out of range");
     return guarded([&]() -> int { return build_begin_impl(c, n_total); });
 }
@@ -113,7 +113,7 @@ int fspann_build_finish(fspann_ctx* c, const int32_t* order) {
     CHECK_UNSHARED(c);
     if (c->bld_done < 0) return fail(FSPANN_E_STATE, "no build in progress (fspann_build_begin)");
     if (c->bld_done == 0) return fail(FSPANN_E_STATE, "no rows appended");
-    if (c->n_ids < c->bld_done) return fail(FSPANN_E_STATE, "%lld rows appended but id metadata covers %lld handles (fspann_set_id_meta)", (long long)c->bld_done, (long long)c->n_ids);
+    if (c->fam->n_ids < c->bld_done) return fail(FSPANN_E_STATE, "%lld rows appended but id metadata covers %lld handles (fspann_set_id_meta)", (long long)c->bld_done, (long long)c->fam->n_ids);
     return guarded([&]() -> int {
         c->bld_n = c->bld_done;     // the rows appended are the index
         const int rc = build_finish_impl(c, order);
@@ -161,7 +161,7 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
     const int capf = java_final_cap_host(table_size_for(static_cast<int>(std::min<int64_t>(n, 1 << 30))), n);
     std::vector<uint32_t> bucket(static_cast<size_t>(n));
     for (int64_t i = 0; i < n; i++) {
-        uint32_t h = static_cast<uint32_t>(c->h_java_hash[ord[i]]);
+        uint32_t h = static_cast<uint32_t>(c->fam->h_java_hash[ord[i]]);
         h ^= (h >> 16);
         bucket[i] = h & static_cast<uint32_t>(capf - 1);
     }
@@ -176,7 +176,7 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
         int64_t thr = static_cast<int64_t>(static_cast<float>(cap) * 0.75f);
         std::vector<uint8_t> occ(static_cast<size_t>(cap), 0);
         for (int64_t i = 0; i < n && !tree_bins; i++) {
-            uint32_t h = static_cast<uint32_t>(c->h_java_hash[ord[i]]);
+            uint32_t h = static_cast<uint32_t>(c->fam->h_java_hash[ord[i]]);
             h ^= (h >> 16);
             uint8_t& o = occ[h & static_cast<uint32_t>(cap - 1)];
             if (o >= 8 && cap >= 64) { tree_bins = true; break; }
@@ -187,7 +187,7 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
                 thr = (oldCap >= 16) ? (thr << 1) : static_cast<int64_t>(static_cast<float>(cap) * 0.75f);
                 occ.assign(static_cast<size_t>(cap), 0);
                 for (int64_t j = 0; j <= i; j++) {
-                    uint32_t hj = static_cast<uint32_t>(c->h_java_hash[ord[j]]);
+                    uint32_t hj = static_cast<uint32_t>(c->fam->h_java_hash[ord[j]]);
                     hj ^= (hj >> 16);
                     uint8_t& oj = occ[hj & static_cast<uint32_t>(cap - 1)];
                     if (oj < 255) oj++;
@@ -197,9 +197,9 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
     }
     std::vector<uint32_t> iter_pos;        // tree_bins: staged positions in the map's iteration order
     if (tree_bins) {
-        jdk::HashMapModel<replay::KeyOrderView> mp(static_cast<int32_t>(std::min<int64_t>(n, INT32_MAX)), replay::KeyOrderView{c->decimal_ids});
+        jdk::HashMapModel<replay::KeyOrderView> mp(static_cast<int32_t>(std::min<int64_t>(n, INT32_MAX)), replay::KeyOrderView{c->fam->decimal_ids});
         mp.reserve(static_cast<size_t>(n));
-        for (int64_t i = 0; i < n; i++) mp.put(ord[i], c->h_java_hash[ord[i]], i);
+        for (int64_t i = 0; i < n; i++) mp.put(ord[i], c->fam->h_java_hash[ord[i]], i);
         if (mp.unmodelled)
             return fail(FSPANN_E_STATE, "a treeified HashMap bin of the staging map holds different ids with EQUAL String.hashCode and the ids are not "
                         "decimal ordinals: their String.compareTo order is unknown to the library, import the partitions with fspann_set_index instead");
@@ -271,7 +271,7 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
             hipLaunchKernelGGL(build_cut_kernel, dim3(eg), dim3(256), 0, c->stream, d_key[cur], d_pay[cur], d_ord, codes_all, TD, W, td, n, S, d_min, d_max,
                                d_repo, d_offo, d_idso);
             FSP_HIP(hipGetLastError());
-            auto& mn = c->h_min[td]; auto& mx = c->h_max[td]; auto& rp = c->h_rep[td]; auto& of = c->h_off[td]; auto& ii = c->h_ids[td];
+            auto& mn = c->fam->h_min[td]; auto& mx = c->fam->h_max[td]; auto& rp = c->fam->h_rep[td]; auto& of = c->fam->h_off[td]; auto& ii = c->fam->h_ids[td];
             mn.resize(np); mx.resize(np); rp.resize(static_cast<size_t>(np) * W); of.resize(np + 1); ii.resize(n);
             FSP_HIP(hipMemcpyAsync(mn.data(), d_min, np * 8, hipMemcpyDeviceToHost, c->stream));
             FSP_HIP(hipMemcpyAsync(mx.data(), d_max, np * 8, hipMemcpyDeviceToHost, c->stream));
@@ -279,9 +279,9 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
             FSP_HIP(hipMemcpyAsync(of.data(), d_offo, (np + 1) * 8, hipMemcpyDeviceToHost, c->stream));
             FSP_HIP(hipMemcpyAsync(ii.data(), d_idso, pb, hipMemcpyDeviceToHost, c->stream));
             FSP_HIP(hipStreamSynchronize(c->stream));       // the outputs of this table are on the host before the scratch is reused
-            c->h_table_set[td] = 1;
+            c->fam->h_table_set[td] = 1;
         }
-        c->dev_index_dirty = true;
+        c->fam->dev_index_dirty = true;
         return fspann_finalize(c);
     }
     struct Ent { int64_t key; uint32_t bucket; int32_t pos; };
@@ -307,7 +307,7 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
             return a.pos < b.pos;
         });
         const int64_t np = (n + S - 1) / S;
-        auto& mn = c->h_min[td]; auto& mx = c->h_max[td]; auto& rp = c->h_rep[td]; auto& of = c->h_off[td]; auto& ii = c->h_ids[td];
+        auto& mn = c->fam->h_min[td]; auto& mx = c->fam->h_max[td]; auto& rp = c->fam->h_rep[td]; auto& of = c->fam->h_off[td]; auto& ii = c->fam->h_ids[td];
         mn.resize(np); mx.resize(np); rp.resize(static_cast<size_t>(np) * W); of.resize(np + 1); ii.resize(n);
         for (int64_t p = 0; p < np; p++) {
             const int64_t i0 = p * S, i1 = std::min<int64_t>(i0 + S, n);
@@ -320,7 +320,7 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
             for (int64_t i = i0; i < i1; i++) ii[i] = ord[ents[i].pos];
         }
         of[np] = n;
-        c->h_table_set[td] = 1;
+        c->fam->h_table_set[td] = 1;
       }
      } catch (...) { worker_oom = true; }
     };
@@ -332,7 +332,7 @@ int build_finish_impl(fspann_ctx* c, const int32_t* order) {
         for (auto& th : pool) th.join();
     }
     if (worker_oom) return fail(FSPANN_E_NOMEM, "out of host memory while cutting partitions");
-    c->dev_index_dirty = true;
+    c->fam->dev_index_dirty = true;
     return fspann_finalize(c);
 }
 }  // namespace

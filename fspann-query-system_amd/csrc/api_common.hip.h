@@ -29,15 +29,6 @@ int java_final_cap_host(int cap0, int64_t n) {
     return cap;
 }
 
-void free_dev(void*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-template <typename T> void free_devt(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 int resolve_unmodelled(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int probe_override, int32_t limit, int64_t cap, int32_t* ids_dev,
                        int32_t* score_dev, int32_t* count_dev, int32_t* kept_dev, int32_t* raw_dev, int64_t* resolved_out, int64_t* left_out);   // api_ext.hip.h
 
@@ -66,15 +57,14 @@ template <class F> int guarded(F&& f) noexcept {
     CHECK_CTX_NOLOCK(c);     \
     std::lock_guard<std::recursive_mutex> _ctx_lock((c)->mu)
 
-// the deleted-id mirror of the index this context serves (its own, or its owner's when it is a clone)
-inline fspann_ctx* index_owner(fspann_ctx* c) { return c->share_parent ? c->share_parent : c; }
-
 // State shared through fspann_ctx_clone is read-only: a clone cannot change it, its owner cannot while clones are alive.
-#define CHECK_UNSHARED(c)                                                                                               \
-    do {                                                                                                                \
-        if ((c)->share_parent) return fail(FSPANN_E_STATE, "a clone reads its parent's index: it cannot be changed here"); \
-        if ((c)->share_children.load() > 0) return fail(FSPANN_E_STATE, "the index is shared with %d clone(s): destroy them first", (c)->share_children.load()); \
-    } while (0)
+inline bool may_change_shared(const fspann_ctx* c) { return !c->is_clone && c->fam->clones.load() == 0; }
+// ... and the refusal of a call that would change `what` ("index", "store", "touched set")
+inline int refuse_shared(const fspann_ctx* c, const char* what) {
+    if (c->is_clone) return fail(FSPANN_E_STATE, "a clone reads its parent's %s: it cannot be changed here", what);
+    return fail(FSPANN_E_STATE, "the %s is shared with %d clone(s): destroy them first", what, c->fam->clones.load());
+}
+#define CHECK_UNSHARED(c) do { if (!may_change_shared(c)) return refuse_shared(c, "index"); } while (0)
 
 // One Refine job on the device: what the entry point or internal caller builds once and every layer down to the launch and the
 // touched-record mark reads.  gather: the rows are the resident store's, row j of query qi is rows[cand_ids[qi * B + j]]; else
@@ -91,7 +81,7 @@ struct RefineJob {
 // ... over the context's resident store
 RefineJob store_job(const fspann_ctx* c, const void* q, int q_dtype, int64_t nq, int64_t B, const int32_t* cand_ids, const int32_t* cand_count, int k, int32_t* out_ids,
                     double* out_dist, int32_t* out_count, int32_t* scored, const int32_t* qlist = nullptr, const int32_t* qcount = nullptr) {
-    return {q, q_dtype, c->d_store, c->store_dtype, true, nq, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount};
+    return {q, q_dtype, c->store->rows, c->store->dtype, true, nq, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored, qlist, qcount};
 }
 
 // The one dispatch over (query dtype, row dtype) of a scan: f(query type tag, row type tag) -> int, or the refusal.

@@ -21,18 +21,18 @@ int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* co
     const int64_t big_blocks = ((nq + 63) / 64) * ((P + 255) / 256);
     if (big_blocks >= 16 * static_cast<int64_t>(c->num_cus) && c->knob_mfma_tile != 1) {
         dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(2) - 1) / mfma_tile_q(2)), static_cast<unsigned>((P + mfma_tile_p(2) - 1) / mfma_tile_p(2)));
-        hipLaunchKernelGGL((encode_mfma_kernel<TIn, 2, 2>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->d_alphaT32, c->d_r, c->d_omega, P, c->cfg.m,
-                           c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->alpha_norm_max);
+        hipLaunchKernelGGL((encode_mfma_kernel<TIn, 2, 2>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P, c->cfg.m,
+                           c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max);
     } else {
         dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)), static_cast<unsigned>((P + mfma_tile_p(1) - 1) / mfma_tile_p(1)));
-        hipLaunchKernelGGL((encode_mfma_kernel<TIn, 1, 1>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->d_alphaT32, c->d_r, c->d_omega, P, c->cfg.m,
-                           c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->alpha_norm_max);
+        hipLaunchKernelGGL((encode_mfma_kernel<TIn, 1, 1>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P, c->cfg.m,
+                           c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max);
     }
     FSP_HIP(hipGetLastError());
     // (a wave per kFixG pairs: as many blocks as the list can need, at most four per CU — the waves stride over the tasks)
     const int64_t fix_blocks = std::min<int64_t>(static_cast<int64_t>(c->num_cus) * 4, (cap + kFixG * 4 - 1) / (kFixG * 4));
     hipLaunchKernelGGL((encode_fix_kernel<TIn>), dim3(static_cast<unsigned>(std::max<int64_t>(1, fix_blocks))), dim3(256), 0, c->stream,
-                       q_dev, d, c->d_alpha_rows, c->d_r, c->d_omega, P, c->cfg.m, c->cfg.lambda, c->W, c->TD, list, cnt, cap, hashes_dev, cw);
+                       q_dev, d, c->fam->d_alpha_rows.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P, c->cfg.m, c->cfg.lambda, c->W, c->TD, list, cnt, cap, hashes_dev, cw);
     FSP_HIP(hipGetLastError());
     c->fix_cap_last = static_cast<unsigned long long>(cap);
     return 1;  // caller enqueues the exact kernel guarded by (count > cap): it only runs if the list overflowed
@@ -49,7 +49,7 @@ int launch_encode(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_d
     // 48 / 75, 1 024 x 1 024 x 768 132 / 77, 4 096 x 256 x 960 169 / 94, 8 192 x 1 024 x 768 758 / 273, 262 144 x 256 x 128 1 080 / 502.
     const bool want_mfma = (c->encode_mode == 2) ||
                            (c->encode_mode == 0 && static_cast<double>(nq) * c->P_total * c->cfg.dim >= 5.0e8);
-    if (want_mfma && !proj_dev && c->d_alphaT32 && c->W <= 3) {      // (the fused bit-pack epilogue carries three code words: <= 192 bits)
+    if (want_mfma && !proj_dev && c->fam->d_alphaT32.get() && c->W <= 3) {      // (the fused bit-pack epilogue carries three code words: <= 192 bits)
         int rc = launch_encode_mfma<TIn>(c, nq, q_dev, codes_dev, hashes_dev, bad_dev);
         if (rc <= 0) return rc;  // error
         // the list can only overflow when almost every pair sits on a bucket boundary (degenerate omega): the
@@ -62,7 +62,7 @@ int launch_encode(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_d
     }
     const int tdPerBlock = std::max(1, kEncThreads / m);
     const int gy = (c->TD + tdPerBlock - 1) / tdPerBlock;
-    const EncodeArgs<TIn> ea{q_dev, nq, c->cfg.dim, c->d_alphaT, c->d_r, c->d_omega, c->P_total, m, c->cfg.lambda, c->W, c->TD, tdPerBlock,
+    const EncodeArgs<TIn> ea{q_dev, nq, c->cfg.dim, c->fam->d_alphaT.get(), c->fam->d_r.get(), c->fam->d_omega.get(), c->P_total, m, c->cfg.lambda, c->W, c->TD, tdPerBlock,
                              codes_dev, hashes_dev, bad_dev, proj_dev, guard, guard_cap, c->dbg_route};
     // QB queries per block: 8 for bulk coding (index build), 4 for query batches so that
     // a 1024-query batch still fills 256 CUs.
@@ -104,7 +104,7 @@ extern "C" {
 int fspann_encode_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int dtype, uint64_t* codes_dev,
                       int32_t* hashes_dev, int32_t* bad_dev) {
     CHECK_CTX(c);
-    if (!c->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized. Build index first.");
+    if (!c->fam->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized. Build index first.");
     if (nq < 0) return fail(FSPANN_E_ARG, "nq < 0");
     if (nq == 0) return FSPANN_OK;
     if (!q_dev || !codes_dev) return fail(FSPANN_E_NULL, "query vector is null");
@@ -116,7 +116,7 @@ int fspann_encode_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int dtype, u
 
 int fspann_encode(fspann_ctx* c, int64_t nq, const void* q, int dtype, uint64_t* codes, int32_t* hashes) {
     CHECK_CTX(c);
-    if (!c->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized. Build index first.");
+    if (!c->fam->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized. Build index first.");
     if (nq < 0) return fail(FSPANN_E_ARG, "nq < 0");
     if (nq == 0) return FSPANN_OK;
     if (!q || !codes) return fail(FSPANN_E_NULL, "query vector is null");

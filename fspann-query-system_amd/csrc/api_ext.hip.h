@@ -38,7 +38,6 @@ int resolve_unmodelled(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int
 int resolve_queries(fspann_ctx* c, const std::vector<int64_t>& todo, const uint64_t* codes_dev, int probe_override, int32_t limit, int64_t cap,
                     int32_t* ids_dev, int32_t* score_dev, int32_t* count_dev, int32_t* kept_dev, int32_t* raw_dev, int64_t* resolved_out, int64_t* left_out) {
     if (todo.empty()) return FSPANN_OK;
-    fspann_ctx* root = index_owner(c);
     const int TD = c->TD, W = c->W;
     const size_t cw = static_cast<size_t>(TD) * W;
     std::vector<uint64_t> codes(todo.size() * cw);
@@ -46,13 +45,13 @@ int resolve_queries(fspann_ctx* c, const std::vector<int64_t>& todo, const uint6
         FSP_HIP(hipMemcpy(codes.data() + t * cw, codes_dev + static_cast<size_t>(todo[t]) * cw, cw * 8, hipMemcpyDeviceToHost));
     std::vector<uint32_t> del;
     {
-        std::lock_guard<std::mutex> dl(root->deleted_mu);
-        if (root->d_deleted_bits.load(std::memory_order_acquire)) del = root->h_deleted_bits;
+        std::lock_guard<std::mutex> dl(c->fam->deleted_mu);
+        if (c->fam->d_deleted_bits.load(std::memory_order_acquire)) del = c->fam->h_deleted_bits;
     }
     replay::IndexView v;
     v.TD = TD; v.W = W; v.S = c->cfg.block_size;
-    v.min_key = &root->h_min; v.max_key = &root->h_max; v.rep = &root->h_rep; v.id_off = &root->h_off; v.ids = &root->h_ids;
-    v.java_hash = root->h_java_hash.data(); v.decimal_ids = root->decimal_ids; v.deleted_bits = del.empty() ? nullptr : del.data();
+    v.min_key = &c->fam->h_min; v.max_key = &c->fam->h_max; v.rep = &c->fam->h_rep; v.id_off = &c->fam->h_off; v.ids = &c->fam->h_ids;
+    v.java_hash = c->fam->h_java_hash.data(); v.decimal_ids = c->fam->decimal_ids; v.deleted_bits = del.empty() ? nullptr : del.data();
     const int probes = effective_probes(c, probe_override);
     std::vector<replay::Result> res(todo.size());
     {
@@ -88,9 +87,9 @@ int resolve_queries(fspann_ctx* c, const std::vector<int64_t>& todo, const uint6
     }
     if (resolved) {       // they are no longer "unmodelled": take them off the context's counter
         int32_t v0 = 0;
-        FSP_HIP(hipMemcpy(&v0, c->d_unmodelled, 4, hipMemcpyDeviceToHost));
+        FSP_HIP(hipMemcpy(&v0, c->d_unmodelled.get(), 4, hipMemcpyDeviceToHost));
         v0 = static_cast<int32_t>(std::max<int64_t>(0, static_cast<int64_t>(v0) - resolved));
-        FSP_HIP(hipMemcpy(c->d_unmodelled, &v0, 4, hipMemcpyHostToDevice));
+        FSP_HIP(hipMemcpy(c->d_unmodelled.get(), &v0, 4, hipMemcpyHostToDevice));
     }
     if (resolved_out) *resolved_out = resolved;
     if (left_out) *left_out = left;
@@ -124,7 +123,7 @@ int fspann_search_store_finish_dev(fspann_ctx* c, int64_t nq, const void* q_dev,
     if (resolved) *resolved = 0;
     if (int rc = refuse_row_only(q_dtype, "q_dtype")) return rc;     // (whether or not a query is left to finish)
     if (!c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     if (nq < 0 || B <= 0 || B > INT32_MAX) return fail(FSPANN_E_ARG, "nq < 0 or B out of range");
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
@@ -150,26 +149,25 @@ int fspann_set_deleted(fspann_ctx* c, const int32_t* handles, int64_t n, int fla
     if (n < 0) return fail(FSPANN_E_ARG, "n < 0");
     if (n == 0) return FSPANN_OK;
     if (!handles) return fail(FSPANN_E_NULL, "handles is null");
-    fspann_ctx* root = index_owner(c);
-    if (root->n_ids <= 0) return fail(FSPANN_E_STATE, "id metadata not set (fspann_set_id_meta)");
+    if (c->fam->n_ids <= 0) return fail(FSPANN_E_STATE, "id metadata not set (fspann_set_id_meta)");
     for (int64_t i = 0; i < n; i++)
-        if (handles[i] < 0 || handles[i] >= root->n_ids) return fail(FSPANN_E_ARG, "handle %d out of range [0,%lld)", handles[i], (long long)root->n_ids);
+        if (handles[i] < 0 || handles[i] >= c->fam->n_ids) return fail(FSPANN_E_ARG, "handle %d out of range [0,%lld)", handles[i], (long long)c->fam->n_ids);
     return guarded([&]() -> int {
-        std::lock_guard<std::mutex> dl(root->deleted_mu);
-        const size_t words = static_cast<size_t>((root->n_ids + 31) / 32);
-        if (root->h_deleted_bits.size() != words) root->h_deleted_bits.assign(words, 0u);
-        uint32_t* bits = root->d_deleted_bits.load(std::memory_order_acquire);
+        std::lock_guard<std::mutex> dl(c->fam->deleted_mu);
+        const size_t words = static_cast<size_t>((c->fam->n_ids + 31) / 32);
+        if (c->fam->h_deleted_bits.size() != words) c->fam->h_deleted_bits.assign(words, 0u);
+        uint32_t* bits = c->fam->d_deleted_bits.load(std::memory_order_acquire);
         if (!bits) {
             if (!flag) return FSPANN_OK;                        // nothing is deleted: nothing to undelete
             // first deletion on this index: allocate the mirror (all clear) and publish it; kernels enqueued from now on read it
             FSP_HIP(hipMalloc(&bits, words * 4));
             if (hipMemset(bits, 0, words * 4) != hipSuccess) { (void)hipFree(bits); return fail(FSPANN_E_DEVICE, "hipMemset failed"); }
-            root->d_deleted_bits.store(bits, std::memory_order_release);
+            c->fam->d_deleted_bits.store(bits, std::memory_order_release);
         }
         for (int64_t i = 0; i < n; i++) {
             const int32_t h = handles[i];
-            if (flag) root->h_deleted_bits[h >> 5] |= 1u << (h & 31);
-            else root->h_deleted_bits[h >> 5] &= ~(1u << (h & 31));
+            if (flag) c->fam->h_deleted_bits[h >> 5] |= 1u << (h & 31);
+            else c->fam->h_deleted_bits[h >> 5] &= ~(1u << (h & 31));
         }
         // On THIS context's stream, then waited for: Route calls enqueued (on any context of the family) after this call
         // returns see the change; calls already in flight see the old or the new flag — as a JVM query racing a delete does.

@@ -177,9 +177,9 @@ int fspann_nn1_exact_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int
                                double* out_d2_dev) {
     return guarded([&]() -> int {
         CHECK_CTX(c);
-        if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-        if (c->store_dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no exact top-1 over an FSPANN_F64 store: the reference's validator reads floats or bytes");
-        return nn1_exact(c, c->store_n, c->d_store, c->store_dtype, nq, q_dev, q_dtype, c->cfg.dim, qsel_dev, nsel, out_idx_dev, out_d2_dev);
+        if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
+        if (c->store->dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no exact top-1 over an FSPANN_F64 store: the reference's validator reads floats or bytes");
+        return nn1_exact(c, c->store->n, c->store->rows, c->store->dtype, nq, q_dev, q_dtype, c->cfg.dim, qsel_dev, nsel, out_idx_dev, out_d2_dev);
     });
 }
 
@@ -195,9 +195,9 @@ int fspann_gt_validate_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, i
                                  int64_t sample_size, double tolerance, fspann_gt_validation* out) {
     return guarded([&]() -> int {
         CHECK_CTX(c);
-        if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-        if (c->store_dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no exact top-1 over an FSPANN_F64 store: the reference's validator reads floats or bytes");
-        return gt_validate(c, c->store_n, c->d_store, c->store_dtype, nq, q_dev, q_dtype, c->cfg.dim, gt_ids_dev, gt_rows, gt_stride, sample_size, tolerance, out);
+        if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
+        if (c->store->dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no exact top-1 over an FSPANN_F64 store: the reference's validator reads floats or bytes");
+        return gt_validate(c, c->store->n, c->store->rows, c->store->dtype, nq, q_dev, q_dtype, c->cfg.dim, gt_ids_dev, gt_rows, gt_stride, sample_size, tolerance, out);
     });
 }
 

@@ -202,9 +202,9 @@ int fspann_groundtruth_rows_dev(fspann_ctx* c, int64_t n, const void* base_dev, 
 int fspann_groundtruth_store_dev(fspann_ctx* c, int64_t nq, const float* q_dev, int k, int32_t* out_ids_dev, double* out_d2_dev) {
     CHECK_CTX(c);
     if (!q_dev || !out_ids_dev) return fail(FSPANN_E_NULL, "ground truth buffer is null");
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-    if (c->store_dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no ground truth over an FSPANN_F64 store: the reference's ground truth reads floats");
-    return fspann_groundtruth_rows_dev(c, c->store_n, c->d_store, c->store_dtype, nq, q_dev, c->cfg.dim, k, out_ids_dev, out_d2_dev);
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (c->store->dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no ground truth over an FSPANN_F64 store: the reference's ground truth reads floats");
+    return fspann_groundtruth_rows_dev(c, c->store->n, c->store->rows, c->store->dtype, nq, q_dev, c->cfg.dim, k, out_ids_dev, out_d2_dev);
 }
 
 // ---- multi-GPU merge: one RCCL all-gather of the packed per-rank top-k -------------------------------

@@ -127,40 +127,39 @@ int fspann_rows_narrow_dev(fspann_ctx* c, int64_t n, const void* src_dev, int sr
 int fspann_store_fit(fspann_ctx* c, uint32_t allowed, fspann_fit* out) {
     CHECK_CTX(c);
     if (!out) return fail(FSPANN_E_NULL, "out is null");
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-    if (!is_query_dtype(c->store_dtype)) {         // a row-only type: nothing is narrower in the order, nothing is scanned
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!is_query_dtype(c->store->dtype)) {         // a row-only type: nothing is narrower in the order, nothing is scanned
         *out = fspann_fit{};
-        out->fits = 1u << c->store_dtype;
-        out->narrowest = c->store_dtype;
+        out->fits = 1u << c->store->dtype;
+        out->narrowest = c->store->dtype;
         for (int64_t& f : out->first_misfit) f = -1;
         out->nonfinite = -1;
         return FSPANN_OK;
     }
-    return rows_fit(c, c->store_n, c->d_store, c->store_dtype, c->cfg.dim, allowed, nullptr, out);
+    return rows_fit(c, c->store->n, c->store->rows, c->store->dtype, c->cfg.dim, allowed, nullptr, out);
 }
 
 int fspann_store_narrow(fspann_ctx* c, uint32_t allowed, int* dtype_out) {
     CHECK_CTX(c);
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-    if (c->share_parent) return fail(FSPANN_E_STATE, "a clone reads its parent's store: it cannot be changed here");
-    if (c->share_children.load() > 0) return fail(FSPANN_E_STATE, "the store is shared with %d clone(s): destroy them first", c->share_children.load());
-    if (!c->store_owned)
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!may_change_shared(c)) return refuse_shared(c, "store");      // (in place: the one call that changes a RowStore others may hold)
+    if (!c->store->owned)
         return fail(FSPANN_E_STATE, "the store is attached, caller-owned memory: narrow into a buffer of your own with fspann_rows_narrow_dev and attach that");
-    if (dtype_out) *dtype_out = c->store_dtype;
-    if (!is_query_dtype(c->store_dtype)) return FSPANN_OK;
+    if (dtype_out) *dtype_out = c->store->dtype;
+    if (!is_query_dtype(c->store->dtype)) return FSPANN_OK;
     fspann_fit fit;
-    if (int rc = rows_fit(c, c->store_n, c->d_store, c->store_dtype, c->cfg.dim, allowed, nullptr, &fit)) return rc;
-    if (fit.narrowest == c->store_dtype) return FSPANN_OK;
+    if (int rc = rows_fit(c, c->store->n, c->store->rows, c->store->dtype, c->cfg.dim, allowed, nullptr, &fit)) return rc;
+    if (fit.narrowest == c->store->dtype) return FSPANN_OK;
     void* rows = nullptr;
-    FSP_HIP(hipMalloc(&rows, static_cast<size_t>(c->store_n) * c->cfg.dim * dtype_size(fit.narrowest)));
+    FSP_HIP(hipMalloc(&rows, static_cast<size_t>(c->store->n) * c->cfg.dim * dtype_size(fit.narrowest)));
     int64_t misfits = 0;
-    int rc = rows_narrow(c, c->store_n, c->d_store, c->store_dtype, c->cfg.dim, rows, fit.narrowest, &misfits);      // (synchronises: nothing reads the old rows any more)
+    int rc = rows_narrow(c, c->store->n, c->store->rows, c->store->dtype, c->cfg.dim, rows, fit.narrowest, &misfits);      // (synchronises: nothing reads the old rows any more)
     if (rc) { (void)hipFree(rows); return rc; }
-    free_dev(c->d_store);
-    c->d_store = rows;
-    c->store_dtype = fit.narrowest;
-    c->store_gen++;
-    if (dtype_out) *dtype_out = c->store_dtype;
+    (void)hipFree(c->store->rows);
+    c->store->rows = rows;
+    c->store->dtype = fit.narrowest;
+    c->store->gen++;
+    if (dtype_out) *dtype_out = c->store->dtype;
     return FSPANN_OK;
 }
 

@@ -100,7 +100,7 @@ int launch_refine_dc(fspann_ctx* c, const RefineJob& j) {
         partial = static_cast<RefinePartial*>(c->ws_refine.p);
         pcnt = reinterpret_cast<int32_t*>(static_cast<char*>(c->ws_refine.p) + ((pb + 15) & ~size_t(15)));
     }
-    const RefineArgs<TC, TQ> ra{static_cast<const TQ*>(j.q), static_cast<const TC*>(j.rows), GATHER ? c->store_n : 0, j.B, c->cfg.dim, j.cand_ids, j.cand_count, k, nchunks,
+    const RefineArgs<TC, TQ> ra{static_cast<const TQ*>(j.q), static_cast<const TC*>(j.rows), GATHER ? c->store->n : 0, j.B, c->cfg.dim, j.cand_ids, j.cand_count, k, nchunks,
                                 j.out_ids, j.out_dist, j.out_count, j.scored, partial, pcnt, npieces, cpp, c->dbg_route};
     // The kernel of this scan.  As a stream: stream_wgs workgroups per CU, each walking several (query, chunk) units with the loads
     // of the next tile in flight across unit boundaries (refine_stream_run); else one workgroup per (query, chunk).  Hand-over: the
@@ -232,38 +232,48 @@ void* fspann_host_buffer(fspann_ctx* c, size_t bytes) {
     if (bytes == 0) bytes = 16;
     if (bytes > c->h_rows_bytes) {
         if (hipStreamSynchronize(c->stream) != hipSuccess) (void)hipGetLastError();      // nothing in flight may still read the old block
-        if (c->h_rows) (void)hipHostFree(c->h_rows);
-        c->h_rows = nullptr; c->h_rows_bytes = 0;
+        c->h_rows.reset(); c->h_rows_bytes = 0;
         const size_t want = (bytes + 4095) & ~size_t(4095);
-        if (hipHostMalloc(&c->h_rows, want, hipHostMallocDefault) != hipSuccess) {
+        void* block = nullptr;
+        if (hipHostMalloc(&block, want, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
-            c->h_rows = nullptr;
             fail(FSPANN_E_NOMEM, "cannot pin %zu bytes of host memory", want);
             return nullptr;
         }
+        c->h_rows.reset(block);
         c->h_rows_bytes = want;
     }
-    return c->h_rows;
+    return c->h_rows.get();
 }
 
 // ---- plaintext store (test / bench harness) ----------------------------------------------
+// A fresh, empty RowStore in place of the one c refers to, the stream drained first: nothing in flight reads the old rows when the
+// last reference to them goes, and a context never holds two stores of its own in HBM.
+static int store_renew(fspann_ctx* c) {
+    FSP_HIP(hipStreamSynchronize(c->stream));
+    return guarded([&]() -> int {
+        auto s = std::make_shared<RowStore>();
+        s->gen = c->store->gen + 1;
+        c->store = std::move(s);
+        return FSPANN_OK;
+    });
+}
+
+// (a clone lets go of its source's rows and refers to its own from here on; an owner may not replace rows that clones read)
 int fspann_store_set(fspann_ctx* c, int64_t n, const void* vectors, int dtype) {
     CHECK_CTX(c);
-    if (c->share_children.load() > 0) return fail(FSPANN_E_STATE, "the store is shared with %d clone(s): destroy them first", c->share_children.load());
+    if (!c->is_clone && !may_change_shared(c)) return refuse_shared(c, "store");
     if (!vectors) return fail(FSPANN_E_NULL, "vectors is null");
     if (n <= 0) return fail(FSPANN_E_ARG, "n <= 0");
     if (!is_row_dtype(dtype)) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     const size_t bytes = static_cast<size_t>(n) * c->cfg.dim * dtype_size(dtype);
-    FSP_HIP(hipStreamSynchronize(c->stream));
-    if (c->store_owned) free_dev(c->d_store);
-    c->d_store = nullptr;
-    c->store_n = 0;
-    FSP_HIP(hipMalloc(&c->d_store, bytes));
-    c->store_owned = true;
-    FSP_HIP(hipMemcpy(c->d_store, vectors, bytes, hipMemcpyHostToDevice));
-    c->store_dtype = dtype;
-    c->store_n = n;
-    c->store_gen++;
+    if (int rc = store_renew(c)) return rc;
+    RowStore& s = *c->store;
+    FSP_HIP(hipMalloc(&s.rows, bytes));
+    s.owned = true;
+    FSP_HIP(hipMemcpy(s.rows, vectors, bytes, hipMemcpyHostToDevice));
+    s.dtype = dtype;
+    s.n = n;
     return FSPANN_OK;
 }
 
@@ -271,18 +281,16 @@ int fspann_store_set(fspann_ctx* c, int64_t n, const void* vectors, int dtype) {
 // memory alive and unchanged while the context refers to it (until the next store_set / store_attach / ctx_destroy).
 int fspann_store_attach_dev(fspann_ctx* c, int64_t n, const void* vectors_dev, int dtype) {
     CHECK_CTX(c);
-    if (c->share_children.load() > 0) return fail(FSPANN_E_STATE, "the store is shared with %d clone(s): destroy them first", c->share_children.load());
+    if (!c->is_clone && !may_change_shared(c)) return refuse_shared(c, "store");
     if (!vectors_dev) return fail(FSPANN_E_NULL, "vectors is null");
     if (n <= 0) return fail(FSPANN_E_ARG, "n <= 0");
     if (!is_row_dtype(dtype)) return fail(FSPANN_E_ARG, "unknown dtype %d", dtype);
     if (reinterpret_cast<uintptr_t>(vectors_dev) & 15) return fail(FSPANN_E_ARG, "store rows must be 16-byte aligned");
-    FSP_HIP(hipStreamSynchronize(c->stream));
-    if (c->store_owned) free_dev(c->d_store);
-    c->d_store = const_cast<void*>(vectors_dev);
-    c->store_owned = false;
-    c->store_dtype = dtype;
-    c->store_n = n;
-    c->store_gen++;
+    if (int rc = store_renew(c)) return rc;
+    RowStore& s = *c->store;
+    s.rows = const_cast<void*>(vectors_dev);
+    s.dtype = dtype;
+    s.n = n;
     return FSPANN_OK;
 }
 
@@ -292,7 +300,7 @@ int fspann_refine_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
                             const int32_t* cand_ids_dev, const int32_t* cand_count_dev, int k, int32_t* out_ids_dev,
                             double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev) {
     CHECK_CTX(c);
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     int rc = check_refine_args(nq, B, k, q_dev && cand_ids_dev && cand_count_dev && out_ids_dev && out_dist_dev && out_count_dev);
     if (rc || nq == 0) return rc;
     return refine_run(c, store_job(c, q_dev, q_dtype, nq, B, cand_ids_dev, cand_count_dev, k, out_ids_dev, out_dist_dev, out_count_dev, scored_dev));
@@ -303,12 +311,12 @@ int fspann_refine_store(fspann_ctx* c, int64_t nq, const void* q, int q_dtype, i
                         const int32_t* cand_count, int k, int32_t* out_ids, double* out_dist, int32_t* out_count,
                         int32_t* scored) {
     CHECK_CTX(c);
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     int rc = check_refine_args(nq, B, k, q && cand_ids && cand_count && out_ids && out_dist && out_count);
     if (rc || nq == 0) return rc;
     if ((rc = refuse_row_only(q_dtype, "q_dtype"))) return rc;
     if (!is_query_dtype(q_dtype)) return fail(FSPANN_E_ARG, "q_dtype %d: a query is FSPANN_F32 or FSPANN_F64", q_dtype);
-    return refine_staged(c, {q, q_dtype, nullptr, c->store_dtype, true, nq, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored}, RefineIo::store_policy);
+    return refine_staged(c, {q, q_dtype, nullptr, c->store->dtype, true, nq, B, cand_ids, cand_count, k, out_ids, out_dist, out_count, scored}, RefineIo::store_policy);
 }
 
 // QueryServiceImpl.search for a batch, all three stages in stream order with one call: TokenGen codes (encode),
@@ -320,7 +328,7 @@ int fspann_search_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
                             int32_t* sel_ids_dev, int32_t* sel_count_dev, int32_t* bad_dev) {
     CHECK_CTX(c);
     if (!c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     if (nq < 0 || B <= 0 || B > INT32_MAX) return fail(FSPANN_E_ARG, "nq < 0 or B out of range");
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (nq == 0) return FSPANN_OK;
@@ -338,23 +346,23 @@ int fspann_search_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_
 
 const void* fspann_store_dev_ptr(fspann_ctx* c, int* dtype) {
     if (!c) return nullptr;
-    if (dtype) *dtype = c->store_dtype;
-    return c->d_store;
+    if (dtype) *dtype = c->store->dtype;
+    return c->store->rows;
 }
 
 int fspann_store_gather_dev(fspann_ctx* c, int64_t nq, const int32_t* sel_ids_dev, const int32_t* sel_count_dev, int64_t B,
                             void* cand_dev) {
     CHECK_CTX(c);
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     if (!sel_ids_dev || !sel_count_dev || !cand_dev) return fail(FSPANN_E_NULL, "gather buffer is null");
     if (nq <= 0 || B <= 0) return FSPANN_OK;
     const int d = c->cfg.dim;
     const int64_t rows = nq * B;
     const unsigned grid = static_cast<unsigned>((rows + 7) / 8);
-    with_row_type(c->store_dtype, [&](auto tc) {      // (a store has a row dtype: fspann_store_set / _attach_dev)
+    with_row_type(c->store->dtype, [&](auto tc) {      // (a store has a row dtype: fspann_store_set / _attach_dev)
         using T = typename decltype(tc)::type;
         const int vec_ok = (d % RowCodec<T>::N == 0) && ((reinterpret_cast<uintptr_t>(cand_dev) & 15) == 0);
-        hipLaunchKernelGGL(store_gather_kernel<T>, dim3(grid), dim3(256), 0, c->stream, static_cast<const T*>(c->d_store), d, sel_ids_dev, sel_count_dev, B, nq,
+        hipLaunchKernelGGL(store_gather_kernel<T>, dim3(grid), dim3(256), 0, c->stream, static_cast<const T*>(c->store->rows), d, sel_ids_dev, sel_count_dev, B, nq,
                            static_cast<T*>(cand_dev), vec_ok);
     });
     FSP_HIP(hipGetLastError());

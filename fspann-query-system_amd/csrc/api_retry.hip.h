@@ -239,7 +239,7 @@ int pipeline_retry(fspann_pipeline* p, fspann_pipeline::Slot& s) {
 
 int check_retry_args(fspann_ctx* c, int64_t nq, const void* q_dev, int64_t B, int k, int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev) {
     if (!c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     if (nq < 0 || B <= 0 || B > INT32_MAX) return fail(FSPANN_E_ARG, "nq < 0 or B out of range");
     if (k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");  // QueryTokenFactory.java:65
     if (nq > INT32_MAX) return fail(FSPANN_E_ARG, "nq > INT32_MAX");

@@ -108,9 +108,10 @@ int plan_route(fspann_ctx* c, int probe_override, int64_t nq, int32_t limit, Rou
     // is seen only by its exact check over bin16 (route_lazy.hip.h, step 0).  Opaque ids (caller-supplied String.hashCode) always run
     // it; decimal ordinals — whose hashCodes spread ~4 500 ids over 32 768 bins like random draws, nine in one bin ~2e-9 per query —
     // run it when FSPANN_ROUTE_BINCHECK=1 asks for it.  No bin16 where it is needed: the full select.
-    pl.bincheck = (c->knob_bincheck == 1) || (c->knob_bincheck < 0 && !c->decimal_ids);
-    const bool check_ok = !pl.bincheck || c->d_bin16 != nullptr;
-    const bool legal = c->d_inv && c->d_ids_bk && c->bk_epoch == c->meta_epoch && !pl.need_cap && cap_fixed && !want_counters && limit <= (for_tick ? 512 : 1024) && pl.lds_mode && check_ok;
+    const IndexFamily& fam = *c->fam;
+    pl.bincheck = (c->knob_bincheck == 1) || (c->knob_bincheck < 0 && !fam.decimal_ids);
+    const bool check_ok = !pl.bincheck || fam.d_bin16.get() != nullptr;
+    const bool legal = fam.d_inv.get() && fam.d_ids_bk.get() && fam.bk_epoch == fam.meta_epoch && !pl.need_cap && cap_fixed && !want_counters && limit <= (for_tick ? 512 : 1024) && pl.lds_mode && check_ok;
     if (legal && c->route_mode != 1 && (c->route_mode == 2 || static_cast<int64_t>(limit) * 4 <= mt)) {
         const int cap_env = c->knob_lazy_cap;   // tests: distinct ids one query may hold before it is handed back
         // size class: 512 entries (19.7 KB, 8 workgroups per CU at 16 x 5) when limit <= 256 and the probe's scratch fits the smaller key
@@ -186,9 +187,10 @@ int prepare_route(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int prob
     const size_t su_g = pl.g_sub ? static_cast<size_t>(pl.grid) * static_cast<size_t>(pl.maxcand) * 4 : 0;          // sub-keys grouped by score
     if (ar_g + so_g + su_g && (rc = ensure(c, c->ws_route, ar_g + so_g + su_g + 1024))) return rc;
     RouteParams p{};
-    p.codes = codes_dev; p.tables = c->d_tables; p.recs = c->d_recs; p.rec_words = c->rec_words; p.ids = c->d_ids;
-    p.dir = c->knob_probe_dir ? c->d_dir : nullptr; p.dir_bits = c->dir_bits;
-    p.java_hash = c->d_java_hash; p.deleted_bits = index_owner(c)->d_deleted_bits.load(std::memory_order_acquire);
+    const IndexFamily& fam = *c->fam;        // (one look at the shared state per call; the deleted bits as published by now)
+    p.codes = codes_dev; p.tables = fam.d_tables.get(); p.recs = fam.d_recs.get(); p.rec_words = fam.rec_words; p.ids = fam.d_ids.get();
+    p.dir = c->knob_probe_dir ? fam.d_dir.get() : nullptr; p.dir_bits = fam.dir_bits;
+    p.java_hash = fam.d_java_hash.get(); p.deleted_bits = fam.d_deleted_bits.load(std::memory_order_acquire);
     p.nq = nq; p.TD = c->TD; p.W = c->W; p.P = pl.P; p.S = pl.S; p.S_shift = pl.S_shift;
     p.hard_cap = c->hard_cap; p.cap0 = c->cap0; p.limit = limit; p.need_cap = pl.need_cap; p.nbins = pl.nbins;
     p.seq_bits = pl.seq_bits;
@@ -203,8 +205,8 @@ int prepare_route(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int prob
     p.slice_bits = pl.slice_bits; p.slice_ht = pl.slice_ht; p.dev_flags = c->knob_devflags;
     p.wave_sort = pl.wave_sort;
     p.dbg = c->dbg_route;
-    p.unmodelled = c->d_unmodelled;
-    p.decimal_ids = c->decimal_ids ? 1 : 0;
+    p.unmodelled = c->d_unmodelled.get();
+    p.decimal_ids = fam.decimal_ids ? 1 : 0;
     p.out_cap = cap; p.out_ids = ids_dev; p.out_score = score_dev; p.out_count = count_dev; p.out_kept = kept_dev; p.out_raw = raw_seen_dev;
     // probe lists in global memory: route_probe_kernel's output, and where the bounded select puts a query it hands over
     const size_t TPn = static_cast<size_t>(c->TD) * pl.P;
@@ -224,8 +226,8 @@ int prepare_route(fspann_ctx* c, int64_t nq, const uint64_t* codes_dev, int prob
         // (tick: the full select of PENDING queries) leave the turn alone, or the next call would start on a counter
         // nobody zeroed and hand its full select a list with another batch's queries in front.
         if (launches_lazy) c->ovf_flip ^= 1;
-        p.bin16 = pl.bincheck ? c->d_bin16 : nullptr; p.bin16_shift = c->bin16_shift;
-        p.inv = c->d_inv; p.ids_bk = c->d_ids_bk; p.n_ids = c->n_ids; p.lazy_cap = pl.lazy_cap; p.lz_ht_size = pl.lz_ht_size;
+        p.bin16 = pl.bincheck ? fam.d_bin16.get() : nullptr; p.bin16_shift = fam.bin16_shift;
+        p.inv = fam.d_inv.get(); p.ids_bk = fam.d_ids_bk.get(); p.n_ids = fam.n_ids; p.lazy_cap = pl.lazy_cap; p.lz_ht_size = pl.lz_ht_size;
         p.lz_ht_shift = 32 - __builtin_ctz(pl.lz_ht_size);
         p.ovf_count = static_cast<int32_t*>(c->ws_ovf.p) + 16 * c->ovf_flip;          // this call's counter ...
         p.ovf_next = static_cast<int32_t*>(c->ws_ovf.p) + 16 * (c->ovf_flip ^ 1);      // ... the next call's is zeroed meanwhile
@@ -267,7 +269,7 @@ int launch_bounded_select(fspann_ctx* c, const RoutePlan& pl, const RouteParams&
     if (pl.lz_entries == 512) {
         if (list) return go(route_select_lazy_list_kernel<kLzThreads, 512, false>, false);
         // (the shape of BASELINE configs #2 / #3 — 16 tables x 5 probes, blocks of 64 — has a build with the shape as constants)
-        if (c->knob_shape_spec && c->TD == 16 && pl.P == 5 && pl.S == 64 && c->W == 1 && c->rec_words == 4 && (p.probe_G == 16 || p.probe_G == 0))
+        if (c->knob_shape_spec && c->TD == 16 && pl.P == 5 && pl.S == 64 && c->W == 1 && c->fam->rec_words == 4 && (p.probe_G == 16 || p.probe_G == 0))
             return go(route_select_lazy_kernel<kLzThreads, 512, false, 16, 5>, false);
         return go(route_select_lazy_kernel<kLzThreads, 512, false>, false);
     }
@@ -411,9 +413,9 @@ int fspann_unmodelled_queries(fspann_ctx* c, int64_t* total, int reset) {
     CHECK_CTX(c);
     FSP_HIP(hipStreamSynchronize(c->stream));
     int32_t v = 0;
-    FSP_HIP(hipMemcpy(&v, c->d_unmodelled, 4, hipMemcpyDeviceToHost));
+    FSP_HIP(hipMemcpy(&v, c->d_unmodelled.get(), 4, hipMemcpyDeviceToHost));
     if (total) *total = v;
-    if (reset && v) FSP_HIP(hipMemset(c->d_unmodelled, 0, 4));
+    if (reset && v) FSP_HIP(hipMemset(c->d_unmodelled.get(), 0, 4));
     return FSPANN_OK;
 }
 // Which select the last fspann_route[_dev] ran: *lazy = 1 for the bounded select; *overflowed = queries it handed back

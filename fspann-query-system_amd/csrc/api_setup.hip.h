@@ -5,9 +5,10 @@
 namespace {
 
 int upload_index(fspann_ctx* c) {
+    IndexFamily& fam = *c->fam;
     const int TD = c->TD, W = c->W;
     for (int td = 0; td < TD; td++)
-        if (!c->h_table_set[td]) return fail(FSPANN_E_STATE, "table %d was never set (fspann_set_index)", td);
+        if (!fam.h_table_set[td]) return fail(FSPANN_E_STATE, "table %d was never set (fspann_set_index)", td);
     // Every handle of every table must lie in [0, n_ids) — the kernels index java_hash / deleted_bits / the store with it —
     // and occur at most once per table (a division's HashMap holds an id once, PIS:331-346; the select kernels rely on it).
     // Checked here rather than in fspann_set_index because the documented import order sets the tables before the id metadata.
@@ -20,12 +21,12 @@ int upload_index(fspann_ctx* c) {
         for (int w = 0; w < nthv; w++)
             thv.emplace_back([&, w] {
                 try {
-                    std::vector<uint64_t> seen(static_cast<size_t>((c->n_ids + 63) / 64));
+                    std::vector<uint64_t> seen(static_cast<size_t>((fam.n_ids + 63) / 64));
                     for (int td = w; td < TD && bad_td.load() < 0; td += nthv) {
                         std::fill(seen.begin(), seen.end(), 0ull);
-                        for (const int32_t id : c->h_ids[td]) {
+                        for (const int32_t id : fam.h_ids[td]) {
                             int kind = 0;
-                            if (id < 0 || id >= c->n_ids) kind = 1;
+                            if (id < 0 || id >= fam.n_ids) kind = 1;
                             else if ((seen[static_cast<size_t>(id) >> 6] >> (id & 63)) & 1ull) kind = 2;
                             if (kind) { bad_td = td; bad_kind = kind; bad_id = id; return; }
                             seen[static_cast<size_t>(id) >> 6] |= 1ull << (id & 63);
@@ -37,42 +38,42 @@ int upload_index(fspann_ctx* c) {
         if (oom) return fail(FSPANN_E_NOMEM, "out of host memory");
         if (bad_td.load() >= 0)
             return bad_kind.load() == 1
-                       ? fail(FSPANN_E_ARG, "table %d: id handle %lld out of range [0,%lld)", bad_td.load(), bad_id.load(), (long long)c->n_ids)
+                       ? fail(FSPANN_E_ARG, "table %d: id handle %lld out of range [0,%lld)", bad_td.load(), bad_id.load(), (long long)fam.n_ids)
                        : fail(FSPANN_E_ARG, "table %d holds id handle %lld twice", bad_td.load(), bad_id.load());
     }
     // Key ranges must ascend over a table's partitions, as GreedyPartitioner cuts them (sorted keys; equal and overlapping ranges
     // are fine): the reference's findNearestPartition is a binary search and means nothing else, and the probe's directory and
     // G-ary search (route.hip.h, route_probe_table) find its centre only then.
     for (int td = 0; td < TD; td++) {
-        const auto& mn = c->h_min[td]; const auto& mx = c->h_max[td];
+        const auto& mn = fam.h_min[td]; const auto& mx = fam.h_max[td];
         for (size_t i = 0; i < mn.size(); i++)
             if (!(mn[i] >= 0 && mn[i] <= mx[i] && (i == 0 || (mn[i] >= mn[i - 1] && mx[i] >= mx[i - 1]))))
                 return fail(FSPANN_E_ARG, "table %d: key range of partition %lld does not ascend (minKey %lld, maxKey %lld)", td, (long long)i,
                             (long long)mn[i], (long long)mx[i]);
     }
-    c->h_tables.assign(TD, RouteTable{});
+    fam.h_tables.assign(TD, RouteTable{});
     int64_t parts = 0, offs = 0, ids = 0;
     for (int td = 0; td < TD; td++) {
-        RouteTable& t = c->h_tables[td];
+        RouteTable& t = fam.h_tables[td];
         t.part_base = parts;
         t.off_base = offs;
         t.ids_base = ids;
-        t.nparts = static_cast<int32_t>(c->h_min[td].size());
+        t.nparts = static_cast<int32_t>(fam.h_min[td].size());
         t.dir_base = 0;
         parts += t.nparts;
         offs += t.nparts + 1;
-        ids += static_cast<int64_t>(c->h_ids[td].size());
+        ids += static_cast<int64_t>(fam.h_ids[td].size());
     }
-    c->total_parts = parts;
-    c->total_ids = ids;
-    free_devt(c->d_tables); free_devt(c->d_recs); free_devt(c->d_ids); free_devt(c->d_dir);
+    fam.total_parts = parts;
+    fam.total_ids = ids;
+    fam.d_tables.reset(); fam.d_recs.reset(); fam.d_ids.reset(); fam.d_dir.reset();
     // Radix directory of the probe (route.hip.h, route_probe_table): for every table and every value p of the key's top
     // dir_bits bits, the first partition with maxKey >= p << s and the first with minKey >= p << s (key ranges ascend: checked above).
     std::vector<int2> dir;
-    c->dir_bits = 0;
+    fam.dir_bits = 0;
     {
         int maxp = 0;
-        for (int td = 0; td < TD; td++) maxp = std::max<int>(maxp, static_cast<int>(c->h_min[td].size()));
+        for (int td = 0; td < TD; td++) maxp = std::max<int>(maxp, static_cast<int>(fam.h_min[td].size()));
         int bits = 1;
         while (bits < 16 && (4 << bits) < maxp) bits++;      // about four partitions per directory entry
         // ... and up to six bits more while the whole directory stays within 64 MB: keys are skewed (the most popular 12-bit prefix of
@@ -89,9 +90,9 @@ int upload_index(fspann_ctx* c) {
             dir.resize(static_cast<size_t>(TD) * (D + 1));
             const int sh = 63 - bits;
             for (int td = 0; td < TD; td++) {
-                const auto& mn = c->h_min[td]; const auto& mx = c->h_max[td];
+                const auto& mn = fam.h_min[td]; const auto& mx = fam.h_max[td];
                 const int np = static_cast<int>(mn.size());
-                c->h_tables[td].dir_base = static_cast<int32_t>(static_cast<size_t>(td) * (D + 1));
+                fam.h_tables[td].dir_base = static_cast<int32_t>(static_cast<size_t>(td) * (D + 1));
                 int2* dd = dir.data() + static_cast<size_t>(td) * (D + 1);
                 int ia = 0, ie = 0;
                 for (size_t pfx = 0; pfx < D; pfx++) {
@@ -102,46 +103,46 @@ int upload_index(fspann_ctx* c) {
                 }
                 dd[D] = make_int2(np, np);
             }
-            c->dir_bits = bits;
+            fam.dir_bits = bits;
         }
     }
     // One RECORD per partition with everything the probe reads about it — {minKey, maxKey, rep[W], id offset | size << 32},
     // padded to an even number of 8-byte words: the last rounds of the search, the gap rule and the Hamming round then touch
     // the same one or two cache lines instead of three arrays (the probe is bound by the latency of cold lines).
     const int rec_words = (3 + W + 1) & ~1;
-    c->rec_words = rec_words;
+    fam.rec_words = rec_words;
     std::vector<int64_t> recs(static_cast<size_t>(std::max<int64_t>(parts, 1)) * rec_words, 0);
     std::vector<int32_t> idv(static_cast<size_t>(std::max<int64_t>(ids, 1)));
     for (int td = 0; td < TD; td++) {
-        const RouteTable& t = c->h_tables[td];
+        const RouteTable& t = fam.h_tables[td];
         for (int p = 0; p < t.nparts; p++) {
             int64_t* r = recs.data() + static_cast<size_t>(t.part_base + p) * rec_words;
-            r[0] = c->h_min[td][p];
-            r[1] = c->h_max[td][p];
-            for (int w = 0; w < W; w++) r[2 + w] = static_cast<int64_t>(c->h_rep[td][static_cast<size_t>(p) * W + w]);
-            const uint64_t b0 = static_cast<uint32_t>(c->h_off[td][p]), sz = static_cast<uint32_t>(c->h_off[td][p + 1] - c->h_off[td][p]);
+            r[0] = fam.h_min[td][p];
+            r[1] = fam.h_max[td][p];
+            for (int w = 0; w < W; w++) r[2 + w] = static_cast<int64_t>(fam.h_rep[td][static_cast<size_t>(p) * W + w]);
+            const uint64_t b0 = static_cast<uint32_t>(fam.h_off[td][p]), sz = static_cast<uint32_t>(fam.h_off[td][p + 1] - fam.h_off[td][p]);
             r[2 + W] = static_cast<int64_t>(b0 | (sz << 32));
         }
-        std::copy(c->h_ids[td].begin(), c->h_ids[td].end(), idv.begin() + t.ids_base);
+        std::copy(fam.h_ids[td].begin(), fam.h_ids[td].end(), idv.begin() + t.ids_base);
     }
-    FSP_HIP(hipMalloc(&c->d_tables, sizeof(RouteTable) * TD));
-    FSP_HIP(hipMalloc(&c->d_recs, recs.size() * 8));
-    FSP_HIP(hipMalloc(&c->d_ids, idv.size() * 4));
-    FSP_HIP(hipMemcpy(c->d_tables, c->h_tables.data(), sizeof(RouteTable) * TD, hipMemcpyHostToDevice));
-    FSP_HIP(hipMemcpy(c->d_recs, recs.data(), recs.size() * 8, hipMemcpyHostToDevice));
-    FSP_HIP(hipMemcpy(c->d_ids, idv.data(), idv.size() * 4, hipMemcpyHostToDevice));
+    FSP_HIP(dev_alloc(fam.d_tables, sizeof(RouteTable) * TD));
+    FSP_HIP(dev_alloc(fam.d_recs, recs.size() * 8));
+    FSP_HIP(dev_alloc(fam.d_ids, idv.size() * 4));
+    FSP_HIP(hipMemcpy(fam.d_tables.get(), fam.h_tables.data(), sizeof(RouteTable) * TD, hipMemcpyHostToDevice));
+    FSP_HIP(hipMemcpy(fam.d_recs.get(), recs.data(), recs.size() * 8, hipMemcpyHostToDevice));
+    FSP_HIP(hipMemcpy(fam.d_ids.get(), idv.data(), idv.size() * 4, hipMemcpyHostToDevice));
     if (!dir.empty()) {
-        FSP_HIP(hipMalloc(&c->d_dir, dir.size() * sizeof(int2)));
-        FSP_HIP(hipMemcpy(c->d_dir, dir.data(), dir.size() * sizeof(int2), hipMemcpyHostToDevice));
+        FSP_HIP(dev_alloc(fam.d_dir, dir.size() * sizeof(int2)));
+        FSP_HIP(hipMemcpy(fam.d_dir.get(), dir.data(), dir.size() * sizeof(int2), hipMemcpyHostToDevice));
     }
     // For the bounded select (route_lazy.hip.h):
     //   inv[td][id]  position of id in table td's id list (a table holding an id twice cannot be inverted: select stays off)
     //   ids_bk       every partition's ids once more, as (id << 32 | bucket field at the initial HashMap capacity),
     //                sorted by bucket within the partition, so the ids with the smallest buckets are a prefix
-    free_devt(c->d_inv); free_devt(c->d_ids_bk); free_devt(c->d_bin16);
-    c->bk_epoch = -1;
-    if (c->n_ids > 0 && static_cast<int64_t>(TD) * c->n_ids < (1LL << 33) && c->cap0 <= (1 << kBucketBits) && c->cfg.block_size <= 4096) {
-        std::vector<int32_t> inv(static_cast<size_t>(TD) * static_cast<size_t>(c->n_ids), -1);
+    fam.d_inv.reset(); fam.d_ids_bk.reset(); fam.d_bin16.reset();
+    fam.bk_epoch = -1;
+    if (fam.n_ids > 0 && static_cast<int64_t>(TD) * fam.n_ids < (1LL << 33) && c->cap0 <= (1 << kBucketBits) && c->cfg.block_size <= 4096) {
+        std::vector<int32_t> inv(static_cast<size_t>(TD) * static_cast<size_t>(fam.n_ids), -1);
         std::vector<uint64_t> bk(static_cast<size_t>(std::max<int64_t>(ids, 1)));
         const int capbits = 31 - __builtin_clz(static_cast<unsigned>(c->cap0));
         const uint32_t bmask = static_cast<uint32_t>(c->cap0 - 1);
@@ -154,19 +155,19 @@ int upload_index(fspann_ctx* c) {
               try {
                 std::vector<uint64_t> tmp;
                 for (int td = w; td < TD; td += nth) {
-                    int32_t* row = inv.data() + static_cast<size_t>(td) * static_cast<size_t>(c->n_ids);
-                    const std::vector<int32_t>& v = c->h_ids[td];
+                    int32_t* row = inv.data() + static_cast<size_t>(td) * static_cast<size_t>(fam.n_ids);
+                    const std::vector<int32_t>& v = fam.h_ids[td];
                     for (size_t i = 0; i < v.size(); i++) {
-                        if (v[i] < 0 || v[i] >= c->n_ids || row[v[i]] != -1) { ok = false; break; }
+                        if (v[i] < 0 || v[i] >= fam.n_ids || row[v[i]] != -1) { ok = false; break; }
                         row[v[i]] = static_cast<int32_t>(i);
                     }
                     if (!ok) return;
-                    const RouteTable& t = c->h_tables[td];
+                    const RouteTable& t = fam.h_tables[td];
                     for (int p = 0; p < t.nparts; p++) {
-                        const int64_t b0 = c->h_off[td][p], b1 = c->h_off[td][p + 1];
+                        const int64_t b0 = fam.h_off[td][p], b1 = fam.h_off[td][p + 1];
                         tmp.clear();
                         for (int64_t i = b0; i < b1; i++) {
-                            uint32_t h = static_cast<uint32_t>(c->h_java_hash[static_cast<size_t>(v[i])]);
+                            uint32_t h = static_cast<uint32_t>(fam.h_java_hash[static_cast<size_t>(v[i])]);
                             h ^= (h >> 16);   // HashMap.hash()
                             const uint64_t bf = static_cast<uint64_t>((h & bmask) << bshift);
                             tmp.push_back((bf << 44) | (static_cast<uint64_t>(i - b0) << 32) | static_cast<uint32_t>(v[i]));   // sort key: bucket, position
@@ -182,25 +183,25 @@ int upload_index(fspann_ctx* c) {
         // bin16: the HashMap bin (table length cap0 <= 65536) of every id in partition order, one padded row of 1 << bin16_shift
         // entries per partition — the bounded select's exact treeify check counts ALL ids of the probed partitions per bin with
         // it (route_lazy.hip.h, step 0).  Built when that check can be asked for: opaque ids (caller-supplied hashCodes), or forced.
-        const bool want_bin16 = (c->knob_bincheck == 1) || (c->knob_bincheck < 0 && !c->decimal_ids);
+        const bool want_bin16 = (c->knob_bincheck == 1) || (c->knob_bincheck < 0 && !fam.decimal_ids);
         std::vector<uint16_t> b16;
         int b16_shift = 0;
         if (ok && want_bin16 && c->cap0 <= 65536 && parts > 0) {
             int64_t maxsz = 4;
             for (int td = 0; td < TD; td++)
-                for (int p = 0; p < c->h_tables[td].nparts; p++) maxsz = std::max<int64_t>(maxsz, c->h_off[td][p + 1] - c->h_off[td][p]);
+                for (int p = 0; p < fam.h_tables[td].nparts; p++) maxsz = std::max<int64_t>(maxsz, fam.h_off[td][p + 1] - fam.h_off[td][p]);
             while ((int64_t(1) << b16_shift) < maxsz) b16_shift++;
             if (b16_shift <= 12 && (static_cast<uint64_t>(parts) << b16_shift) < (uint64_t(1) << 33)) {
                 try {
                     b16.assign(static_cast<size_t>(parts) << b16_shift, 0xFFFFu);
                     for (int td = 0; td < TD; td++) {
-                        const RouteTable& t = c->h_tables[td];
-                        const std::vector<int32_t>& v = c->h_ids[td];
+                        const RouteTable& t = fam.h_tables[td];
+                        const std::vector<int32_t>& v = fam.h_ids[td];
                         for (int p = 0; p < t.nparts; p++) {
                             uint16_t* row = b16.data() + (static_cast<size_t>(t.part_base + p) << b16_shift);
-                            const int64_t b0 = c->h_off[td][p], b1 = c->h_off[td][p + 1];
+                            const int64_t b0 = fam.h_off[td][p], b1 = fam.h_off[td][p + 1];
                             for (int64_t i = b0; i < b1; i++) {
-                                uint32_t h = static_cast<uint32_t>(c->h_java_hash[static_cast<size_t>(v[i])]);
+                                uint32_t h = static_cast<uint32_t>(fam.h_java_hash[static_cast<size_t>(v[i])]);
                                 h ^= (h >> 16);   // HashMap.hash()
                                 row[i - b0] = static_cast<uint16_t>(h & bmask);
                             }
@@ -211,18 +212,18 @@ int upload_index(fspann_ctx* c) {
         }
         if (ok) {
             if (!b16.empty()) {
-                FSP_HIP(hipMalloc(&c->d_bin16, b16.size() * 2 + 64));
-                FSP_HIP(hipMemcpy(c->d_bin16, b16.data(), b16.size() * 2, hipMemcpyHostToDevice));
-                c->bin16_shift = b16_shift;
+                FSP_HIP(dev_alloc(fam.d_bin16, b16.size() * 2 + 64));
+                FSP_HIP(hipMemcpy(fam.d_bin16.get(), b16.data(), b16.size() * 2, hipMemcpyHostToDevice));
+                fam.bin16_shift = b16_shift;
             }
-            FSP_HIP(hipMalloc(&c->d_inv, inv.size() * 4));
-            FSP_HIP(hipMemcpy(c->d_inv, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-            FSP_HIP(hipMalloc(&c->d_ids_bk, bk.size() * 8));
-            FSP_HIP(hipMemcpy(c->d_ids_bk, bk.data(), bk.size() * 8, hipMemcpyHostToDevice));
-            c->bk_epoch = c->meta_epoch;
+            FSP_HIP(dev_alloc(fam.d_inv, inv.size() * 4));
+            FSP_HIP(hipMemcpy(fam.d_inv.get(), inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
+            FSP_HIP(dev_alloc(fam.d_ids_bk, bk.size() * 8));
+            FSP_HIP(hipMemcpy(fam.d_ids_bk.get(), bk.data(), bk.size() * 8, hipMemcpyHostToDevice));
+            fam.bk_epoch = fam.meta_epoch;
         }
     }
-    c->dev_index_dirty = false;
+    fam.dev_index_dirty = false;
     return FSPANN_OK;
 }
 
@@ -254,6 +255,12 @@ int fspann_ctx_create(int device, const fspann_cfg* cfg, fspann_ctx** out) {
     if (e != hipSuccess || ndev <= 0) return fail(FSPANN_E_DEVICE, "no HIP device available (%s)", hipGetErrorString(e));
     if (device < 0 || device >= ndev) return fail(FSPANN_E_ARG, "device %d out of range [0,%d)", device, ndev);
     FSP_HIP(hipSetDevice(device));
+    const int hard_cap = std::max(g.max_global_candidates, g.refinement_limit);  // PIS:612-615
+    const int cap0 = table_size_for(std::min(hard_cap, 1 << 16));                // PIS:619
+    if (hard_cap > 700000) return fail(FSPANN_E_ARG, "max(maxGlobalCandidates, refinementLimit) > 700000 exceeds the %d-bit bucket field", kBucketBits);
+    if (cap0 < 64)
+        return fail(FSPANN_E_ARG, "max(maxGlobalCandidates, refinementLimit) < 33: HashMap order with a table shorter "
+                                  "than MIN_TREEIFY_CAPACITY is not modelled");
     fspann_ctx* c = new (std::nothrow) fspann_ctx();
     if (!c) return fail(FSPANN_E_NOMEM, "out of host memory");
     c->device = device;
@@ -262,17 +269,7 @@ int fspann_ctx_create(int device, const fspann_cfg* cfg, fspann_ctx** out) {
     c->bits = static_cast<int>(bits);
     c->W = (c->bits + 63) / 64;
     c->P_total = c->TD * g.m;
-    c->hard_cap = std::max(g.max_global_candidates, g.refinement_limit);  // PIS:612-615
-    c->cap0 = table_size_for(std::min(c->hard_cap, 1 << 16));             // PIS:619
-    if (c->hard_cap > 700000) {
-        delete c;
-        return fail(FSPANN_E_ARG, "max(maxGlobalCandidates, refinementLimit) > 700000 exceeds the %d-bit bucket field", kBucketBits);
-    }
-    if (c->cap0 < 64) {
-        delete c;
-        return fail(FSPANN_E_ARG, "max(maxGlobalCandidates, refinementLimit) < 33: HashMap order with a table shorter "
-                                  "than MIN_TREEIFY_CAPACITY is not modelled");
-    }
+    c->hard_cap = hard_cap; c->cap0 = cap0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
         c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -317,12 +314,16 @@ int fspann_ctx_create(int device, const fspann_cfg* cfg, fspann_ctx** out) {
             c->knob_front_encode = (fe && std::strcmp(fe, "exact") == 0) ? 0 : 1;   // unset / "mfma": the MFMA role
         }
     }
-    c->h_min.resize(c->TD); c->h_max.resize(c->TD); c->h_off.resize(c->TD); c->h_rep.resize(c->TD); c->h_ids.resize(c->TD);
-    c->h_table_set.assign(c->TD, 0);
-    if (hipMalloc(&c->d_unmodelled, 256) != hipSuccess || hipMemset(c->d_unmodelled, 0, 256) != hipSuccess) {
-        fspann_ctx_destroy(c);
-        return fail(FSPANN_E_NOMEM, "hipMalloc failed");
-    }
+    int rc = guarded([&]() -> int {      // a family and a store of its own, both empty
+        c->fam = std::make_shared<IndexFamily>();
+        c->store = std::make_shared<RowStore>();
+        c->fam->device = device;
+        c->fam->h_min.resize(c->TD); c->fam->h_max.resize(c->TD); c->fam->h_off.resize(c->TD); c->fam->h_rep.resize(c->TD); c->fam->h_ids.resize(c->TD);
+        c->fam->h_table_set.assign(c->TD, 0);
+        return FSPANN_OK;
+    });
+    if (!rc && (dev_alloc(c->d_unmodelled, 256) != hipSuccess || hipMemset(c->d_unmodelled.get(), 0, 256) != hipSuccess)) rc = fail(FSPANN_E_NOMEM, "hipMalloc failed");
+    if (rc) { fspann_ctx_destroy(c); return rc; }
     *out = c;
     return FSPANN_OK;
 }
@@ -338,73 +339,33 @@ void fspann_ctx_destroy(fspann_ctx* c) {
         if (c->comm_refs.load() > 0) return;
         if (!c->destroy_deferred.exchange(false)) return;      // the communicator went in between and took the destroy with it
     }
-    fspann_ctx* parent = c->share_parent;
-    {
-        // the family's bookkeeping (clones alive, owner gone) changes under the OWNER's lock: clones are driven — and destroyed —
-        // from different threads
-        std::unique_lock<std::recursive_mutex> fam((parent ? parent : c)->mu);
-        if (!parent && c->share_children.load() > 0 && !c->zombie) {   // clones still read this context's arrays: keep them until the last clone goes
-            c->zombie = true;
-            return;
-        }
-    }
-    if (parent) {                                   // a clone owns none of the shared arrays
-        c->d_alphaT = nullptr; c->d_r = nullptr; c->d_omega = nullptr; c->d_alphaT32 = nullptr; c->d_alpha_rows = nullptr;
-        c->d_tables = nullptr; c->d_recs = nullptr; c->d_ids = nullptr; c->d_dir = nullptr; c->d_inv = nullptr; c->d_ids_bk = nullptr; c->d_bin16 = nullptr;
-        c->d_java_hash = nullptr; c->d_deleted_bits = nullptr;
-        if (!c->store_owned) c->d_store = nullptr;
-    }
-    free_devt(c->d_alphaT); free_devt(c->d_r); free_devt(c->d_omega); free_devt(c->d_alphaT32); free_devt(c->d_alpha_rows); free_dev(c->ws_fix.p);
-    free_devt(c->d_tables); free_devt(c->d_recs); free_devt(c->d_ids); free_devt(c->d_dir);
-    free_devt(c->d_java_hash); free_devt(c->d_unmodelled);
-    if (uint32_t* db = c->d_deleted_bits.exchange(nullptr)) (void)hipFree(db);
-    if (uint8_t* ts = c->d_touch.exchange(nullptr)) (void)hipFree(ts);
-    free_dev(c->store_ok.p); free_dev(c->ws_touch.p); free_dev(c->ws_narrow.p);
-    if (c->store_owned) free_dev(c->d_store);
-    free_dev(c->ws_tickfix.p); free_dev(c->d_fixparams); free_dev(c->ws_gt.p); free_dev(c->bld_codes.p);
-    free_dev(c->ws_route.p); free_dev(c->ws_refine.p); free_dev(c->ws_probe.p); free_dev(c->ws_ovf.p); free_dev(c->ws_search.p); free_dev(c->ws_retry.p); free_dev(c->ws_fallback.p); free_dev(c->ws_sweep.p); free_devt(c->d_inv); free_devt(c->d_ids_bk); free_devt(c->d_bin16);
     for (hipEvent_t e : c->rt_events) (void)hipEventDestroy(e);
-    for (auto& b : c->ws_io) free_dev(b.p);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    if (c->h_rows) (void)hipHostFree(c->h_rows);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-    if (parent) {
-        bool last_of_zombie;
-        {
-            std::unique_lock<std::recursive_mutex> fam(parent->mu);
-            last_of_zombie = (--parent->share_children == 0) && parent->zombie;
-        }
-        if (last_of_zombie) fspann_ctx_destroy(parent);   // exactly one clone sees the transition to zero
-    }
+    // The family's bookkeeping: a clone leaves the count only now that its stream is idle; an owner's going closes the family to new
+    // clones.  What the family shares lives on with its last member (~IndexFamily), the rows with their last holder (~RowStore).
+    if (c->is_clone) c->fam->clones--;
+    else if (c->fam) c->fam->owner_gone.store(true);
+    const hipStream_t stream = c->stream;
+    delete c;                                       // its work areas, pinned blocks, and its references to the family and the store
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
-// A context that shares src's frozen state (include/fspann.h).
+// A context that shares src's frozen state (include/fspann.h).  Under src's lock: src is not changing what it shares meanwhile, and
+// a family whose count is raised here is either the owner's own (count 0 or more, nothing mutating) or already counted (src is a clone).
 int fspann_ctx_clone(fspann_ctx* src, fspann_ctx** out) {
-    CHECK_CTX_NOLOCK(src);
+    CHECK_CTX(src);
     if (!out) return fail(FSPANN_E_NULL, "out is null");
-    fspann_ctx* root = src->share_parent ? src->share_parent : src;      // clones of clones share the same owner
-    std::lock_guard<std::recursive_mutex> fam(root->mu);                 // the owner's state is read (and its clone count raised) under its lock
     if (!src->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
-    if (src->zombie || root->zombie) return fail(FSPANN_E_STATE, "context was destroyed");
+    if (src->fam->owner_gone.load()) return fail(FSPANN_E_STATE, "context was destroyed");
     fspann_ctx* c = nullptr;
     int rc = fspann_ctx_create(src->device, &src->cfg, &c);
     if (rc) return rc;
-    c->have_g = root->have_g; c->alpha_norm_max = root->alpha_norm_max; c->encode_mode = src->encode_mode;
-    c->h_alpha = root->h_alpha; c->h_r = root->h_r; c->h_omega = root->h_omega;
-    c->d_alphaT = root->d_alphaT; c->d_r = root->d_r; c->d_omega = root->d_omega; c->d_alphaT32 = root->d_alphaT32; c->d_alpha_rows = root->d_alpha_rows;
-    c->h_tables = root->h_tables;
-    c->h_table_set.assign(c->TD, 1);
-    c->d_tables = root->d_tables; c->d_recs = root->d_recs; c->rec_words = root->rec_words; c->d_dir = root->d_dir; c->dir_bits = root->dir_bits;
-    c->d_ids = root->d_ids; c->d_inv = root->d_inv; c->d_ids_bk = root->d_ids_bk; c->d_bin16 = root->d_bin16; c->bin16_shift = root->bin16_shift;
-    c->meta_epoch = root->meta_epoch; c->bk_epoch = root->bk_epoch; c->route_mode = src->route_mode;
-    c->total_parts = root->total_parts; c->total_ids = root->total_ids;
-    c->n_ids = root->n_ids; c->d_java_hash = root->d_java_hash; c->decimal_ids = root->decimal_ids;   // (deleted bits: read from the owner at every call)
-    c->d_store = root->d_store; c->store_owned = false; c->store_dtype = root->store_dtype; c->store_n = root->store_n;
-    c->dev_index_dirty = false;
+    c->fam = src->fam;
+    c->store = src->store;
+    c->encode_mode = src->encode_mode;
+    c->route_mode = src->route_mode;
     c->frozen = true;
-    c->share_parent = root;
-    root->share_children++;
+    c->is_clone = true;
+    c->fam->clones++;
     *out = c;
     return FSPANN_OK;
 }
@@ -420,6 +381,7 @@ int fspann_sync(fspann_ctx* c) {
 int fspann_set_gfunctions(fspann_ctx* c, const double* alpha, const double* r, const double* omega) {
     CHECK_CTX(c);
     CHECK_UNSHARED(c);
+    IndexFamily& fam = *c->fam;
     if (!alpha || !r || !omega) return fail(FSPANN_E_NULL, "alpha/r/omega is null");
     const int P = c->P_total, d = c->cfg.dim;
     for (int p = 0; p < P; p++)
@@ -428,7 +390,7 @@ int fspann_set_gfunctions(fspann_ctx* c, const double* alpha, const double* r, c
     std::vector<double> aT(static_cast<size_t>(d) * P);
     for (int p = 0; p < P; p++)
         for (int i = 0; i < d; i++) aT[static_cast<size_t>(i) * P + p] = alpha[static_cast<size_t>(p) * d + i];
-    free_devt(c->d_alphaT); free_devt(c->d_r); free_devt(c->d_omega); free_devt(c->d_alphaT32); free_devt(c->d_alpha_rows);
+    fam.d_alphaT.reset(); fam.d_r.reset(); fam.d_omega.reset(); fam.d_alphaT32.reset(); fam.d_alpha_rows.reset();
     {
         std::vector<float> aT32(aT.size());
         for (size_t i = 0; i < aT.size(); i++) aT32[i] = static_cast<float>(aT[i]);
@@ -438,20 +400,20 @@ int fspann_set_gfunctions(fspann_ctx* c, const double* alpha, const double* r, c
             for (int i = 0; i < d; i++) s2 += alpha[static_cast<size_t>(pp) * d + i] * alpha[static_cast<size_t>(pp) * d + i];
             nmax = std::max(nmax, std::sqrt(s2));
         }
-        c->alpha_norm_max = nmax * (1.0 + 1e-12);
-        FSP_HIP(hipMalloc(&c->d_alphaT32, aT32.size() * 4));
-        FSP_HIP(hipMemcpy(c->d_alphaT32, aT32.data(), aT32.size() * 4, hipMemcpyHostToDevice));
+        fam.alpha_norm_max = nmax * (1.0 + 1e-12);
+        FSP_HIP(dev_alloc(fam.d_alphaT32, aT32.size() * 4));
+        FSP_HIP(hipMemcpy(fam.d_alphaT32.get(), aT32.data(), aT32.size() * 4, hipMemcpyHostToDevice));
     }
-    FSP_HIP(hipMalloc(&c->d_alphaT, aT.size() * 8));
-    FSP_HIP(hipMalloc(&c->d_r, static_cast<size_t>(P) * 8));
-    FSP_HIP(hipMalloc(&c->d_omega, static_cast<size_t>(P) * 8));
-    FSP_HIP(hipMemcpy(c->d_alphaT, aT.data(), aT.size() * 8, hipMemcpyHostToDevice));
-    FSP_HIP(hipMalloc(&c->d_alpha_rows, aT.size() * 8));
-    FSP_HIP(hipMemcpy(c->d_alpha_rows, alpha, aT.size() * 8, hipMemcpyHostToDevice));
-    FSP_HIP(hipMemcpy(c->d_r, r, static_cast<size_t>(P) * 8, hipMemcpyHostToDevice));
-    FSP_HIP(hipMemcpy(c->d_omega, omega, static_cast<size_t>(P) * 8, hipMemcpyHostToDevice));
-    if (c->h_alpha.data() != alpha) { c->h_alpha.assign(alpha, alpha + static_cast<size_t>(P) * d); c->h_r.assign(r, r + P); c->h_omega.assign(omega, omega + P); }
-    c->have_g = true;
+    FSP_HIP(dev_alloc(fam.d_alphaT, aT.size() * 8));
+    FSP_HIP(dev_alloc(fam.d_r, static_cast<size_t>(P) * 8));
+    FSP_HIP(dev_alloc(fam.d_omega, static_cast<size_t>(P) * 8));
+    FSP_HIP(hipMemcpy(fam.d_alphaT.get(), aT.data(), aT.size() * 8, hipMemcpyHostToDevice));
+    FSP_HIP(dev_alloc(fam.d_alpha_rows, aT.size() * 8));
+    FSP_HIP(hipMemcpy(fam.d_alpha_rows.get(), alpha, aT.size() * 8, hipMemcpyHostToDevice));
+    FSP_HIP(hipMemcpy(fam.d_r.get(), r, static_cast<size_t>(P) * 8, hipMemcpyHostToDevice));
+    FSP_HIP(hipMemcpy(fam.d_omega.get(), omega, static_cast<size_t>(P) * 8, hipMemcpyHostToDevice));
+    if (fam.h_alpha.data() != alpha) { fam.h_alpha.assign(alpha, alpha + static_cast<size_t>(P) * d); fam.h_r.assign(r, r + P); fam.h_omega.assign(omega, omega + P); }
+    fam.have_g = true;
     return FSPANN_OK;
     });
 }
@@ -517,7 +479,7 @@ int fspann_registry_initialize(fspann_ctx* c, const double* sample, int64_t ns, 
     FSP_HIP(hipMemcpyAsync(bad.data(), c->ws_io[2].p, static_cast<size_t>(ns) * 4, hipMemcpyDeviceToHost, c->stream));
     FSP_HIP(hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < ns; i++)
-        if (bad[i]) { c->have_g = false; return fail(FSPANN_E_ARG, "Vector contains NaN/Inf (sample %lld)", (long long)i); }
+        if (bad[i]) { c->fam->have_g = false; return fail(FSPANN_E_ARG, "Vector contains NaN/Inf (sample %lld)", (long long)i); }
     for (int p = 0; p < P; p++) {
         double mn = INFINITY, mx = -INFINITY;
         for (int64_t s = 0; s < ns; s++) {
@@ -532,18 +494,16 @@ int fspann_registry_initialize(fspann_ctx* c, const double* sample, int64_t ns, 
     }
     for (int td = 0; td < TD; td++)
         for (int j = 0; j < m; j++) r[td * m + j] = rngs[td].nextDouble() * w[td * m + j];  // one draw per j, after all alpha
-    c->h_alpha = alpha; c->h_r = r; c->h_omega = w;
-    rc = fspann_set_gfunctions(c, alpha.data(), r.data(), w.data());
-    return rc;
+    return fspann_set_gfunctions(c, alpha.data(), r.data(), w.data());      // (keeps the host copies for export)
     });
 }
 
 int fspann_get_gfunctions(fspann_ctx* c, double* alpha, double* r, double* omega) {
     CHECK_CTX(c);
-    if (!c->have_g || c->h_alpha.empty()) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
-    if (alpha) std::copy(c->h_alpha.begin(), c->h_alpha.end(), alpha);
-    if (r) std::copy(c->h_r.begin(), c->h_r.end(), r);
-    if (omega) std::copy(c->h_omega.begin(), c->h_omega.end(), omega);
+    if (!c->fam->have_g || c->fam->h_alpha.empty()) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
+    if (alpha) std::copy(c->fam->h_alpha.begin(), c->fam->h_alpha.end(), alpha);
+    if (r) std::copy(c->fam->h_r.begin(), c->fam->h_r.end(), r);
+    if (omega) std::copy(c->fam->h_omega.begin(), c->fam->h_omega.end(), omega);
     return FSPANN_OK;
 }
 
@@ -565,13 +525,13 @@ int fspann_set_index(fspann_ctx* c, int td, int64_t n_parts, const int64_t* min_
     // id handles are validated against n_ids by fspann_finalize (the id metadata may arrive after the tables)
     c->frozen = false;
     return guarded([&]() -> int {
-    c->h_min[td].assign(min_key, min_key + n_parts);
-    c->h_max[td].assign(max_key, max_key + n_parts);
-    c->h_rep[td].assign(rep, rep + n_parts * c->W);
-    if (n_parts > 0) c->h_off[td].assign(id_off, id_off + n_parts + 1); else c->h_off[td].assign(1, 0);
-    c->h_ids[td].assign(ids, ids + nid);
-    c->h_table_set[td] = 1;
-    c->dev_index_dirty = true;
+    c->fam->h_min[td].assign(min_key, min_key + n_parts);
+    c->fam->h_max[td].assign(max_key, max_key + n_parts);
+    c->fam->h_rep[td].assign(rep, rep + n_parts * c->W);
+    if (n_parts > 0) c->fam->h_off[td].assign(id_off, id_off + n_parts + 1); else c->fam->h_off[td].assign(1, 0);
+    c->fam->h_ids[td].assign(ids, ids + nid);
+    c->fam->h_table_set[td] = 1;
+    c->fam->dev_index_dirty = true;
     return FSPANN_OK;
     });
 }
@@ -579,38 +539,39 @@ int fspann_set_index(fspann_ctx* c, int td, int64_t n_parts, const int64_t* min_
 int fspann_set_id_meta(fspann_ctx* c, int64_t n_ids, const int32_t* java_hash, const uint8_t* deleted) {
     CHECK_CTX(c);
     CHECK_UNSHARED(c);
+    IndexFamily& fam = *c->fam;
     if (n_ids <= 0 || n_ids >= (1LL << 31)) return fail(FSPANN_E_ARG, "n_ids out of range");
     c->frozen = false;           // Route stays off until the next successful fspann_finalize re-validates every table
     return guarded([&]() -> int {
-    c->h_java_hash.resize(static_cast<size_t>(n_ids));
-    c->decimal_ids = (java_hash == nullptr);
-    if (java_hash) std::copy(java_hash, java_hash + n_ids, c->h_java_hash.begin());
-    else for (int64_t i = 0; i < n_ids; i++) c->h_java_hash[i] = decimal_string_hash(i);
-    free_devt(c->d_java_hash);
-    if (uint32_t* db = c->d_deleted_bits.exchange(nullptr)) (void)hipFree(db);
-    FSP_HIP(hipMalloc(&c->d_java_hash, static_cast<size_t>(n_ids) * 4));
-    FSP_HIP(hipMemcpy(c->d_java_hash, c->h_java_hash.data(), static_cast<size_t>(n_ids) * 4, hipMemcpyHostToDevice));
+    fam.h_java_hash.resize(static_cast<size_t>(n_ids));
+    fam.decimal_ids = (java_hash == nullptr);
+    if (java_hash) std::copy(java_hash, java_hash + n_ids, fam.h_java_hash.begin());
+    else for (int64_t i = 0; i < n_ids; i++) fam.h_java_hash[i] = decimal_string_hash(i);
+    fam.d_java_hash.reset();
+    if (uint32_t* db = fam.d_deleted_bits.exchange(nullptr)) (void)hipFree(db);
+    FSP_HIP(dev_alloc(fam.d_java_hash, static_cast<size_t>(n_ids) * 4));
+    FSP_HIP(hipMemcpy(fam.d_java_hash.get(), fam.h_java_hash.data(), static_cast<size_t>(n_ids) * 4, hipMemcpyHostToDevice));
     {
-        std::lock_guard<std::mutex> dl(c->deleted_mu);
-        c->h_deleted_bits.assign(static_cast<size_t>((n_ids + 31) / 32), 0u);
+        std::lock_guard<std::mutex> dl(fam.deleted_mu);
+        fam.h_deleted_bits.assign(static_cast<size_t>((n_ids + 31) / 32), 0u);
         bool any = false;
         if (deleted)
             for (int64_t i = 0; i < n_ids; i++)
-                if (deleted[i]) { c->h_deleted_bits[i >> 5] |= (1u << (i & 31)); any = true; }
+                if (deleted[i]) { fam.h_deleted_bits[i >> 5] |= (1u << (i & 31)); any = true; }
         if (any) {      // (none deleted: the kernels skip the lookup until the first fspann_set_deleted)
             uint32_t* db = nullptr;
-            FSP_HIP(hipMalloc(&db, c->h_deleted_bits.size() * 4));
-            if (hipMemcpy(db, c->h_deleted_bits.data(), c->h_deleted_bits.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(db); return fail(FSPANN_E_DEVICE, "hipMemcpy failed"); }
-            c->d_deleted_bits.store(db, std::memory_order_release);
+            FSP_HIP(hipMalloc(&db, fam.h_deleted_bits.size() * 4));
+            if (hipMemcpy(db, fam.h_deleted_bits.data(), fam.h_deleted_bits.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(db); return fail(FSPANN_E_DEVICE, "hipMemcpy failed"); }
+            fam.d_deleted_bits.store(db, std::memory_order_release);
         }
     }
-    c->meta_epoch++;             // d_inv / d_ids_bk were built for the previous hashes: the bounded select waits for the next finalize
-    c->dev_index_dirty = true;
-    c->n_ids = n_ids;
+    fam.meta_epoch++;             // d_inv / d_ids_bk were built for the previous hashes: the bounded select waits for the next finalize
+    fam.dev_index_dirty = true;
+    fam.n_ids = n_ids;
     {   // a touched set in use follows the new handle count, cleared (no clone is alive here: CHECK_UNSHARED)
-        std::lock_guard<std::mutex> tl(c->touch_mu);
-        if (c->d_touch.load(std::memory_order_acquire) && c->touch_n != n_ids) {
-            int rc = touch_alloc(c, c);
+        std::lock_guard<std::mutex> tl(fam.touch_mu);
+        if (fam.d_touch.load(std::memory_order_acquire) && fam.touch_n != n_ids) {
+            int rc = touch_alloc(c);
             if (rc) return rc;
         }
     }
@@ -620,11 +581,11 @@ int fspann_set_id_meta(fspann_ctx* c, int64_t n_ids, const int32_t* java_hash, c
 
 int fspann_finalize(fspann_ctx* c) {
     CHECK_CTX(c);
-    if (c->share_parent) return FSPANN_OK;      // a clone is frozen with its parent's state
-    if (c->share_children.load() > 0) return fail(FSPANN_E_STATE, "the index is shared with %d clone(s): destroy them first", c->share_children.load());
-    if (!c->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
-    if (c->n_ids <= 0) return fail(FSPANN_E_STATE, "id metadata not set (fspann_set_id_meta)");
-    if (c->dev_index_dirty) {
+    if (c->is_clone) return FSPANN_OK;          // a clone is frozen with its family's state
+    if (!may_change_shared(c)) return refuse_shared(c, "index");
+    if (!c->fam->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized");
+    if (c->fam->n_ids <= 0) return fail(FSPANN_E_STATE, "id metadata not set (fspann_set_id_meta)");
+    if (c->fam->dev_index_dirty) {
         c->frozen = false;
         int rc = guarded([&]() -> int { return upload_index(c); });
         if (rc) return rc;
@@ -647,7 +608,7 @@ extern "C" {
 
 int fspann_index_save(fspann_ctx* c, const char* path) {
     CHECK_CTX(c);
-    if (c->share_parent) c = c->share_parent;   // the host mirror of a shared index lives in its owner
+    IndexFamily& fam = *c->fam;                 // (the host mirror of the index is the family's)
     if (!path) return fail(FSPANN_E_NULL, "path is null");
     if (!c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
     FILE* f = std::fopen(path, "wb");
@@ -658,21 +619,21 @@ int fspann_index_save(fspann_ctx* c, const char* path) {
     const char magic[8] = {'F', 'S', 'P', 'A', 'N', 'N', 'I', 'X'};
     const uint32_t ver = 1;
     const int32_t hdr[6] = {c->cfg.tables, c->cfg.divisions, c->cfg.m, c->cfg.lambda, c->cfg.dim, c->cfg.block_size};
-    const uint8_t dec = c->decimal_ids ? 1 : 0;
-    ok = ok && wr(f, magic, 8) && wr(f, &ver, 1) && wr(f, hdr, 6) && wr(f, &c->n_ids, 1) && wr(f, &dec, 1);
-    ok = ok && wr(f, c->h_alpha.data(), c->h_alpha.size()) && wr(f, c->h_r.data(), c->h_r.size()) && wr(f, c->h_omega.data(), c->h_omega.size());
-    ok = ok && wr(f, c->h_java_hash.data(), c->h_java_hash.size());
-    std::vector<uint8_t> del(static_cast<size_t>(c->n_ids), 0);
+    const uint8_t dec = fam.decimal_ids ? 1 : 0;
+    ok = ok && wr(f, magic, 8) && wr(f, &ver, 1) && wr(f, hdr, 6) && wr(f, &fam.n_ids, 1) && wr(f, &dec, 1);
+    ok = ok && wr(f, fam.h_alpha.data(), fam.h_alpha.size()) && wr(f, fam.h_r.data(), fam.h_r.size()) && wr(f, fam.h_omega.data(), fam.h_omega.size());
+    ok = ok && wr(f, fam.h_java_hash.data(), fam.h_java_hash.size());
+    std::vector<uint8_t> del(static_cast<size_t>(fam.n_ids), 0);
     {
-        std::lock_guard<std::mutex> dl(c->deleted_mu);
-        if (!c->h_deleted_bits.empty())
-            for (int64_t i = 0; i < c->n_ids; i++) del[i] = (c->h_deleted_bits[i >> 5] >> (i & 31)) & 1u;
+        std::lock_guard<std::mutex> dl(fam.deleted_mu);
+        if (!fam.h_deleted_bits.empty())
+            for (int64_t i = 0; i < fam.n_ids; i++) del[i] = (fam.h_deleted_bits[i >> 5] >> (i & 31)) & 1u;
     }
     ok = ok && wr(f, del.data(), del.size());
     for (int td = 0; td < c->TD && ok; td++) {
-        const int64_t np = static_cast<int64_t>(c->h_min[td].size()), ni = static_cast<int64_t>(c->h_ids[td].size());
-        ok = ok && wr(f, &np, 1) && wr(f, &ni, 1) && wr(f, c->h_min[td].data(), np) && wr(f, c->h_max[td].data(), np) &&
-             wr(f, c->h_rep[td].data(), c->h_rep[td].size()) && wr(f, c->h_off[td].data(), c->h_off[td].size()) && wr(f, c->h_ids[td].data(), ni);
+        const int64_t np = static_cast<int64_t>(fam.h_min[td].size()), ni = static_cast<int64_t>(fam.h_ids[td].size());
+        ok = ok && wr(f, &np, 1) && wr(f, &ni, 1) && wr(f, fam.h_min[td].data(), np) && wr(f, fam.h_max[td].data(), np) &&
+             wr(f, fam.h_rep[td].data(), fam.h_rep[td].size()) && wr(f, fam.h_off[td].data(), fam.h_off[td].size()) && wr(f, fam.h_ids[td].data(), ni);
     }
     ok = (std::fclose(f) == 0) && ok;
     f = nullptr;
@@ -737,25 +698,25 @@ int fspann_index_load(fspann_ctx* c, const char* path) {
 
 int fspann_index_dims(fspann_ctx* c, int td, int64_t* n_parts, int64_t* n_ids) {
     CHECK_CTX(c);
-    if (c->share_parent) c = c->share_parent;   // the host mirror of a shared index lives in its owner
+    IndexFamily& fam = *c->fam;                 // (the host mirror of the index is the family's)
     if (td < 0 || td >= c->TD) return fail(FSPANN_E_ARG, "td out of range");
-    if (!c->h_table_set[td]) return fail(FSPANN_E_STATE, "table %d not set", td);
-    if (n_parts) *n_parts = static_cast<int64_t>(c->h_min[td].size());
-    if (n_ids) *n_ids = static_cast<int64_t>(c->h_ids[td].size());
+    if (!fam.h_table_set[td]) return fail(FSPANN_E_STATE, "table %d not set", td);
+    if (n_parts) *n_parts = static_cast<int64_t>(fam.h_min[td].size());
+    if (n_ids) *n_ids = static_cast<int64_t>(fam.h_ids[td].size());
     return FSPANN_OK;
 }
 
 int fspann_get_index(fspann_ctx* c, int td, int64_t* min_key, int64_t* max_key, uint64_t* rep, int64_t* id_off,
                      int32_t* ids) {
     CHECK_CTX(c);
-    if (c->share_parent) c = c->share_parent;   // the host mirror of a shared index lives in its owner
+    IndexFamily& fam = *c->fam;                 // (the host mirror of the index is the family's)
     if (td < 0 || td >= c->TD) return fail(FSPANN_E_ARG, "td out of range");
-    if (!c->h_table_set[td]) return fail(FSPANN_E_STATE, "table %d not set", td);
-    std::copy(c->h_min[td].begin(), c->h_min[td].end(), min_key);
-    std::copy(c->h_max[td].begin(), c->h_max[td].end(), max_key);
-    std::copy(c->h_rep[td].begin(), c->h_rep[td].end(), rep);
-    std::copy(c->h_off[td].begin(), c->h_off[td].end(), id_off);
-    std::copy(c->h_ids[td].begin(), c->h_ids[td].end(), ids);
+    if (!fam.h_table_set[td]) return fail(FSPANN_E_STATE, "table %d not set", td);
+    std::copy(fam.h_min[td].begin(), fam.h_min[td].end(), min_key);
+    std::copy(fam.h_max[td].begin(), fam.h_max[td].end(), max_key);
+    std::copy(fam.h_rep[td].begin(), fam.h_rep[td].end(), rep);
+    std::copy(fam.h_off[td].begin(), fam.h_off[td].end(), id_off);
+    std::copy(fam.h_ids[td].begin(), fam.h_ids[td].end(), ids);
     return FSPANN_OK;
 }
 

@@ -49,7 +49,7 @@ int launch_refine_keys_t(fspann_ctx* c, const RefineJob& j, int nchunks, uint64_
     int rc = with_tile_width<TC>(c, [&](auto dc) -> int {
         constexpr int DC = decltype(dc)::value;
         const ScanPlan sp = scan_plan<TC, DC, GATHER>(c, j.nq, static_cast<const TC*>(j.rows), nchunks);
-        const RefineArgs<TC, TQ> ra{static_cast<const TQ*>(j.q), static_cast<const TC*>(j.rows), GATHER ? c->store_n : 0, j.B, c->cfg.dim, j.cand_ids, j.cand_count, 0, nchunks,
+        const RefineArgs<TC, TQ> ra{static_cast<const TQ*>(j.q), static_cast<const TC*>(j.rows), GATHER ? c->store->n : 0, j.B, c->cfg.dim, j.cand_ids, j.cand_count, 0, nchunks,
                                     nullptr, nullptr, nullptr, nullptr, reinterpret_cast<RefinePartial*>(keys), nullptr, 0, 0, c->dbg_route};
         int r = FSPANN_OK;
         bool streamed = false;
@@ -126,7 +126,7 @@ struct SweepCall {
 int sweep_search_args(fspann_ctx* c, int64_t nq, const void* q_dev, const int64_t* limits, int nl, int k, int32_t* out_ids_dev, double* out_dist_dev,
                       int32_t* out_count_dev, SweepCall& s) {
     if (!c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     if (nq < 0 || nq > INT32_MAX) return fail(FSPANN_E_ARG, "nq < 0 or nq > INT32_MAX");
     int rc = sweep_check(limits, nl, k, s.lim);
     if (rc) return rc;
@@ -185,8 +185,8 @@ int fspann_refine_store_sweep_dev(fspann_ctx* c, int64_t nq, const void* q_dev, 
                                   const int32_t* cand_count_dev, const int64_t* limits, int nl, int k, int32_t* out_ids_dev, double* out_dist_dev,
                                   int32_t* out_count_dev, int32_t* scored_dev) {
     CHECK_CTX(c);
-    if (!c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
-    return refine_sweep_call<true>(c, nq, q_dev, q_dtype, c->d_store, c->store_dtype, stride, cand_ids_dev, cand_count_dev, limits, nl, k, out_ids_dev, out_dist_dev,
+    if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
+    return refine_sweep_call<true>(c, nq, q_dev, q_dtype, c->store->rows, c->store->dtype, stride, cand_ids_dev, cand_count_dev, limits, nl, k, out_ids_dev, out_dist_dev,
                                    out_count_dev, scored_dev);
 }
 

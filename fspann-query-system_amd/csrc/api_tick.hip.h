@@ -30,7 +30,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
     const bool E = t->nq_encode > 0, R = t->nq_route > 0, F = t->nq_refine > 0;
     if (!E && !R && !F) return FSPANN_OK;
     if ((R || (F && t->ref_handover_dev)) && !c->frozen) return fail(FSPANN_E_STATE, "Index not finalized");
-    if (E && !c->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized. Build index first.");
+    if (E && !c->fam->have_g) return fail(FSPANN_E_STATE, "GFunctionRegistry not initialized. Build index first.");
     if (E && (!t->enc_q_dev || !t->enc_codes_dev)) return fail(FSPANN_E_NULL, "query vector is null");
     if (R && !t->route_codes_dev) return fail(FSPANN_E_STATE, "MSANNP violation: QueryToken missing BitSet codes");
     if (R && (!t->route_ids_dev || !t->route_count_dev)) return fail(FSPANN_E_NULL, "output buffer is null");
@@ -39,7 +39,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
     if (F && t->k <= 0) return fail(FSPANN_E_ARG, "topK must be > 0");
     if (F && (!t->ref_q_dev || !t->ref_ids_dev || !t->ref_count_dev || !t->out_ids_dev || !t->out_dist_dev || !t->out_count_dev))
         return fail(FSPANN_E_NULL, "refine buffer is null");
-    if (F && !t->ref_cand_dev && !c->d_store) return fail(FSPANN_E_STATE, "plaintext store not set");
+    if (F && !t->ref_cand_dev && !c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
     if (F && ((t->ref_handover_dev != nullptr) != (t->ref_codes_dev != nullptr)))
         return fail(FSPANN_E_ARG, "ref_handover_dev and ref_codes_dev go together (the batch's codes and the buffer its Route wrote)");
     const bool gather = F && !t->ref_cand_dev;
@@ -83,8 +83,8 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
 
     // ---- can the three roles share one kernel?
     const int nchunks = F ? static_cast<int>((t->ref_B + kRefRows - 1) / kRefRows) : 1;
-    const void* rows = gather ? c->d_store : t->ref_cand_dev;
-    const int rows_dtype = gather ? c->store_dtype : t->ref_cand_dtype;
+    const void* rows = gather ? c->store->rows : t->ref_cand_dev;
+    const int rows_dtype = gather ? c->store->dtype : t->ref_cand_dtype;
     bool fuse = c->knob_tick_fuse != 0;
     if (E) fuse = fuse && t->enc_dtype == FSPANN_F32;
     if (R) fuse = fuse && plR.lazy && fusedR;
@@ -104,7 +104,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
     // loop that cycles through a few buffer sets uploads each block once
     auto upload_fix = [&](const RouteParams& fixT, const RouteParams** out) -> int {
         if (!c->d_fixparams) {
-            FSP_HIP(hipMalloc(&c->d_fixparams, sizeof(RouteParams) * fspann_ctx::kFixSlots));
+            FSP_HIP(dev_alloc(c->d_fixparams, sizeof(RouteParams) * fspann_ctx::kFixSlots));
             c->h_fixparams.assign(sizeof(RouteParams) * fspann_ctx::kFixSlots, 0);
             c->fix_valid = 0;
         }
@@ -116,10 +116,10 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
             c->fix_next = (c->fix_next + 1) % fspann_ctx::kFixSlots;
             std::memcpy(c->h_fixparams.data() + sizeof(RouteParams) * slot, &fixT, sizeof(RouteParams));
             // stream-ordered: ticks already enqueued that read this slot run before the copy
-            FSP_HIP(hipMemcpyAsync(static_cast<char*>(c->d_fixparams) + sizeof(RouteParams) * slot, &fixT, sizeof(RouteParams), hipMemcpyHostToDevice, c->stream));
+            FSP_HIP(hipMemcpyAsync(static_cast<char*>(c->d_fixparams.get()) + sizeof(RouteParams) * slot, &fixT, sizeof(RouteParams), hipMemcpyHostToDevice, c->stream));
             c->fix_valid |= 1u << slot;
         }
-        *out = reinterpret_cast<const RouteParams*>(static_cast<char*>(c->d_fixparams) + sizeof(RouteParams) * slot);
+        *out = reinterpret_cast<const RouteParams*>(static_cast<char*>(c->d_fixparams.get()) + sizeof(RouteParams) * slot);
         return FSPANN_OK;
     };
 
@@ -200,13 +200,13 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
         const int gy = (c->TD + tdPerBlock - 1) / tdPerBlock;
         p.enc_gx = static_cast<int>((t->nq_encode + kTickEncQB - 1) / kTickEncQB);
         p.n_enc = p.enc_gx * gy;
-        eaT = EncodeArgs<float>{static_cast<const float*>(t->enc_q_dev), t->nq_encode, d, c->d_alphaT, c->d_r, c->d_omega, c->P_total, m, c->cfg.lambda,
+        eaT = EncodeArgs<float>{static_cast<const float*>(t->enc_q_dev), t->nq_encode, d, c->fam->d_alphaT.get(), c->fam->d_r.get(), c->fam->d_omega.get(), c->P_total, m, c->cfg.lambda,
                                   c->W, c->TD, tdPerBlock, t->enc_codes_dev, nullptr, t->enc_bad_dev, nullptr, nullptr, 0, nullptr,
-                                  c->d_alphaT32, c->d_alpha_rows, c->alpha_norm_max};
+                                  c->fam->d_alphaT32.get(), c->fam->d_alpha_rows.get(), c->fam->alpha_norm_max};
         // front launch: the MFMA role (encode_mfma_block) where the stand-alone MFMA path could run (fp32 alpha present, <= 3 code
         // words, encode mode not forced to exact fp64 by fspann_set_encode_mode(1)), for P <= 256 (one pass of its four waves), lambda <= 16 (its h table keeps 16 bits) and when its h table fits the
         // Route workgroups' LDS (the launch's LDS stays theirs)
-        p.enc_mfma = (front_launch && c->knob_front_encode == 1 && c->encode_mode != 1 && c->d_alphaT32 && c->d_alpha_rows && c->W <= 3 && c->P_total <= 4 * 64 && c->cfg.lambda <= 16 &&
+        p.enc_mfma = (front_launch && c->knob_front_encode == 1 && c->encode_mode != 1 && c->fam->d_alphaT32.get() && c->fam->d_alpha_rows.get() && c->W <= 3 && c->P_total <= 4 * 64 && c->cfg.lambda <= 16 &&
                       encode_mfma_block_lds(c->P_total) <= plR.lz_lds_bytes) ? 1 : 0;
         if (p.enc_mfma) {
             p.enc_gx = static_cast<int>((t->nq_encode + kFrontEncQ - 1) / kFrontEncQ);
@@ -223,7 +223,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
     if (F) {
         p.n_refine = static_cast<int>(t->nq_refine);          // one workgroup per query (nchunks == 1)
         p.nq_refine = t->nq_refine;
-        raT = RefineArgs<float, float>{static_cast<const float*>(t->ref_q_dev), static_cast<const float*>(rows), gather ? c->store_n : 0, t->ref_B, d,
+        raT = RefineArgs<float, float>{static_cast<const float*>(t->ref_q_dev), static_cast<const float*>(rows), gather ? c->store->n : 0, t->ref_B, d,
                                          t->ref_ids_dev, t->ref_count_dev, t->k, 1, t->out_ids_dev, t->out_dist_dev, t->out_count_dev, t->scored_dev,
                                          nullptr, nullptr};
         p.has_fix = fix ? 1 : 0;
@@ -246,7 +246,7 @@ int fspann_tick_dev(fspann_ctx* c, const fspann_tick* t) {
     };
     if (front_launch) {
         if (plR.lz_entries == 512) {
-            if (c->knob_shape_spec && c->TD == 16 && plR.P == 5 && plR.S == 64 && c->W == 1 && c->rec_words == 4 && (routeT.probe_G == 16 || routeT.probe_G == 0))
+            if (c->knob_shape_spec && c->TD == 16 && plR.P == 5 && plR.S == 64 && c->W == 1 && c->fam->rec_words == 4 && (routeT.probe_G == 16 || routeT.probe_G == 0))
                 hipLaunchKernelGGL((front_kernel<512, false, 16, 5>), dim3(static_cast<unsigned>(total)), dim3(kTickThreads), lds, c->stream, p, eaT, routeT);
             else
                 hipLaunchKernelGGL((front_kernel<512, false>), dim3(static_cast<unsigned>(total)), dim3(kTickThreads), lds, c->stream, p, eaT, routeT);

@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -95,10 +96,28 @@ struct RouteTable {
     int32_t dir_base;   // first entry pair of this table in the radix directory (RouteParams::dir), in pairs
 };
 
+// Members that free themselves: a device block, a pinned host block, a grown-on-demand work area.  Whoever destroys their holder has
+// set the device and drained the streams that may still read them (fspann_ctx_destroy, ~IndexFamily).
+struct HipFree { void operator()(void* p) const { (void)hipFree(p); } };
+struct HipHostFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+template <class T> using DevPtr = std::unique_ptr<T, HipFree>;
+using PinPtr = std::unique_ptr<void, HipHostFree>;
+// p = a fresh device block of `bytes`; what it held goes first
+template <class T> hipError_t dev_alloc(DevPtr<T>& p, size_t bytes) {
+    p.reset();
+    void* raw = nullptr;
+    const hipError_t e = hipMalloc(&raw, bytes);
+    p.reset(static_cast<T*>(raw));
+    return e;
+}
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
     unsigned gen = 0;   // bumped by every (re)allocation: "same address" does not mean "same contents"
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
 // fspann_ctx::ws_io by what each host-pointer call keeps in a slot on its Direct transport (host_staging.h lays the calls out; a Block
@@ -108,6 +127,84 @@ enum IoSlot : int {
     kIoRouteCodes = 0, kIoRouteIds = 1 /* Block: down */, kIoRouteScores = 2, kIoRouteCounts = 3,
     kIoRefQ = 0, kIoRefRows = 1, kIoRefIds = 2, kIoRefCounts = 3 /* in | count | scored */, kIoRefOutIds = 4 /* Block: down */, kIoRefOutDist = 5,
     kIoHandles = 6      // fspann_set_deleted's handles (api_ext.hip.h)
+};
+
+// What fspann_ctx_clone shares: GFunctions, frozen index, id metadata and touched set of ONE index in HBM, held by shared_ptr from
+// its owner (the context that built or imported it) and from every clone, freed with the last of them.  Read-only while a clone is
+// alive (may_change_shared, api_common.hip.h), except the deleted bits and the touched set: own locks, published as atomics.  The
+// clone count changes only while nothing here can be mutated: a clone is made under its source's lock (an owner mutates under its
+// own lock and at count 0; a clone as source keeps the count above 0) and leaves the count after synchronising its own stream.
+struct IndexFamily {
+    int device = 0;
+    std::atomic<int> clones{0};               // clones alive
+    std::atomic<bool> owner_gone{false};      // the owner was destroyed: the family takes no new clone
+
+    // GFunctions: alphaT[dim][P_total] fp64 (transposed for coalescing), r/omega[P_total]
+    DevPtr<double> d_alphaT;
+    DevPtr<double> d_alpha_rows;               // alpha as the JVM hands it over, [P][d]: the re-check of the MFMA path reads a projection's row 64 dimensions at a time
+    DevPtr<double> d_r, d_omega;
+    std::vector<double> h_alpha, h_r, h_omega;  // host copies (export)
+    DevPtr<float> d_alphaT32;                  // fp32 copy of alphaT for the MFMA fast path
+    double alpha_norm_max = 1.0;               // max_j ||alpha_j||_2 (error bound of the fast path)
+    bool have_g = false;
+
+    // frozen index (concatenated over td)
+    std::vector<RouteTable> h_tables;
+    std::vector<std::vector<int64_t>> h_min, h_max, h_off;  // host mirror per td (export / rebuild / the host's replay of a query)
+    std::vector<std::vector<uint64_t>> h_rep;
+    std::vector<std::vector<int32_t>> h_ids;
+    std::vector<char> h_table_set;
+    bool dev_index_dirty = true;
+    DevPtr<RouteTable> d_tables;
+    DevPtr<int64_t> d_recs;       // [total_parts][rec_words] partition records {minKey, maxKey, rep[W], id offset | size << 32}
+    int rec_words = 0;
+    DevPtr<int2> d_dir;           // radix directory of the probe: [TD][2^dir_bits + 1] {first maxKey >= bound, first minKey >= bound}
+    int dir_bits = 0;
+    DevPtr<int32_t> d_ids;
+    DevPtr<int32_t> d_inv;        // [TD][n_ids] inverse id map for the bounded select (null: a table holds an id twice)
+    DevPtr<uint64_t> d_ids_bk;    // per partition: (id << 32 | bucket field) sorted by bucket, for the bounded select
+    DevPtr<uint16_t> d_bin16;     // [total_parts][1 << bin16_shift] HashMap bin (at cap0) of every id, partition order, padded per partition:
+    int bin16_shift = 0;          //   what the bounded select's exact treeify check reads (one 128-byte line per 64-id partition)
+    int meta_epoch = 0, bk_epoch = -1;  // d_ids_bk / d_inv are valid for the id metadata of bk_epoch
+    int64_t total_parts = 0, total_ids = 0;
+
+    // id metadata
+    int64_t n_ids = 0;
+    DevPtr<int32_t> d_java_hash;
+    std::vector<int32_t> h_java_hash;
+    bool decimal_ids = false;  // ids are Long.toString(handle): String.hashCode computed in-kernel
+    // mirror of metadata.isDeleted (PIS:739), one bit per handle; nullptr => nothing deleted so far.  fspann_set_deleted may allocate
+    // it on any context of the family while the others serve: published with release, read with acquire at every call.
+    std::atomic<uint32_t*> d_deleted_bits{nullptr};
+    std::vector<uint32_t> h_deleted_bits;   // host mirror (guarded by deleted_mu): the host replay of a query reads it
+    std::mutex deleted_mu;
+    // touched-record set of selective re-encryption (api_touch.hip.h): one byte per handle, whole kTouchTile tiles (padding zero).
+    // Every context of the family marks into it.  Allocated / reallocated under touch_mu, and published before touch_on: a context
+    // that sees touch_on sees the set.  Count and drain hold touch_mu.
+    std::mutex touch_mu;
+    std::atomic<uint8_t*> d_touch{nullptr};
+    int64_t touch_n = 0;             // handles the set covers (n_ids when it was allocated)
+    size_t touch_bytes = 0;
+    std::atomic<bool> touch_on{false};
+
+    ~IndexFamily() {
+        (void)hipSetDevice(device);
+        if (uint32_t* db = d_deleted_bits.load()) (void)hipFree(db);
+        if (uint8_t* ts = d_touch.load()) (void)hipFree(ts);
+    }
+};
+
+// The plaintext store (test / bench harness) a context refines from.  A clone starts on its source's store and may install one of
+// its own (fspann_store_set / fspann_store_attach_dev install a NEW RowStore; the rows go with the last context that refers to them).
+struct RowStore {
+    void* rows = nullptr;
+    bool owned = false;              // false: rows attached from caller-owned device memory (fspann_store_attach_dev)
+    int dtype = FSPANN_F32;
+    int64_t n = 0;
+    unsigned gen = 1;                // one more than the store it replaced (fspann_ctx::store_ok_gen keys on it)
+    RowStore() = default;
+    RowStore(const RowStore&) = delete; RowStore& operator=(const RowStore&) = delete;
+    ~RowStore() { if (owned && rows) (void)hipFree(rows); }
 };
 
 }  // namespace fspann
@@ -128,8 +225,11 @@ struct fspann_ctx {
     int num_cus = 256;
     int lds_limit = 160 * 1024;
     bool frozen = false;
-    bool have_g = false;
-    long long* dbg_route = nullptr;  // per-block phase stamps; only reachable in FSPANN_DEBUG_STAMPS builds (tools/)
+    // a clone reads its source's family and store in place; its stream, knobs and work areas are its own and go when IT is destroyed
+    std::shared_ptr<fspann::IndexFamily> fam;
+    std::shared_ptr<fspann::RowStore> store;   // never null; rows == nullptr: no store set
+    bool is_clone = false;           // made by fspann_ctx_clone: counted in fam->clones, may not change what the family shares
+    long long* dbg_route = nullptr;  // per-block phase stamps, caller-owned; only reachable in FSPANN_DEBUG_STAMPS builds (tools/)
     // tuning / test knobs, read from the environment ONCE at fspann_ctx_create (never per call)
     int knob_ht_x4 = 0;              // FSPANN_ROUTE_HT_X4=1: hash load factor <= 0.5 instead of <= 0.8
     int knob_threads = 0;            // FSPANN_ROUTE_THREADS: 512 / 1024 force the full select's workgroup size (0: by list length)
@@ -160,37 +260,10 @@ struct fspann_ctx {
     int last_tick_fused = 0;
     int last_front_encode_mfma = 0;  // the last fspann_tick_dev coded its batch with front_kernel's MFMA role (encode_mfma_block)
 
-    // GFunctions: alphaT[dim][P_total] fp64 (transposed for coalescing), r/omega[P_total]
-    double* d_alphaT = nullptr;
-    double* d_alpha_rows = nullptr;   // alpha as the JVM hands it over, [P][d]: the re-check of the MFMA path reads a projection's row 64 dimensions at a time
-    double* d_r = nullptr;
-    double* d_omega = nullptr;
-    std::vector<double> h_alpha, h_r, h_omega;  // host copies (export)
-    float* d_alphaT32 = nullptr;               // fp32 copy of alphaT for the MFMA fast path
-    double alpha_norm_max = 1.0;               // max_j ||alpha_j||_2 (error bound of the fast path)
     int encode_mode = 0;                       // 0 auto, 1 exact fp64, 2 MFMA fp32 + exact re-check
     unsigned long long fix_cap_last = 0;       // capacity of the re-check list of the last MFMA-path call
     bool mfma_last = false;                    // the last encode took the MFMA path
     fspann::DevBuf ws_fix;                     // fix list + counter + int32 hashes of the MFMA path
-
-    // frozen index (concatenated over td)
-    std::vector<fspann::RouteTable> h_tables;
-    std::vector<std::vector<int64_t>> h_min, h_max, h_off;  // host mirror per td (export / rebuild)
-    std::vector<std::vector<uint64_t>> h_rep;
-    std::vector<std::vector<int32_t>> h_ids;
-    std::vector<char> h_table_set;
-    bool dev_index_dirty = true;
-    fspann::RouteTable* d_tables = nullptr;
-    int64_t* d_recs = nullptr;    // [total_parts][rec_words] partition records {minKey, maxKey, rep[W], id offset | size << 32}
-    int rec_words = 0;
-    int2* d_dir = nullptr;        // radix directory of the probe: [TD][2^dir_bits + 1] {first maxKey >= bound, first minKey >= bound}
-    int dir_bits = 0;
-    int32_t* d_ids = nullptr;
-    int32_t* d_inv = nullptr;        // [TD][n_ids] inverse id map for the bounded select (null: a table holds an id twice)
-    uint64_t* d_ids_bk = nullptr;    // per partition: (id << 32 | bucket field) sorted by bucket, for the bounded select
-    uint16_t* d_bin16 = nullptr;     // [total_parts][1 << bin16_shift] HashMap bin (at cap0) of every id, partition order, padded per partition:
-    int bin16_shift = 0;             //   what the bounded select's exact treeify check reads (one 128-byte line per 64-id partition)
-    int meta_epoch = 0, bk_epoch = -1;  // d_ids_bk / d_inv are valid for the id metadata of bk_epoch
     int route_mode = 0;              // 0 auto, 1 always route_select_kernel, 2 bounded select whenever its preconditions hold
     fspann::DevBuf ws_ovf;
     // kernel-attached HIP events of the refinement scan (fspann_refine_timing_begin / _end)
@@ -212,35 +285,9 @@ struct fspann_ctx {
     int ovf_flip = 0;                // which of the two overflow counters the last bounded select used
     unsigned ovf_gen_seen = 0;       // ws_ovf.gen whose counters have been zeroed (0 = never)
     int last_route_lazy = 0;         // 1 if the last fspann_route[_dev] ran the bounded select
-    int32_t* d_unmodelled = nullptr; // device counter: queries flagged "HashMap bin treeified" (out_count = -1) since the last reset
-    int64_t total_parts = 0, total_ids = 0;
+    fspann::DevPtr<int32_t> d_unmodelled;   // device counter: queries flagged "HashMap bin treeified" (out_count = -1) since the last reset
 
-    // id metadata
-    int64_t n_ids = 0;
-    int32_t* d_java_hash = nullptr;
-    // mirror of metadata.isDeleted (PIS:739), one bit per handle; nullptr => nothing deleted so far.  Owned by the index owner;
-    // a clone reads the OWNER's pointer at every call (fspann_set_deleted may allocate it while clones are alive), so it is atomic.
-    std::atomic<uint32_t*> d_deleted_bits{nullptr};
-    std::vector<uint32_t> h_deleted_bits;   // host mirror (owner only; guarded by deleted_mu): the host replay of a query reads it
-    std::mutex deleted_mu;
-    std::vector<int32_t> h_java_hash;
-    bool decimal_ids = false;  // ids are Long.toString(handle): String.hashCode computed in-kernel
-    // touched-record set of selective re-encryption (api_touch.hip.h): one byte per handle, whole kTouchTile tiles (padding zero).
-    // Owned by the index owner like the deleted bits; the owner and all its clones mark into it.  Allocated / reallocated under
-    // touch_mu, and published before touch_on: a context that sees touch_on sees the set.  Count and drain hold touch_mu.
-    std::mutex touch_mu;
-    std::atomic<uint8_t*> d_touch{nullptr};
-    int64_t touch_n = 0;             // handles the set covers (n_ids when it was allocated)
-    size_t touch_bytes = 0;
-    std::atomic<bool> touch_on{false};
-
-    // plaintext store (test / bench harness)
-    void* d_store = nullptr;
-    bool store_owned = false;        // false: rows attached from caller-owned device memory (fspann_store_attach_dev)
-    int store_dtype = FSPANN_F32;
-    int64_t store_n = 0;
-    unsigned store_gen = 1;          // bumped by fspann_store_set / fspann_store_attach_dev
-    unsigned store_ok_gen = 0;       // store_gen that store_ok was computed for (0: none)
+    unsigned store_ok_gen = 0;       // store->gen that store_ok was computed for (0: none)
     fspann::DevBuf store_ok;         // per store row: 1 = all dim values finite (api_touch.hip.h, computed at the first mark)
     fspann::DevBuf ws_touch;         // tile counts / offsets / total / handles of fspann_touch_count / _drain
     fspann::DevBuf ws_narrow;        // FitResult / NarrowResult of the fit and narrow passes (api_narrow.hip.h)
@@ -252,14 +299,14 @@ struct fspann_ctx {
     fspann::DevBuf ws_gt;      // [query chunk][n] distance matrix of fspann_groundtruth_dev (fp64) / _typed_dev over bytes (uint32, + the norms)
     fspann::DevBuf ws_tickfix; // arenas of the full select run by the refine role of a tick for PENDING queries
     static constexpr int kFixSlots = 8;
-    void* d_fixparams = nullptr;         // kFixSlots RouteParams blocks in device memory (parameters of that redo) ...
+    fspann::DevPtr<void> d_fixparams;    // kFixSlots RouteParams blocks in device memory (parameters of that redo) ...
     std::vector<unsigned char> h_fixparams;   // ... and what each slot holds
     unsigned fix_valid = 0;
     int fix_next = 0;
     fspann::DevBuf ws_io[8];   // staging for the host-pointer entry points (IoSlot)
-    void* h_pin = nullptr;     // pinned host block (kPinBytes) for the small transfers of the host-pointer entry points: one H2D and one D2H
+    fspann::PinPtr h_pin;      // pinned host block (kPinBytes) for the small transfers of the host-pointer entry points: one H2D and one D2H
     void* d_pin = nullptr;     // the same block as the device sees it (mapped host memory): kernels of the tiniest calls read and write it directly
-    void* h_rows = nullptr;    // fspann_host_buffer: pinned host memory the adapter packs decrypted rows into (grown on demand)
+    fspann::PinPtr h_rows;     // fspann_host_buffer: pinned host memory the adapter packs decrypted rows into (grown on demand)
     size_t h_rows_bytes = 0;
                                //   per call instead of one synchronous pageable copy per argument (a per-query caller pays each of them)
     // transient, set by fspann_tick_dev around a refine-only tick: device-resident RouteParams of the batch's hand-over buffer
@@ -268,12 +315,7 @@ struct fspann_ctx {
     size_t refine_fix_lds = 0;
     bool refine_fix_used = false;
 
-    // fspann_ctx_clone: a clone reads its parent's GFunctions, frozen index, id metadata and store in place (no second copy in
-    // HBM, and ONE working set in the caches however many contexts serve it); it owns its stream and work areas.
-    fspann_ctx* share_parent = nullptr;  // non-null: the index arrays above belong to that context
-    std::atomic<int> share_children{0};  // clones alive; the shared state may not change while > 0 (changed under the owner's `mu`)
-    bool zombie = false;                 // destroyed by its owner while clones were alive: freed with the last clone
-    std::atomic<int> comm_refs{0};       // fspann_comm objects that hold this context (it must outlive them)
+    std::atomic<int> comm_refs{0};      // fspann_comm objects that hold this context (it must outlive them)
     std::atomic<bool> destroy_deferred{false};   // fspann_ctx_destroy came while a communicator still held the context: the last fspann_comm_destroy finishes it
     // incremental Setup (fspann_build_begin / _append / _finish): codes of the rows appended so far stay in HBM
     int64_t bld_n = 0, bld_done = -1;    // bld_done < 0: no build in progress

@@ -65,12 +65,14 @@ struct Staging {
     // the context's pinned block, allocated at the first call whose sizes qualify for it (none to be had: the call goes Direct)
     void choose(fspann_ctx* c, int64_t nq, StagePolicy p) {
         if (!c->h_pin && pick(nq, p, {c->knob_zero_copy, true, true}) != Transport::Direct) {
-            if (hipHostMalloc(&c->h_pin, kPinBytes, hipHostMallocDefault) != hipSuccess) { c->h_pin = nullptr; (void)hipGetLastError(); }
-            else if (hipHostGetDevicePointer(&c->d_pin, c->h_pin, 0) != hipSuccess) { c->d_pin = nullptr; (void)hipGetLastError(); }
+            void* block = nullptr;
+            if (hipHostMalloc(&block, kPinBytes, hipHostMallocDefault) != hipSuccess) { block = nullptr; (void)hipGetLastError(); }
+            else if (hipHostGetDevicePointer(&c->d_pin, block, 0) != hipSuccess) { c->d_pin = nullptr; (void)hipGetLastError(); }
+            c->h_pin.reset(block);
         }
         t = pick(nq, p, {c->knob_zero_copy, c->h_pin != nullptr, c->d_pin != nullptr});
     }
-    unsigned char* pin(const fspann_ctx* c) const { return static_cast<unsigned char*>(c->h_pin); }
+    unsigned char* pin(const fspann_ctx* c) const { return static_cast<unsigned char*>(c->h_pin.get()); }
     static size_t grown(size_t need, const Piece& p) { return need > p.slot_off + p.bytes ? need : p.slot_off + p.bytes; }
     // device buffers of this transport, then where a piece lives on the device (a piece of no bytes: nowhere)
     int begin(fspann_ctx* c) {

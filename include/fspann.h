@@ -131,8 +131,9 @@ void fspann_ctx_destroy(fspann_ctx* ctx);
  * second copy in HBM, one working set in the caches — and owns its HIP stream and work areas: the way to serve one index from
  * several threads / streams (a context is not re-entrant; the reference shares one PartitionedIndexService between its
  * query threads the same way, PIS:68-73).  src must be finalized.  While clones are alive the shared state is read-only
- * (the mutating entry points return FSPANN_E_STATE on the owner and on the clones); destroying the owner first is allowed,
- * its arrays are released with the last clone.                                                                            */
+ * (the mutating entry points return FSPANN_E_STATE on the owner and on the clones); destroying the owner first is allowed:
+ * its own stream and work areas go at once, the shared arrays are released with the last clone, and from then on the
+ * clones take no new clone (FSPANN_E_STATE).  A clone of a clone starts on the store its source refers to.                */
 int fspann_ctx_clone(fspann_ctx* src, fspann_ctx** out);
 const char* fspann_last_error(void);
 const char* fspann_version(void);

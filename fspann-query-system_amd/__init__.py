@@ -9,4 +9,4 @@ reference's Java operator surface), dist.py (query sharding + RCCL top-k merge).
 from . import _native  # noqa: F401
 from ._native import (FspannArgumentError, FspannDeviceError, FspannError, FspannNullError,  # noqa: F401
                       FspannRangeError, FspannStateError, build)
-from .engine import FspannContext, PaperRuntimeConfig, bfloat16, float8_e4m3fn  # noqa: F401
+from .engine import FspannContext, PaperRuntimeConfig, bfloat16, coverage_grid, float8_e4m3fn  # noqa: F401

@@ -1,6 +1,6 @@
 """ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
 include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h, include/fspann_narrow.h,
-include/fspann_route_recall.h).
+include/fspann_route_recall.h, include/fspann_route_coverage.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -88,7 +88,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h", "fspann_route_coverage.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -272,6 +272,13 @@ _SIGS_ROUTE_RECALL = {
     "fspann_recall_ceiling_dev": (_i, [_vp, _i64, _vp, _i64, C.POINTER(_i32), _i, _i64p, _i, _vp, _vp]),
 }
 
+# include/fspann_route_coverage.h: where Route reaches the ground truth, per table, and the ceiling of every (tables, divisions,
+# probes) below the index's own (a table of its own: those above stay as they are)
+_SIGS_COVERAGE = {
+    "fspann_gt_reach_dev": (_i, [_vp, _i64, _vp, _i, _vp, _i64, _i, _vp]),
+    "fspann_route_coverage_dev": (_i, [_vp, _i64, _vp, _i, _i, C.POINTER(_i32), _i, C.POINTER(_i32), _i, _vp, _vp, _vp, _vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
@@ -282,7 +289,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()) + list(_SIGS_COVERAGE.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -334,3 +341,8 @@ def narrow_symbols():
 def route_recall_symbols():
     """the entry points of include/fspann_route_recall.h"""
     return sorted(_SIGS_ROUTE_RECALL)
+
+
+def coverage_symbols():
+    """the entry points of include/fspann_route_coverage.h"""
+    return sorted(_SIGS_COVERAGE)

@@ -25,6 +25,7 @@
 #include "route.hip.h"
 #include "route_lazy.hip.h"
 #include "route_recall.hip.h"
+#include "route_coverage.hip.h"
 #include "search_pick.hip.h"
 #include "tick.hip.h"
 #include "touch.hip.h"
@@ -50,3 +51,4 @@
 #include "api_sweep.hip.h"
 #include "api_narrow.hip.h"
 #include "api_route_recall.hip.h"
+#include "api_route_coverage.hip.h"

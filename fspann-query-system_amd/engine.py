@@ -200,6 +200,11 @@ def _typed_rows(vectors, dtype, what):
     return v, _row_dt(v), v.dtype
 
 
+def coverage_grid(tables, divisions, probes):
+    """every (tables, divisions, probes) of the three sequences, as route_coverage's grid [nc][3] (the last varies fastest)"""
+    return np.array([(t, d, p) for t in tables for d in divisions for p in probes], np.int32).reshape(-1, 3)
+
+
 class FspannContext:
     def __init__(self, cfg: PaperRuntimeConfig, device: int = 0):
         self.cfg = cfg
@@ -1224,6 +1229,72 @@ class FspannContext:
         out["true_nn_rank"] = out["rank"][:, 0].copy()
         out["true_nn_seen"] = out["true_nn_rank"] >= 0
         return out
+
+    # -- Route coverage map (include/fspann_route_coverage.h) -----------------------------------
+    def gt_reach_dev(self, nq, codes_ptr, probes_max, gt_ptr, gt_stride, kg, reach_ptr):
+        """reach [nq][kg][T*D]: per ground-truth id and table (step << 16) | hamming — the position of the id's partition in the order
+        Route polls that table's partitions for the query, and the partition's Hamming score — or -1 (the table does not offer the
+        id within probes_max probes; padding, an id >= n_ids or a deleted id: every table).  probes_max is literal, 1 .. 32.  One
+        launch, stream order."""
+        N.check(self.L.fspann_gt_reach_dev(self._h, nq, codes_ptr, probes_max, gt_ptr, gt_stride, kg, reach_ptr))
+
+    def route_coverage_dev(self, nq, reach_ptr, kg, reach_probes, ks, grid, hits_ptr, ceiling_ptr=0, score_ptr=0):
+        """hits / ceiling [nc][nk][nq] and score [nc][nq][kg] of the configurations grid [nc][3] = (tables, divisions, probes) from the
+        records of gt_reach_dev at probes_max = reach_probes.  ks (at most 64) and grid (at most 64 rows) are host sequences.
+        Returns exact [nc] (bool): the configuration cannot meet HARD_CAP, its answer is Route's own; elsewhere it is an upper bound."""
+        kk = [int(x) for x in ks]
+        karr = (C.c_int32 * max(1, len(kk)))(*kk)
+        gg = [int(x) for row in grid for x in row]
+        if len(gg) % 3:
+            raise N.FspannArgumentError("grid must be [nc][3] = (tables, divisions, probes)")
+        nc = len(gg) // 3
+        garr = (C.c_int32 * max(3, len(gg)))(*gg)
+        exact = (C.c_uint8 * max(1, nc))()
+        N.check(self.L.fspann_route_coverage_dev(self._h, nq, reach_ptr, kg, reach_probes, karr, len(kk), garr, nc, hits_ptr, ceiling_ptr or None,
+                                                 score_ptr or None, exact))
+        return np.frombuffer(exact, np.uint8, nc).astype(bool)
+
+    def route_coverage(self, q, k_variants, grid, gt_ids=None, probes_max=None):
+        """How many tables, divisions and probes Route needs before it offers the true neighbours, for every configuration of grid
+        [nc][3] = (tables <= T, divisions <= D, probes) at once, from this index and one pass: the probe order of a table does not
+        depend on the probe count, and the index a Setup at (T', D') builds is the sub-grid of tables t < T', d < D' of this one.  One
+        encode, the ground truth over the store at K = max(k_variants) (groundtruth_store_dev) unless gt_ids [nq][>= K] is given,
+        gt_reach_dev at probes_max (default: the largest probes of grid) and route_coverage_dev in groups of 64 configurations.  No
+        candidate row is read, nothing is set up or routed.
+        Returns dict(gt_ids [nq][K]; step, hamming [nq][K][T][D] (-1: not reached within probes_max); hits int32, ceiling float64
+        [nc][nk][nq]; score [nc][nq][K] (the Hamming score Route ranks the id with, -1: not offered); exact [nc] bool — where False,
+        HARD_CAP may stop Route early: offered is a superset and ceiling an upper bound; grid [nc][3])."""
+        ks, qq, g = self._attribution_args("route_coverage", q, k_variants, gt_ids)
+        if not np.isfinite(qq).all():
+            raise N.FspannArgumentError("Vector contains NaN/Inf")      # (what encode() says: Coding.java:360)
+        gr = np.asarray(grid, np.int64).reshape(-1, 3)
+        if not len(gr):
+            raise N.FspannArgumentError("grid is empty")
+        P = int(gr[:, 2].max()) if probes_max is None else int(probes_max)
+        K, nk, nc, nq = max(ks), len(ks), len(gr), qq.shape[0]
+        T, D = self.cfg.tables, self.cfg.divisions
+        with self._Dev(self) as dv:
+            qd = dv.up(qq)
+            if g is None:
+                gd, gs = dv.new((nq, K), np.int32), K
+                self.groundtruth_store_dev(nq, qd, K, gd)
+            else:
+                gd, gs = dv.up(g), g.shape[1]
+            codes = dv.new((nq, self.TD, self.W), np.uint64)
+            self.encode_dev(nq, qd, N.F32, codes)
+            reach = dv.new((nq, K, self.TD), np.int32)
+            self.gt_reach_dev(nq, codes, P, gd, gs, K, reach)
+            hits, ceil, score, exact = [], [], [], []
+            for c0 in range(0, nc, 64):
+                part = gr[c0:c0 + 64]
+                h, ce, sc = dv.new((len(part), nk, nq), np.int32), dv.new((len(part), nk, nq), np.float64), dv.new((len(part), nq, K), np.int32)
+                exact.append(self.route_coverage_dev(nq, reach, K, P, ks, part, h, ce, sc))
+                hits.append(dv.down(h)), ceil.append(dv.down(ce)), score.append(dv.down(sc))
+            rec = dv.down(reach).reshape(nq, K, T, D)
+            gt = dv.down(gd)[:, :K].copy()
+        return dict(gt_ids=gt, step=np.where(rec >= 0, rec >> 16, -1).astype(np.int32), hamming=np.where(rec >= 0, rec & 0xFFFF, -1).astype(np.int32),
+                    hits=np.concatenate(hits), ceiling=np.concatenate(ceil), score=np.concatenate(score), exact=np.concatenate(exact),
+                    grid=gr.astype(np.int32))
 
     def _last_probes(self, probe_override, retried, fellback):
         """The probes of each query's last pass in run_queries (the rule of fspann_eval.h for whose rows a query keeps): 10 if it

@@ -1,7 +1,6 @@
 // api_eval.hip.h — ForwardSecureANNSystem.runQueries' loop (FSA:622-748) over a resident store, include/fspann_eval.h:
-//   * fspann_eval_kvariants_dev: computeMetricsAtK for every k of kVariants from one result list (eval_sweep.hip.h);
-//   * fspann_search_fallback_dev / _finish_dev: QSI.search, then the empty-result fallback (FSA:667-678): the empty queries are
-//     searched again, a whole QSI.search with its adaptive retry, at max(2 base, 4) probes, in list mode, in place.
+// fspann_search_fallback_dev / _finish_dev: QSI.search, then the empty-result fallback (FSA:667-678): the empty queries are
+// searched again, a whole QSI.search with its adaptive retry, at max(2 base, 4) probes, in list mode, in place.
 // Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
 #include "../../include/fspann_eval.h"
@@ -45,51 +44,6 @@ int search_list_dev(fspann_ctx* c, const SearchBufs& s, int probes, const int32_
 }  // namespace
 
 extern "C" {
-
-int fspann_eval_kvariants_dev(fspann_ctx* c, int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev, int q_dtype, int dim,
-                              const int32_t* ks, int nk, const int32_t* ann_ids_dev, int64_t ann_stride, const int32_t* ann_count_dev,
-                              const int32_t* gt_ids_dev, int64_t gt_stride, const int32_t* unique_dev, double* recall_dev, double* ratio_dev,
-                              double* cand_ratio_dev) {
-    CHECK_CTX(c);
-    if (!ks) return fail(FSPANN_E_NULL, "ks is null");
-    if (nk < 1 || nk > kEvalMaxK) return fail(FSPANN_E_ARG, "nk must be in [1, %d]: %d", kEvalMaxK, nk);
-    EvalKs kv{};
-    int kmax = 0;
-    for (int j = 0; j < nk; j++) {
-        if (ks[j] <= 0 || ks[j] > kGtMaxK) return fail(FSPANN_E_ARG, "ks[%d] = %d: k must be in [1, %d]", j, ks[j], kGtMaxK);
-        kv.k[j] = ks[j];
-        kmax = std::max(kmax, ks[j]);
-    }
-    if ((unique_dev == nullptr) != (cand_ratio_dev == nullptr))
-        return fail(FSPANN_E_ARG, "unique_dev and cand_ratio_dev go together: both or neither");
-    // buffers, dtype pair (refused by name), n, dim and the strides: fspann_eval_metrics_typed_dev's checks at k = max(ks), no launch
-    if (int rc = fspann_eval_metrics_typed_dev(c, n, base_dev, base_dtype, 0, q_dev, q_dtype, dim, kmax, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev,
-                                               gt_stride, recall_dev, ratio_dev)) return rc;
-    if (nq < 0 || nq > INT32_MAX) return fail(FSPANN_E_ARG, "nq < 0 or nq > INT32_MAX");
-    if (nq == 0) return FSPANN_OK;
-    const size_t lds = eval_lds_bytes(dim, kmax);      // at most 32 KB of query + 24 KB at kmax = 1024
-    const bool same_bytes = q_dtype == base_dtype && base_dtype != FSPANN_F32;
-    with_row_type(base_dtype, [&](auto tb) {
-        using TB = typename decltype(tb)::type;
-        auto go = [&](auto tq) {
-            using TQ = typename decltype(tq)::type;
-            // 16 bytes at a time when every row starts on a 16-byte boundary and is whole pieces (and the query is in LDS)
-            const bool vec = (static_cast<int64_t>(dim) * static_cast<int64_t>(sizeof(TB))) % 16 == 0 && (reinterpret_cast<uintptr_t>(base_dev) & 15) == 0 &&
-                             dim <= kEvalQLdsMax;
-            auto launch = [&](auto kernel) {
-                hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(nq)), dim3(kEvalThreads), lds, c->stream, static_cast<const TB*>(base_dev), n,
-                                   static_cast<const TQ*>(q_dev), dim, nq, kv, nk, kmax, ann_ids_dev, ann_stride, ann_count_dev, gt_ids_dev, gt_stride, unique_dev,
-                                   recall_dev, ratio_dev, cand_ratio_dev);
-            };
-            if (vec) launch(eval_kvariants_kernel<TB, TQ, true>);
-            else launch(eval_kvariants_kernel<TB, TQ, false>);
-        };
-        if constexpr (DtypeOf<TB>::finite) { if (same_bytes) go(tb); else go(DtypeTag<float>{}); }
-        else if constexpr (DtypeOf<TB>::id != FSPANN_F64) go(DtypeTag<float>{});
-    });
-    FSP_HIP(hipGetLastError());
-    return FSPANN_OK;
-}
 
 int fspann_search_fallback_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int q_dtype, int probe_override, int64_t B, int k,
                                int32_t* out_ids_dev, double* out_dist_dev, int32_t* out_count_dev, int32_t* scored_dev,

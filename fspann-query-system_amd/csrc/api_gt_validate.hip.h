@@ -25,6 +25,7 @@ size_t nn1_scratch_bytes(const fspann_ctx* c, int64_t n, int dim, int64_t nsel) 
     return (static_cast<size_t>(nn1_chunk(c, n, dim, nsel)) * nn1_query_bytes(n, dim) + 255) & ~size_t(255);
 }
 
+constexpr const char* kNn1NoF64Store = "no exact top-1 over an FSPANN_F64 store: the reference's validator reads floats or bytes";      // (the two store calls)
 // The arguments both exact top-1 calls and both validate calls share (every refusal, in one place)
 int nn1_check(int64_t n, const void* base_dev, int base_dtype, int64_t nq, const void* q_dev, int q_dtype, int dim) {
     if (!base_dev || !q_dev) return fail(FSPANN_E_NULL, "exact top-1 buffer is null");
@@ -50,8 +51,7 @@ int nn1_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const void* q,
     double* qd = reinterpret_cast<double*>(w);
     unsigned long long* pkey = reinterpret_cast<unsigned long long*>(w + static_cast<size_t>(chunk) * dim * 8);
     int32_t* pidx = reinterpret_cast<int32_t*>(w + static_cast<size_t>(chunk) * dim * 8 + static_cast<size_t>(chunk) * gx * 8);
-    // a lane reads its row 16 bytes at a time when every row starts on a 16-byte boundary and ends on one
-    const bool vec = (static_cast<int64_t>(dim) * static_cast<int64_t>(sizeof(TB))) % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 15) == 0;
+    const bool vec = rows_vec16<TB>(base, dim);
     for (int64_t s = 0; s < nsel; s += chunk) {
         const int64_t cq = std::min(chunk, nsel - s);
         const dim3 wgrid(static_cast<unsigned>(std::min<int64_t>((cq * dim + 255) / 256, 1024)));
@@ -177,9 +177,9 @@ int fspann_nn1_exact_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, int
                                double* out_d2_dev) {
     return guarded([&]() -> int {
         CHECK_CTX(c);
-        if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
-        if (c->store->dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no exact top-1 over an FSPANN_F64 store: the reference's validator reads floats or bytes");
-        return nn1_exact(c, c->store->n, c->store->rows, c->store->dtype, nq, q_dev, q_dtype, c->cfg.dim, qsel_dev, nsel, out_idx_dev, out_d2_dev);
+        return with_store_rows(c, kNn1NoF64Store, [&](int64_t n, const void* rows, int dtype, int dim) {
+            return nn1_exact(c, n, rows, dtype, nq, q_dev, q_dtype, dim, qsel_dev, nsel, out_idx_dev, out_d2_dev);
+        });
     });
 }
 
@@ -195,9 +195,9 @@ int fspann_gt_validate_store_dev(fspann_ctx* c, int64_t nq, const void* q_dev, i
                                  int64_t sample_size, double tolerance, fspann_gt_validation* out) {
     return guarded([&]() -> int {
         CHECK_CTX(c);
-        if (!c->store->rows) return fail(FSPANN_E_STATE, "plaintext store not set");
-        if (c->store->dtype == FSPANN_F64) return fail(FSPANN_E_ARG, "no exact top-1 over an FSPANN_F64 store: the reference's validator reads floats or bytes");
-        return gt_validate(c, c->store->n, c->store->rows, c->store->dtype, nq, q_dev, q_dtype, c->cfg.dim, gt_ids_dev, gt_rows, gt_stride, sample_size, tolerance, out);
+        return with_store_rows(c, kNn1NoF64Store, [&](int64_t n, const void* rows, int dtype, int dim) {
+            return gt_validate(c, n, rows, dtype, nq, q_dev, q_dtype, dim, gt_ids_dev, gt_rows, gt_stride, sample_size, tolerance, out);
+        });
     });
 }
 

@@ -42,6 +42,7 @@
 #include "api_refine.hip.h"
 #include "api_tick.hip.h"
 #include "api_hostpipe.hip.h"
+#include "api_groundtruth.hip.h"
 #include "api_misc.hip.h"
 #include "api_build.hip.h"
 #include "api_ext.hip.h"

@@ -4,8 +4,51 @@
 
 namespace {
 
+// Slices of the split-k MFMA encode for a batch of nq rows (1: the unsplit 32 x 128 tile).  FSPANN_ENCODE_SPLITK forces a count; the
+// rule otherwise, settled by measurement (tools/encode_bench.py with SPLITK=..., profiles/notes/encode_splitk.txt): split only while
+// the slices together stay at or below one block per two CUs, at most four ways, and no slice shorter than four k tiles.  A slice's
+// publish / arrive / join is NOT small: per added slice a 256-block grid pays ~40 us (1 024 x 1 024 x 768: 75 us unsplit, 115 / 138 /
+// 176 / 274 us at S = 2 / 3 / 4 / 8; 4 096 x 256 x 960: 91 unsplit, 129 / 152 / 185), so a grid that already has a block per CU is
+// never split; 512 x 256 x 960 (32 blocks): 75 us unsplit, 65.9 / 62.5 / 60.8 / 64.7 / 65.2 / 74.7 at S = 2 / 3 / 4 / 6 / 8 / 10.
+// Either way S <= ceil(d / 32), and S is then lowered to the number of slices that ceil(KT / S) tiles each actually fill, so no
+// slice is empty (KT = 4, S = 3: two slices of two tiles).
+inline int encode_splitk_slices(const fspann_ctx* c, int64_t nq) {
+    const int KT = (c->cfg.dim + kMfmaKT - 1) / kMfmaKT;
+    int S = c->knob_encode_splitk;
+    if (S <= 0) {
+        const int64_t blocks = ((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)) * ((c->P_total + mfma_tile_p(1) - 1) / mfma_tile_p(1));
+        S = static_cast<int>(std::min<int64_t>(4, static_cast<int64_t>(c->num_cus) / (2 * blocks)));
+        S = std::min(S, KT / 4);
+    }
+    S = std::max(1, std::min(S, KT));
+    const int per = (KT + S - 1) / S;
+    return (KT + per - 1) / per;
+}
+
+// The split-k kernel in place of the small tile (S >= 2 slices).  Work area: one arrival counter per 32 x 128 tile (cleared on the
+// stream, like the code words), then [tiles][S] slots of one block's partial (16 KB of accumulators + 32 norms + 32 flags).
 template <typename TIn>
-int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_dev, int32_t* hashes_dev, int32_t* bad_dev) {
+int launch_encode_mfma_splitk(fspann_ctx* c, int64_t nq, const TIn* q_dev, int32_t* hashes_dev, unsigned long long* cw, int32_t* bad_dev,
+                              int64_t* list, int64_t cap, unsigned long long* cnt, int S) {
+    const int P = c->P_total, d = c->cfg.dim;
+    const int KT = (d + kMfmaKT - 1) / kMfmaKT, per = (KT + S - 1) / S;
+    const dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)), static_cast<unsigned>((P + mfma_tile_p(1) - 1) / mfma_tile_p(1)),
+                    static_cast<unsigned>(S));
+    const size_t tiles = static_cast<size_t>(grid.x) * grid.y;
+    const size_t ctr_bytes = (tiles * 4 + 255) / 256 * 256;
+    int rc = ensure(c, c->ws_splitk, ctr_bytes + tiles * S * kSplitSlotBytes);
+    if (rc) return rc;
+    unsigned* arrive = static_cast<unsigned*>(c->ws_splitk.p);
+    FSP_HIP(hipMemsetAsync(arrive, 0, tiles * 4, c->stream));
+    hipLaunchKernelGGL((encode_mfma_splitk_kernel<TIn>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P,
+                       c->cfg.m, c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max, per,
+                       static_cast<unsigned char*>(c->ws_splitk.p) + ctr_bytes, arrive);
+    return FSPANN_OK;
+}
+
+// splitk: slices of the dimension (encode_splitk_slices); 1 = the unsplit kernels
+template <typename TIn>
+int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_dev, int32_t* hashes_dev, int32_t* bad_dev, int splitk = 1) {
     const int P = c->P_total, d = c->cfg.dim;
     const int64_t cap = std::max<int64_t>(65536, nq * P / 16);
     int rc = ensure(c, c->ws_fix, 256 + static_cast<size_t>(cap) * 8);
@@ -19,7 +62,9 @@ int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* co
     // block tile: 64 x 256 for bulk coding (Setup: hundreds of thousands of rows per call); 32 x 128 with tiles in flight for batches
     // of up to a few thousand blocks of the large tile (8 192 x 1 024 x 768: 273 against 327 us; equal at 262 144 rows)
     const int64_t big_blocks = ((nq + 63) / 64) * ((P + 255) / 256);
-    if (big_blocks >= 16 * static_cast<int64_t>(c->num_cus) && c->knob_mfma_tile != 1) {
+    if (splitk > 1) {
+        if ((rc = launch_encode_mfma_splitk<TIn>(c, nq, q_dev, hashes_dev, cw, bad_dev, list, cap, cnt, splitk))) return rc;
+    } else if (big_blocks >= 16 * static_cast<int64_t>(c->num_cus) && c->knob_mfma_tile != 1) {
         dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(2) - 1) / mfma_tile_q(2)), static_cast<unsigned>((P + mfma_tile_p(2) - 1) / mfma_tile_p(2)));
         hipLaunchKernelGGL((encode_mfma_kernel<TIn, 2, 2>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P, c->cfg.m,
                            c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max);
@@ -47,10 +92,16 @@ int launch_encode(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_d
     // auto: the MFMA pre-filter pays from ~5e8 multiply-adds per call (its fixed part: clearing the code words, the exact re-check of the
     // pairs on a bucket edge, four launches).  tools/encode_bench.py, exact vs MFMA: 1 024 x 256 x 128 12 / 31 us, 512 x 256 x 960
     // 48 / 75, 1 024 x 1 024 x 768 132 / 77, 4 096 x 256 x 960 169 / 94, 8 192 x 1 024 x 768 758 / 273, 262 144 x 256 x 128 1 080 / 502.
-    const bool want_mfma = (c->encode_mode == 2) ||
+    // With the split-k kernel (mode 3, exact / MFMA / split-k under its rule, medians of three rounds): 512 x 256 x 960 48 / 75 / 61
+    // (S = 4), 1 024 x 1 024 x 768 130 / 75 / 75 (not split), 4 096 x 256 x 960 162 / 91 / 91 (not split).  The split beats the
+    // unsplit MFMA path only where the exact kernel beats both, so auto never takes it: mode 3 is opt-in.
+    const bool want_mfma = (c->encode_mode == 2) || (c->encode_mode == 3) ||
                            (c->encode_mode == 0 && static_cast<double>(nq) * c->P_total * c->cfg.dim >= 5.0e8);
     if (want_mfma && !proj_dev && c->fam->d_alphaT32.get() && c->W <= 3) {      // (the fused bit-pack epilogue carries three code words: <= 192 bits)
-        int rc = launch_encode_mfma<TIn>(c, nq, q_dev, codes_dev, hashes_dev, bad_dev);
+        // mode 3: the dimension split over workgroups where encode_splitk_slices asks for it — query batches only, never Setup's coding
+        // (a build in progress: hundreds of thousands of rows per call fill the chip unsplit)
+        const int splitk = (c->encode_mode == 3 && c->bld_done < 0) ? encode_splitk_slices(c, nq) : 1;
+        int rc = launch_encode_mfma<TIn>(c, nq, q_dev, codes_dev, hashes_dev, bad_dev, splitk);
         if (rc <= 0) return rc;  // error
         // the list can only overflow when almost every pair sits on a bucket boundary (degenerate omega): the
         // exact kernel below is enqueued with a device-side guard and returns immediately otherwise.
@@ -145,11 +196,13 @@ int fspann_encode(fspann_ctx* c, int64_t nq, const void* q, int dtype, uint64_t*
     });
 }
 
-// Encode path selection: 0 = auto (MFMA pre-filter for nq >= 4096, exact fp64 otherwise), 1 = exact fp64 VALU only,
-// 2 = always MFMA fp32 GEMM + exact re-check.  All modes produce bit-identical hashes and codes.
+// Encode path selection: 0 = auto (MFMA pre-filter from 5e8 multiply-adds per call — rows x projections x dim —, exact fp64 below),
+// 1 = exact fp64 VALU only, 2 = always MFMA fp32 GEMM + exact re-check, 3 = as 2 with the dimension split over workgroups for batches
+// that leave CUs idle (encode_mfma_splitk_kernel; where the MFMA path is not eligible it falls back like 2).  All modes produce
+// bit-identical hashes and codes.
 int fspann_set_encode_mode(fspann_ctx* c, int mode) {
     if (!c) return fail(FSPANN_E_NULL, "ctx is null");
-    if (mode < 0 || mode > 2) return fail(FSPANN_E_ARG, "encode mode must be 0, 1 or 2");
+    if (mode < 0 || mode > 3) return fail(FSPANN_E_ARG, "encode mode must be 0, 1, 2 or 3");
     c->encode_mode = mode;
     return FSPANN_OK;
 }

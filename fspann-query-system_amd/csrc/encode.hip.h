@@ -595,6 +595,246 @@ __global__ __launch_bounds__(256) void encode_fix_kernel(const TIn* __restrict__
 }
 
 // =====================================================================================
+// Split-k MFMA encode: the 32 x 128 tile of encode_mfma_kernel<TIn, 1, 1> with the DIMENSION divided over gridDim.z workgroups.
+// A query batch at d = 768 / 960 gives the small tile a few dozen to a few hundred blocks, each one dependent chain of d / 2 MFMAs per
+// wave behind d / 32 tile loads; S slices give S times the blocks and chains a S-th as long.  Grid (ceil(nq / 32), ceil(P / 128), S);
+// slice z owns the k tiles [z tiles_per_slice, (z + 1) tiles_per_slice) and walks them with the small tile's loop (three register
+// sets in rotation, unconditional clamped loads, zeroing at the LDS write — against the SLICE's end, the elements behind it belong to
+// the next slice —, lds_barrier).
+//
+// Reduction, one launch, deterministic, no floating-point atomics: a block stores its partial into the workspace slot [tile][z] —
+// the 32 x 32 accumulators in register order, word (reg * 4 + wave) * 64 + lane, so one wave's store of one register is 256
+// contiguous bytes; then its 32 partial squared row norms (fp64) and its 32 non-finite flags — and adds 1 to the tile's arrival
+// counter.  The block that reads S - 1 there is the last: it sums ALL S slots, its own included, in the order z = 0 .. S - 1 (fp32
+// for the accumulators, fp64 for the norms, OR for the flags: the same result whichever block arrives last) and runs the epilogue of
+// encode_mfma_kernel; the others exit.  Nobody waits for anybody: no spin, any residency.
+// Memory order: every thread's stores -> release fence at agent scope (the writes leave this CU and its XCD's L2) -> workgroup barrier
+// -> thread 0's acq_rel agent-scope atomic add -> its old value through ONE LDS word behind ONE barrier (workgroup-uniform, outside
+// any loop) -> acquire fence at agent scope -> the reads.  The reads of the slots are relaxed agent-scope ATOMIC loads: on gfx950 they
+// are global_load ... sc1, which are never served from this CU's vector L1 and are coherent across the XCDs' L2s, so a line of the
+// workspace that an earlier call left in the L1 cannot be returned even were the acquire's invalidate to be moved by the compiler;
+// behind the acquire fence they observe everything the S - 1 release sequences on the counter published.
+//
+// Error bound: a slice is one chain of at most 32 tiles_per_slice fused multiply-adds, the slices are joined by S - 1 fp32 additions:
+// a summation tree over the same d products.  The bound of a sum holds for any order of its additions with the DEPTH of the tree in
+// place of the chain's length (Higham, Accuracy and Stability of Numerical Algorithms, §4.2), and no product passes through more than
+// 32 tiles_per_slice + S - 1 additions.  With KT = ceil(d / 32) tiles, 2 <= S <= KT and tiles_per_slice = ceil(KT / S) <= KT - S + 1
+// that is <= 32 (KT - 1) + 63 - 31 S <= 32 (KT - 1) + 1 <= d: never deeper than the single chain.  So (d + 4) 2^-24 ||v||_2
+// alpha_norm_max, inflated by 1.01, plus the underflow floor — mfma_row_band as it is — covers it; it is evaluated on the TOTAL norm
+// of the row (a slice's own norm would give a band too narrow for the other slices' share of the error).
+// The fp32 additions of the join are written as v_add_f32 (add_f32_single): one IEEE addition per lane and instruction, never paired
+// into packed fp32 operations by the compiler.
+// =====================================================================================
+__device__ __forceinline__ float add_f32_single(const float a, const float b) {
+    float o;
+    asm("v_add_f32 %0, %1, %2" : "=v"(o) : "v"(a), "v"(b));
+    return o;
+}
+constexpr int kSplitAccWords = 16 * 256;                                                      // one block's accumulators: 16 KB
+constexpr size_t kSplitSlotBytes = static_cast<size_t>(kSplitAccWords) * 4 + 32 * 8 + 32 * 4;  // + partial norms + non-finite flags
+
+template <typename TIn>
+__global__ __launch_bounds__(256, 2) void encode_mfma_splitk_kernel(
+    const TIn* __restrict__ q, int64_t nq, int d, const float* __restrict__ alphaT32 /*[d][P]*/,
+    const double* __restrict__ r, const double* __restrict__ omega, int P, int m, int lambda, int W, int TD, int32_t* __restrict__ hashes,
+    unsigned long long* __restrict__ codes, int32_t* __restrict__ bad, int64_t* __restrict__ fix_list, int64_t fix_cap,
+    unsigned long long* __restrict__ fix_count, double alpha_norm_max, int tiles_per_slice,
+    unsigned char* slots /*[tiles][S] of kSplitSlotBytes*/, unsigned* arrive /*[tiles], zero at launch*/) {
+    constexpr int kTileQ = mfma_tile_q(1), kTileP = mfma_tile_p(1);
+    __shared__ float Vs[kTileQ][kMfmaKT + 1];
+    __shared__ __align__(16) float As[kMfmaKT][kTileP];
+    __shared__ double rnorm2[kTileQ];
+    __shared__ int badrow[kTileQ];
+    __shared__ unsigned arrived;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kTileQ;
+    const int p0 = blockIdx.y * kTileP;
+    const int S = static_cast<int>(gridDim.z), z = static_cast<int>(blockIdx.z);
+    const int k_lo = min(d, z * tiles_per_slice * kMfmaKT), k_hi = min(d, k_lo + tiles_per_slice * kMfmaKT);   // this slice's dimensions
+    if (tid < kTileQ) { rnorm2[tid] = 0.0; badrow[tid] = 0; }
+    fsp_acc16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = 0.0f;
+    constexpr int kVRows = kTileQ / 8;                   // V rows per thread (thread t: column t & 31 of rows (t >> 5) + 8 i)
+    constexpr int kAVecs = kMfmaKT * kTileP / 4 / 256;   // 16-byte pieces of the A tile per thread
+    double nrm[kVRows];
+#pragma unroll
+    for (int i = 0; i < kVRows; i++) nrm[i] = 0.0;
+    __syncthreads();
+    const bool a_vec = ((P & 3) == 0);
+
+    constexpr int kSets = 3;
+    double vreg[kSets][kVRows];
+    fsp_f4 areg[kSets][kAVecs];
+    auto fetch = [&](auto set_c, const int k0) {
+        constexpr int st = decltype(set_c)::value;
+#pragma unroll
+        for (int i = 0; i < kVRows; i++) {
+            const int row = (tid >> 5) + 8 * i, col = tid & 31;
+            vreg[st][i] = static_cast<double>(q[min(q0 + row, nq - 1) * d + min(k0 + col, d - 1)]);
+        }
+#pragma unroll
+        for (int i = 0; i < kAVecs; i++) {
+            const int e = (tid + i * 256) * 4;
+            const int kk = e / kTileP, pc = e % kTileP;
+            if (a_vec) {                           // uniform: P % 4 == 0, so a 16-byte piece lies wholly inside or wholly outside P
+                areg[st][i] = *reinterpret_cast<const fsp_f4*>(alphaT32 + static_cast<int64_t>(min(k0 + kk, d - 1)) * P + min(p0 + pc, P - 4));
+            } else {
+                fsp_f4 a = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (k0 + kk < k_hi) {
+                    const float* src = alphaT32 + static_cast<int64_t>(k0 + kk) * P + p0 + pc;
+#pragma unroll
+                    for (int u = 0; u < 4; u++) if (p0 + pc + u < P) a[u] = src[u];
+                }
+                areg[st][i] = a;
+            }
+        }
+    };
+    auto tile_from = [&](auto set_c, const int k0) {
+        constexpr int st = decltype(set_c)::value;
+#pragma unroll
+        for (int i = 0; i < kVRows; i++) {
+            const int row = (tid >> 5) + 8 * i, col = tid & 31;
+            const double v = (q0 + row < nq && k0 + col < k_hi) ? vreg[st][i] : 0.0;
+            if (!(fabs(v) <= 1.79769313486231570815e+308)) badrow[row] = 1;
+            Vs[row][col] = static_cast<float>(v);
+            nrm[i] += v * v;
+        }
+#pragma unroll
+        for (int i = 0; i < kAVecs; i++) {
+            const int e = (tid + i * 256) * 4;
+            const int kk = e / kTileP, pc = e % kTileP;
+            const fsp_f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+            *reinterpret_cast<fsp_f4*>(&As[kk][pc]) = (!a_vec || (k0 + kk < k_hi && p0 + pc < P)) ? areg[st][i] : zero;
+        }
+        lds_barrier();
+        if (k0 + kSets * kMfmaKT < k_hi) fetch(set_c, k0 + kSets * kMfmaKT);      // uniform: the set just emptied takes the tile kSets ahead
+#pragma unroll
+        for (int kk = 0; kk < kMfmaKT; kk += 2) {
+            const float av = Vs[lane & 31][kk + (lane >> 5)];
+            const float bv = As[kk + (lane >> 5)][wave * 32 + (lane & 31)];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+        }
+        lds_barrier();
+    };
+    using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>; using S2 = std::integral_constant<int, 2>;
+    fetch(S0{}, k_lo);                                                              // (an empty slice: clamped addresses, no trip)
+    if (k_lo + kMfmaKT < k_hi) fetch(S1{}, k_lo + kMfmaKT);
+    if (k_lo + 2 * kMfmaKT < k_hi) fetch(S2{}, k_lo + 2 * kMfmaKT);
+    for (int k0 = k_lo; k0 < k_hi; k0 += kSets * kMfmaKT) {                         // uniform trips
+        tile_from(S0{}, k0);
+        if (k0 + kMfmaKT < k_hi) tile_from(S1{}, k0 + kMfmaKT);
+        if (k0 + 2 * kMfmaKT < k_hi) tile_from(S2{}, k0 + 2 * kMfmaKT);
+    }
+    // the slice's part of the row norms: reduce the 32 lanes that share a row, one writer per row
+#pragma unroll
+    for (int i = 0; i < kVRows; i++) {
+        double s = nrm[i];
+        for (int off = 16; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        if ((tid & 31) == 0) rnorm2[(tid >> 5) + 8 * i] = s;
+    }
+    __syncthreads();
+
+    // publish this slice's partial, arrive
+    const int64_t tile = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
+    unsigned char* const tile_slots = slots + static_cast<size_t>(tile) * S * kSplitSlotBytes;
+    {
+        unsigned char* const mine = tile_slots + static_cast<size_t>(z) * kSplitSlotBytes;
+        float* part = reinterpret_cast<float*>(mine) + wave * 64 + lane;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) part[reg * 256] = acc[reg];
+        if (tid < kTileQ) {
+            reinterpret_cast<double*>(mine + kSplitAccWords * 4)[tid] = rnorm2[tid];
+            reinterpret_cast<int*>(mine + kSplitAccWords * 4 + kTileQ * 8)[tid] = badrow[tid];
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (tid == 0) arrived = __hip_atomic_fetch_add(arrive + tile, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (arrived != static_cast<unsigned>(S - 1)) return;              // workgroup-uniform: not the last slice of this tile to arrive
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+
+    // join: every slot in the order z = 0 .. S - 1 (a slot's 16 loads requested together)
+    for (int zz = 0; zz < S; zz++) {
+        const unsigned* src = reinterpret_cast<const unsigned*>(tile_slots + static_cast<size_t>(zz) * kSplitSlotBytes) + wave * 64 + lane;
+        float v[16];
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) v[reg] = __builtin_bit_cast(float, __hip_atomic_load(src + reg * 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) acc[reg] = (zz == 0) ? v[reg] : add_f32_single(acc[reg], v[reg]);
+    }
+    if (tid < kTileQ) {
+        double s = 0.0;
+        int flag = 0;
+        for (int zz = 0; zz < S; zz++) {
+            const unsigned char* slot = tile_slots + static_cast<size_t>(zz) * kSplitSlotBytes + kSplitAccWords * 4;
+            s = s + __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(slot) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            flag |= __hip_atomic_load(reinterpret_cast<const int*>(slot + kTileQ * 8) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        badrow[tid] = flag;
+        rnorm2[tid] = mfma_row_band(d, alpha_norm_max, s);             // per-row guard band (y units) of the WHOLE row's norm
+        if (bad && blockIdx.y == 0 && q0 + tid < nq) bad[q0 + tid] = flag;
+    }
+    __syncthreads();
+
+    // epilogue of encode_mfma_kernel (RT = CT = 1): quantise, interval test, bit-pack into the pre-zeroed code words, fix list
+    const int half = lane >> 5, c32 = lane & 31;
+    const int pb = p0 + wave * 32;                          // first projection of this wave's 32 columns (wave-uniform)
+    const int p = pb + c32;
+    const double rr = (p < P) ? r[p] : 0.0, ww = (p < P) ? omega[p] : 1.0;
+    const double iw = 1.0 / ww;
+    // the (t,d) tables whose projections fall into this tile: lane (half, seg) packs the bits of table td_first + seg for row-half `half`
+    const int td_first = pb / m;
+    const int td_last = min(P - 1, pb + 31) / m;
+    const int nseg = (pb < P) ? td_last - td_first + 1 : 0;
+    const int my_td = td_first + c32;
+    const bool seg_on = c32 < nseg;
+    const int c_lo = seg_on ? max(0, my_td * m - pb) : 0;
+    const int c_hi = seg_on ? min(min(31, P - 1 - pb), my_td * m + m - 1 - pb) : -1;
+    const int flen = c_hi - c_lo + 1;
+    const int j_lo = pb + c_lo - my_td * m;
+    const unsigned fmask = (flen >= 32) ? 0xFFFFFFFFu : ((1u << max(flen, 0)) - 1u);
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        const int64_t qi = q0 + row;
+        const bool live = (qi < nq) && (p < P);
+        const double y = static_cast<double>(acc[reg]);
+        double fl;
+        const bool inside = mfma_pair_safe(y, rnorm2[row], rr, ww, iw, &fl);
+        const bool safe = live && inside && !badrow[row];
+        const int32_t h = java_d2i(fl);
+        if (live && hashes) hashes[qi * P + p] = h;
+        if (live && !safe) {
+            const unsigned long long pos = atomicAdd(fix_count, 1ull);
+            if (pos < static_cast<unsigned long long>(fix_cap)) fix_list[pos] = qi * P + p;
+        }
+        // Coding.C: bit pos = (lambda-1-i)*m + j  <-  bit i of (h_j ^ 0x80000000); one ballot per plane, low half = the
+        // 32 columns of row `row` (half 0), high half = those of row + 4 (half 1)
+        const uint32_t hj = static_cast<uint32_t>(h) ^ 0x80000000u;
+        unsigned long long w0 = 0, w1 = 0, w2 = 0;
+        for (int i = 0; i < lambda; i++) {                            // uniform trip count: every lane takes part in the ballot
+            const unsigned long long bm = __ballot(safe && ((hj >> (i & 31)) & 1u));
+            if (flen > 0) {
+                const unsigned long long field = (bm >> (half * 32 + c_lo)) & fmask;
+                const int bp = (lambda - 1 - i) * m + j_lo;
+                const int wd = bp >> 6, off = bp & 63;
+                const unsigned long long lo = field << off;
+                const unsigned long long hi = (off + flen > 64) ? (field >> (64 - off)) : 0ull;
+                if (wd == 0) { w0 |= lo; w1 |= hi; } else if (wd == 1) { w1 |= lo; w2 |= hi; } else { w2 |= lo; }
+            }
+        }
+        if (flen > 0 && qi < nq) {
+            unsigned long long* cw = codes + (qi * TD + my_td) * W;
+            if (w0) atomicOr(cw, w0);
+            if (W > 1 && w1) atomicOr(cw + 1, w1);
+            if (W > 2 && w2) atomicOr(cw + 2, w2);
+        }
+    }
+}
+
+// =====================================================================================
 // The MFMA encode as ONE workgroup role (front_kernel's encode role, tick.hip.h): kFrontEncQ query rows x ALL P projections.
 // Owning whole tables it writes whole code words — no clearing launch, no atomicOr, no fix list, no fix launch — and it
 // re-checks its own undecided pairs.  Inside the front launch the role's latency hides behind the Route workgroups beside it;

@@ -251,7 +251,8 @@ struct fspann_ctx {
     bool knob_shape_spec = true;     // FSPANN_ROUTE_SHAPE_SPEC=0: the bounded select's build with run-time tables x probes also for 16 x 5 (dev A/B)
     int knob_mfma_tile = 0;          // FSPANN_ENCODE_MFMA_TILE=1: the 32 x 128 block tile of the MFMA encode for every batch size (dev A/B)
     int knob_encode_qb = 0;          // FSPANN_ENCODE_QB: query rows per workgroup of the exact encode (0 = by batch size; dev A/B)
-    bool knob_zero_copy = true;      // FSPANN_ZERO_COPY=0: tiny host-pointer calls go through copy commands like larger ones (dev A/B)
+    int knob_encode_splitk = 0;      // FSPANN_ENCODE_SPLITK: slices of the split-k MFMA encode, encode mode 3 (0 = by batch size; dev A/B and tests)
+    bool knob_zero_copy = true;     // FSPANN_ZERO_COPY=0: tiny host-pointer calls go through copy commands like larger ones (dev A/B)
     int knob_route_lds_kb = 0;       // FSPANN_ROUTE_LDS_KB: LDS the full select may plan with (0 = all of it); less leaves room for scan workgroups beside it
     int knob_route_wgs = 0;          // FSPANN_ROUTE_WGS: workgroups per CU of the full select's grid (0 = what fits, at most 4)
     int knob_devflags = 0;           // FSPANN_ROUTE_DEVFLAGS: dev A/B switches of the full select (route.hip.h)
@@ -260,10 +261,11 @@ struct fspann_ctx {
     int last_tick_fused = 0;
     int last_front_encode_mfma = 0;  // the last fspann_tick_dev coded its batch with front_kernel's MFMA role (encode_mfma_block)
 
-    int encode_mode = 0;                       // 0 auto, 1 exact fp64, 2 MFMA fp32 + exact re-check
+    int encode_mode = 0;                       // 0 auto, 1 exact fp64, 2 MFMA fp32 + exact re-check, 3 = 2 with the dimension split over workgroups
     unsigned long long fix_cap_last = 0;       // capacity of the re-check list of the last MFMA-path call
     bool mfma_last = false;                    // the last encode took the MFMA path
     fspann::DevBuf ws_fix;                     // fix list + counter + int32 hashes of the MFMA path
+    fspann::DevBuf ws_splitk;                  // arrival counters + [tile][slice] partials of the split-k MFMA encode
     int route_mode = 0;              // 0 auto, 1 always route_select_kernel, 2 bounded select whenever its preconditions hold
     fspann::DevBuf ws_ovf;
     // kernel-attached HIP events of the refinement scan (fspann_refine_timing_begin / _end)

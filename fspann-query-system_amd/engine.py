@@ -389,7 +389,8 @@ class FspannContext:
         return (codes, hs) if want_hashes else codes
 
     def set_encode_mode(self, mode: int):
-        """0 auto, 1 exact fp64, 2 MFMA fp32 + exact re-check (all bit-identical)."""
+        """0 auto, 1 exact fp64, 2 MFMA fp32 + exact re-check, 3 as 2 with the dimension split over workgroups for
+        batches that leave CUs idle (all bit-identical)."""
         N.check(self.L.fspann_set_encode_mode(self._h, mode))
 
     def last_encode_rechecked(self) -> int:

@@ -1,6 +1,6 @@
 """ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
 include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h, include/fspann_narrow.h,
-include/fspann_route_recall.h, include/fspann_route_coverage.h).
+include/fspann_route_recall.h, include/fspann_route_coverage.h, include/fspann_groundtruth_mfma.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -88,7 +88,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h", "fspann_route_coverage.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h", "fspann_route_coverage.h", "fspann_groundtruth_mfma.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -280,6 +280,20 @@ _SIGS_COVERAGE = {
 }
 
 
+class GtMfmaStats(C.Structure):
+    """fspann_gt_mfma_stats of include/fspann_groundtruth_mfma.h"""
+    _fields_ = [("queries_fast", C.c_int64), ("queries_exact", C.c_int64), ("survivors_max", C.c_int64), ("survivors_total", C.c_int64),
+                ("whole_call_exact", C.c_int32), ("reserved", C.c_int32)]
+
+
+# include/fspann_groundtruth_mfma.h: the ground truth with the fp32 matrix-core pre-filter (a table of its own: those above stay as
+# they are)
+_SIGS_GT_MFMA = {
+    "fspann_groundtruth_mfma_dev": (_i, [_vp, _i64, _vp, _i, _i64, _vp, _i, _i, _vp, _vp, C.POINTER(GtMfmaStats)]),
+    "fspann_groundtruth_mfma_store_dev": (_i, [_vp, _i64, _vp, _i, _vp, _vp, C.POINTER(GtMfmaStats)]),
+}
+
+
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
     global _LIB
@@ -289,7 +303,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()) + list(_SIGS_COVERAGE.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()) + list(_SIGS_COVERAGE.items()) + list(_SIGS_GT_MFMA.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -346,3 +360,8 @@ def route_recall_symbols():
 def coverage_symbols():
     """the entry points of include/fspann_route_coverage.h"""
     return sorted(_SIGS_COVERAGE)
+
+
+def gt_mfma_symbols():
+    """the entry points of include/fspann_groundtruth_mfma.h"""
+    return sorted(_SIGS_GT_MFMA)

@@ -17,6 +17,7 @@
 #include "groundtruth.hip.h"
 #include "eval_sweep.hip.h"
 #include "groundtruth_u8.hip.h"
+#include "groundtruth_mfma.hip.h"
 #include "gt_validate.hip.h"
 #include "hostpipe.hip.h"
 #include "narrow.hip.h"
@@ -43,6 +44,7 @@
 #include "api_tick.hip.h"
 #include "api_hostpipe.hip.h"
 #include "api_groundtruth.hip.h"
+#include "api_groundtruth_mfma.hip.h"
 #include "api_misc.hip.h"
 #include "api_build.hip.h"
 #include "api_ext.hip.h"

@@ -164,6 +164,13 @@ def _row_dt(a):
     return _dt(a)
 
 
+def _gt_method(method):
+    """method= of the numpy-level ground-truth calls: True for "mfma", False for "exact", anything else refused"""
+    if method not in ("exact", "mfma"):
+        raise N.FspannArgumentError(f"method must be 'exact' or 'mfma': {method!r}")
+    return method == "mfma"
+
+
 def _typed_rows(vectors, dtype, what):
     """Rows as store_set takes them (its docstring says what each dtype= accepts; `what` names the caller in the messages): the
     contiguous array to hand over, its FSPANN_* code, and what store_dtype reports for it."""
@@ -785,18 +792,62 @@ class FspannContext:
         needs for recall against that store, with no fp32 copy of it."""
         N.check(self.L.fspann_groundtruth_store_dev(self._h, nq, q_ptr, k, out_ids_ptr, out_d2_ptr or None))
 
-    def groundtruth_rows(self, base, q, k, dtype=None):
+    last_gt_stats = None     # what the last method="mfma" ground truth did: fspann_gt_mfma_stats as a dict
+
+    def _gt_stats(self, st):
+        self.last_gt_stats = {name: int(getattr(st, name)) for name, _ in N.GtMfmaStats._fields_ if name != "reserved"}
+
+    def groundtruth_mfma_dev(self, n, base_ptr, base_dtype, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr=0):
+        """groundtruth_rows_dev by the fp32 matrix-core pre-filter with an exact finish (fspann_groundtruth_mfma_dev): the same
+        arguments and bit-identical results; synchronises the stream once.  Leaves last_gt_stats."""
+        st = N.GtMfmaStats()
+        N.check(self.L.fspann_groundtruth_mfma_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr or None, C.byref(st)))
+        self._gt_stats(st)
+
+    def groundtruth_mfma_store_dev(self, nq, q_ptr, k, out_ids_ptr, out_d2_ptr=0):
+        """groundtruth_mfma_dev with the resident store as the base (what groundtruth_store_dev is to groundtruth_rows_dev)."""
+        st = N.GtMfmaStats()
+        N.check(self.L.fspann_groundtruth_mfma_store_dev(self._h, nq, q_ptr, k, out_ids_ptr, out_d2_ptr or None, C.byref(st)))
+        self._gt_stats(st)
+
+    def groundtruth_store(self, q, k, method="exact"):
+        """Exact k-NN of host fp32 queries q [nq][dim] over the resident store: ids [nq][k] int32, squared distances [nq][k] float64.
+        method="mfma": the fp32 matrix-core pre-filter with an exact finish, the same arrays (last_gt_stats says what it did)."""
+        run = self.groundtruth_mfma_store_dev if _gt_method(method) else self.groundtruth_store_dev
+        qq = _c(q, np.float32)
+        if qq.ndim != 2 or qq.shape[1] != self.cfg.dim:
+            raise N.FspannArgumentError("q must be [nq][dim] of the context's dim")
+        nq = qq.shape[0]
+        ids, d2 = np.empty((nq, k), np.int32), np.empty((nq, k), np.float64)
+        ptrs = []
+        try:
+            for nbytes in (qq.nbytes, ids.nbytes, d2.nbytes):
+                p = C.c_void_p()
+                N.check(self.L.fspann_dev_alloc(self._h, nbytes, C.byref(p)))
+                ptrs.append(p)
+            qd, idd, d2d = ptrs
+            N.check(self.L.fspann_h2d(self._h, qd, _p(qq), qq.nbytes))
+            run(nq, qd, k, idd, d2d)
+            N.check(self.L.fspann_d2h(self._h, _p(ids), idd, ids.nbytes))
+            N.check(self.L.fspann_d2h(self._h, _p(d2), d2d, d2.nbytes))
+        finally:
+            for p in ptrs:
+                self.L.fspann_dev_free(self._h, p)
+        return ids, d2
+
+    def groundtruth_rows(self, base, q, k, dtype=None, method="exact"):
         """Exact k-NN of fp32 queries over host rows kept in their type on the device.  base [n][dim] and dtype= are what store_set
         takes (np.uint8 / np.int8 / np.float16 arrays or values, the bfloat16 / float8_e4m3fn markers with tensors, bit patterns or
         exact floats); without dtype= a uint8, int8 or float16 array keeps its own type (nothing here widens rows).  q [nq][dim] goes
         as fp32.  float64 rows are refused (the reference's ground truth reads floats: pass dtype=np.float32 to have them cast).
         Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n), what groundtruth() returns
-        for the same values held as float32."""
+        for the same values held as float32.  method="mfma": the fp32 matrix-core pre-filter with an exact finish
+        (groundtruth_mfma_dev), the same arrays; last_gt_stats says what it did."""
+        run = self.groundtruth_mfma_dev if _gt_method(method) else self.groundtruth_rows_dev
         if dtype is None and getattr(base, "dtype", None) in (np.uint8, np.int8, np.float16):
             dtype = base.dtype
         b, code, _ = _typed_rows(base, dtype, "groundtruth_rows")
-        return self._groundtruth_host(b, _c(q, np.float32), k,
-                                      lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_rows_dev(n, bd, code, nq, qd, dim, k, idd, d2d))
+        return self._groundtruth_host(b, _c(q, np.float32), k, lambda n, bd, nq, qd, dim, idd, d2d: run(n, bd, code, nq, qd, dim, k, idd, d2d))
 
     def gt_validator_sample(self, nq, sample_size=100) -> np.ndarray:
         """GroundtruthValidator's sample (java.util.Random(42).nextInt(nq) into a HashSet<Integer> until it holds
@@ -1349,15 +1400,21 @@ class FspannContext:
                 self.L.fspann_dev_free(self._h, p)
         return ids, d2
 
-    def groundtruth(self, base, q, k):
+    def groundtruth(self, base, q, k, method="exact"):
         """Exact k-NN of host arrays: uint8 arrays stay bytes on the device, int8 arrays signed bytes, anything else goes as fp32
         (base and q alike; bytes with anything but bytes of the same signedness do not match).
-        Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n)."""
+        Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n).  method="mfma": fp32 pairs
+        go through groundtruth_mfma_dev, the same arrays; a byte pair is refused (it runs on the int8 matrix cores as it is)."""
+        mfma = _gt_method(method)
         base, q = np.asarray(base), np.asarray(q)
         if (base.dtype == np.uint8) != (q.dtype == np.uint8) or (base.dtype == np.int8) != (q.dtype == np.int8):
             raise N.FspannArgumentError("Base and query types must match (both fvecs or both bvecs)")
         dt = base.dtype if base.dtype in (np.uint8, np.int8) else np.float32
         b, qq = _c(base, dt), _c(q, dt)
+        if mfma:
+            if dt != np.float32:
+                raise N.FspannArgumentError("method='mfma' takes fp32 pairs: a byte pair is exact on the int8 matrix cores already (method='exact')")
+            return self._groundtruth_host(b, qq, k, lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_mfma_dev(n, bd, N.F32, nq, qd, dim, k, idd, d2d))
         return self._groundtruth_host(b, qq, k, lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_typed_dev(n, bd, _row_dt(b), nq, qd, _row_dt(qq), dim, k,
                                                                                                         idd, d2d))
 

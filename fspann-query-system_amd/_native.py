@@ -1,6 +1,7 @@
 """ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
 include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h, include/fspann_narrow.h,
-include/fspann_route_recall.h, include/fspann_route_coverage.h, include/fspann_groundtruth_mfma.h).
+include/fspann_route_recall.h, include/fspann_route_coverage.h, include/fspann_groundtruth_mfma.h,
+include/fspann_encode_kwaves.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -88,7 +89,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h", "fspann_route_coverage.h", "fspann_groundtruth_mfma.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h", "fspann_route_coverage.h", "fspann_groundtruth_mfma.h", "fspann_encode_kwaves.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -293,6 +294,12 @@ _SIGS_GT_MFMA = {
     "fspann_groundtruth_mfma_store_dev": (_i, [_vp, _i64, _vp, _i, _vp, _vp, C.POINTER(GtMfmaStats)]),
 }
 
+# include/fspann_encode_kwaves.h: the k-wave variant of the MFMA encode (a table of its own: those above stay as they are)
+_SIGS_KWAVES = {
+    "fspann_set_encode_kwaves": (_i, [_vp, _i]),
+    "fspann_last_encode_kwaves": (_i, [_vp]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
@@ -303,7 +310,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()) + list(_SIGS_COVERAGE.items()) + list(_SIGS_GT_MFMA.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()) + list(_SIGS_COVERAGE.items()) + list(_SIGS_GT_MFMA.items()) + list(_SIGS_KWAVES.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -365,3 +372,8 @@ def coverage_symbols():
 def gt_mfma_symbols():
     """the entry points of include/fspann_groundtruth_mfma.h"""
     return sorted(_SIGS_GT_MFMA)
+
+
+def kwaves_symbols():
+    """the entry points of include/fspann_encode_kwaves.h"""
+    return sorted(_SIGS_KWAVES)

@@ -1,6 +1,7 @@
 // api_encode.hip.h — TokenGen / Setup coding entry points: fspann_encode[_dev], the encode path switch (Coding.H / Coding.C, idx/Coding.java:250-301)
 // Part of the single translation unit fspann_api.hip (included there, in order); product code, no CPU fallback.
 #pragma once
+#include "../../include/fspann_encode_kwaves.h"
 
 namespace {
 
@@ -46,9 +47,25 @@ int launch_encode_mfma_splitk(fspann_ctx* c, int64_t nq, const TIn* q_dev, int32
     return FSPANN_OK;
 }
 
+// The k-wave kernel in place of the small tile: one workgroup of 4 G waves per 32 x 128 tile, the k tiles dealt to its G groups, the
+// join in LDS (no work area, nothing to clear).  G = 4 needs 84 352 B of dynamic LDS: the kernel's ceiling is raised once per context.
+template <typename TIn, int G>
+int launch_encode_mfma_kwave(fspann_ctx* c, int64_t nq, const TIn* q_dev, int32_t* hashes_dev, unsigned long long* cw, int32_t* bad_dev,
+                             int64_t* list, int64_t cap, unsigned long long* cnt) {
+    const int P = c->P_total;
+    constexpr size_t lds = encode_kwave_lds(G);
+    if (lds > 64 * 1024)
+        if (int rc = raise_lds_ceiling(c, encode_mfma_kwave_kernel<TIn, G>, lds)) return rc;
+    const dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)), static_cast<unsigned>((P + mfma_tile_p(1) - 1) / mfma_tile_p(1)));
+    hipLaunchKernelGGL((encode_mfma_kwave_kernel<TIn, G>), grid, dim3(256 * G), lds, c->stream, q_dev, nq, c->cfg.dim, c->fam->d_alphaT32.get(), c->fam->d_r.get(),
+                       c->fam->d_omega.get(), P, c->cfg.m, c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max);
+    return FSPANN_OK;
+}
+
+// kwaves: k-groups of the k-wave kernel (fspann_set_encode_kwaves; 0 = off), taken ahead of
 // splitk: slices of the dimension (encode_splitk_slices); 1 = the unsplit kernels
 template <typename TIn>
-int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_dev, int32_t* hashes_dev, int32_t* bad_dev, int splitk = 1) {
+int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_dev, int32_t* hashes_dev, int32_t* bad_dev, int splitk = 1, int kwaves = 0) {
     const int P = c->P_total, d = c->cfg.dim;
     const int64_t cap = std::max<int64_t>(65536, nq * P / 16);
     int rc = ensure(c, c->ws_fix, 256 + static_cast<size_t>(cap) * 8);
@@ -62,7 +79,11 @@ int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* co
     // block tile: 64 x 256 for bulk coding (Setup: hundreds of thousands of rows per call); 32 x 128 with tiles in flight for batches
     // of up to a few thousand blocks of the large tile (8 192 x 1 024 x 768: 273 against 327 us; equal at 262 144 rows)
     const int64_t big_blocks = ((nq + 63) / 64) * ((P + 255) / 256);
-    if (splitk > 1) {
+    if (kwaves == 2 || kwaves == 4) {
+        rc = (kwaves == 2) ? launch_encode_mfma_kwave<TIn, 2>(c, nq, q_dev, hashes_dev, cw, bad_dev, list, cap, cnt)
+                           : launch_encode_mfma_kwave<TIn, 4>(c, nq, q_dev, hashes_dev, cw, bad_dev, list, cap, cnt);
+        if (rc) return rc;
+    } else if (splitk > 1) {
         if ((rc = launch_encode_mfma_splitk<TIn>(c, nq, q_dev, hashes_dev, cw, bad_dev, list, cap, cnt, splitk))) return rc;
     } else if (big_blocks >= 16 * static_cast<int64_t>(c->num_cus) && c->knob_mfma_tile != 1) {
         dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(2) - 1) / mfma_tile_q(2)), static_cast<unsigned>((P + mfma_tile_p(2) - 1) / mfma_tile_p(2)));
@@ -101,8 +122,13 @@ int launch_encode(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_d
         // mode 3: the dimension split over workgroups where encode_splitk_slices asks for it — query batches only, never Setup's coding
         // (a build in progress: hundreds of thousands of rows per call fill the chip unsplit)
         const int splitk = (c->encode_mode == 3 && c->bld_done < 0) ? encode_splitk_slices(c, nq) : 1;
-        int rc = launch_encode_mfma<TIn>(c, nq, q_dev, codes_dev, hashes_dev, bad_dev, splitk);
+        // the k-wave kernel (fspann_set_encode_kwaves, opt-in): only where mode 2 or 3 chose this path (never auto), for query batches, and
+        // with at least two k tiles to deal out; it goes ahead of mode 3's split over workgroups
+        const int kwaves = (c->encode_mode != 0 && c->bld_done < 0 && c->cfg.dim > kMfmaKT) ? c->encode_kwaves : 0;
+        c->kwaves_last = 0;
+        int rc = launch_encode_mfma<TIn>(c, nq, q_dev, codes_dev, hashes_dev, bad_dev, splitk, kwaves);
         if (rc <= 0) return rc;  // error
+        c->kwaves_last = kwaves;
         // the list can only overflow when almost every pair sits on a bucket boundary (degenerate omega): the
         // exact kernel below is enqueued with a device-side guard and returns immediately otherwise.
         guard = static_cast<const unsigned long long*>(c->ws_fix.p);
@@ -110,6 +136,7 @@ int launch_encode(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* codes_d
         c->mfma_last = true;
     } else {
         c->mfma_last = false;
+        c->kwaves_last = 0;
     }
     const int tdPerBlock = std::max(1, kEncThreads / m);
     const int gy = (c->TD + tdPerBlock - 1) / tdPerBlock;
@@ -205,6 +232,19 @@ int fspann_set_encode_mode(fspann_ctx* c, int mode) {
     if (mode < 0 || mode > 3) return fail(FSPANN_E_ARG, "encode mode must be 0, 1, 2 or 3");
     c->encode_mode = mode;
     return FSPANN_OK;
+}
+// include/fspann_encode_kwaves.h: the k-groups of the k-wave MFMA encode (encode_mfma_kwave_kernel), 0 = off.  It applies where mode
+// 2 or 3 chose the MFMA path for a query batch of at least two k tiles (launch_encode); every mode stays bit-identical.
+int fspann_set_encode_kwaves(fspann_ctx* c, int groups) {
+    CHECK_CTX(c);
+    if (groups != 0 && groups != 2 && groups != 4) return fail(FSPANN_E_ARG, "encode k-groups must be 0, 2 or 4");
+    c->encode_kwaves = groups;
+    return FSPANN_OK;
+}
+// k-groups the last encode call ran with (0: it ran another kernel)
+int fspann_last_encode_kwaves(fspann_ctx* c) {
+    CHECK_CTX(c);
+    return c->kwaves_last;
 }
 // (query, projection) pairs the last MFMA-path encode re-checked with the exact kernel (0 for the exact path).
 int64_t fspann_last_encode_rechecked(fspann_ctx* c) {

@@ -298,6 +298,10 @@ int fspann_ctx_create(int device, const fspann_cfg* cfg, fspann_ctx** out) {
         c->knob_encode_qb = env_int("FSPANN_ENCODE_QB", 0);
         c->knob_mfma_tile = env_int("FSPANN_ENCODE_MFMA_TILE", 0);
         c->knob_encode_splitk = std::max(0, env_int("FSPANN_ENCODE_SPLITK", 0));
+        {
+            const int kw = env_int("FSPANN_ENCODE_KWAVES", 0);      // the initial value of fspann_set_encode_kwaves (anything but 2 or 4: off)
+            c->encode_kwaves = (kw == 2 || kw == 4) ? kw : 0;
+        }
         c->knob_route_wgs = env_int("FSPANN_ROUTE_WGS", 0);
         c->knob_refine_run = env_int("FSPANN_REFINE_RUN", 1) != 0;
         c->knob_devflags = env_int("FSPANN_ROUTE_DEVFLAGS", 0);
@@ -363,6 +367,7 @@ int fspann_ctx_clone(fspann_ctx* src, fspann_ctx** out) {
     c->fam = src->fam;
     c->store = src->store;
     c->encode_mode = src->encode_mode;
+    c->encode_kwaves = src->encode_kwaves;
     c->route_mode = src->route_mode;
     c->frozen = true;
     c->is_clone = true;

@@ -835,6 +835,235 @@ __global__ __launch_bounds__(256, 2) void encode_mfma_splitk_kernel(
 }
 
 // =====================================================================================
+// k-wave MFMA encode: the slices of one 32 x 128 tile as the WAVES of one larger workgroup, joined through LDS.  For the batches that
+// leave most CUs without a block (512 x 256 x 960: 32 tiles on 256 CUs) a block may take a whole CU: 4 G waves, G k-groups of four.
+// Wave w of group g owns columns [32 w, 32 w + 32) of the tile like wave w of encode_mfma_kernel<TIn, 1, 1>, and group g accumulates
+// the k tiles g, g + G, g + 2 G, ... (interleaved: the groups' loads of one trip are neighbours in alphaT32 and in the query rows).
+// Each group has an LDS stage of its own (Vs[32][33] + As[32][128]) and fills it with the small tile's scheme — register sets in
+// rotation (three at G = 2; two at G = 4, where 1 024 threads leave a lane 128 registers), unconditional clamped loads, zeroing at
+// the LDS write against d: a tile of the group's list that starts behind d is all zeros.
+//
+// Barriers: s_barrier is workgroup-wide, so EVERY wave runs the same trips = ceil(ceil(d / 32) / G) trips and the same two
+// lds_barrier()s per trip whatever its group's list holds (a shorter list: the last trip multiplies zeros); the trip count is a
+// function of d and G alone, there is no exit in front of the join, nothing waits for another workgroup, no fence is wider than
+// the workgroup.
+//
+// Join: behind the loop's last barrier the G x 16 KB of As stages are free and become part[G][16][256] floats — group g's
+// accumulators in register order, word (reg * 4 + w) * 64 + lane as in the split-k slots, so a wave's store of one register is 256
+// contiguous bytes; beside them each group's 32 partial squared norms (fp64) and 32 non-finite flags.  One barrier, then the tile is
+// REDISTRIBUTED: wave (g, w) takes the registers [16 g / G, 16 (g + 1) / G) of column block w and sums their G partials in the order
+// 0 .. G - 1 (add_f32_single: never packed), the first 32 threads sum the norms (fp64, same order) and OR the flags.  One more
+// barrier, and every wave runs the unsplit epilogue on its 16 / G registers: the ~12 fp64 instructions per pair, which bound the
+// unsplit kernel, are spread over G times the waves.  A register is two rows x 32 columns whoever holds it, so the ballot pack is
+// the unsplit one per register.  Nothing depends on timing.
+//
+// Error bound: group g's chain is at most 32 ceil(KT / G) fused multiply-adds, the join adds G - 1 fp32 additions: a summation tree
+// over the same d products of depth 32 ceil(KT / G) + G - 1 <= d for 2 <= G <= KT (the split-k argument above with S = G; a group
+// whose list is empty adds exact zeros, which shortens the tree).  mfma_row_band on the TOTAL norm covers it unchanged.
+// =====================================================================================
+__host__ __device__ constexpr size_t encode_kwave_lds(int G) {
+    return static_cast<size_t>(G) * (kMfmaKT * 128 * 4 + 32 * (kMfmaKT + 1) * 4 + 32 * 8 + 32 * 4) + 32 * 8 + 32 * 4;
+}
+
+template <typename TIn, int G>
+__global__ __launch_bounds__(256 * G) void encode_mfma_kwave_kernel(
+    const TIn* __restrict__ q, int64_t nq, int d, const float* __restrict__ alphaT32 /*[d][P]*/,
+    const double* __restrict__ r, const double* __restrict__ omega, int P, int m, int lambda, int W, int TD, int32_t* __restrict__ hashes,
+    unsigned long long* __restrict__ codes, int32_t* __restrict__ bad, int64_t* __restrict__ fix_list, int64_t fix_cap,
+    unsigned long long* __restrict__ fix_count, double alpha_norm_max) {
+    static_assert(G == 2 || G == 4, "k-groups per workgroup: 2 or 4");
+    constexpr int kTileQ = mfma_tile_q(1), kTileP = mfma_tile_p(1);
+    constexpr int kVsLd = kMfmaKT + 1;
+    extern __shared__ __align__(16) unsigned char kwave_smem[];
+    float* const As_all = reinterpret_cast<float*>(kwave_smem);                  // [G][kMfmaKT][kTileP]; behind the loop: part[G][16][256]
+    float* const Vs_all = As_all + G * kMfmaKT * kTileP;                         // [G][kTileQ][kVsLd]
+    double* const pnorm = reinterpret_cast<double*>(Vs_all + G * kTileQ * kVsLd);   // [G][kTileQ] partial squared row norms
+    double* const band = pnorm + G * kTileQ;                                     // [kTileQ] guard band of the whole row
+    int* const pflag = reinterpret_cast<int*>(band + kTileQ);                    // [G][kTileQ] non-finite flags per group
+    int* const badrow = pflag + G * kTileQ;                                      // [kTileQ] ... OR-ed
+    const int tid = threadIdx.x, lane = tid & 63, g = tid >> 8, w = (tid >> 6) & 3, gt = tid & 255;    // gt: thread of its group
+    float* const Vs = Vs_all + g * kTileQ * kVsLd;
+    float* const As = As_all + g * kMfmaKT * kTileP;
+    int* const myflag = pflag + g * kTileQ;
+    const int64_t q0 = static_cast<int64_t>(blockIdx.x) * kTileQ;
+    const int p0 = blockIdx.y * kTileP;
+    const int trips = ((d + kMfmaKT - 1) / kMfmaKT + G - 1) / G;     // the SAME for every wave of the workgroup: d and G alone
+    if (gt < kTileQ) myflag[gt] = 0;
+    fsp_acc16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = 0.0f;
+    // V tile: group thread t holds the four k [4 (t & 7), 4 (t & 7) + 4) of row t >> 3 — one row per thread, so one partial norm and
+    // one row offset instead of the small tile's four (registers: G = 4 has 128 per lane)
+    constexpr int kVEls = kTileQ * kMfmaKT / 256;
+    constexpr int kAVecs = kMfmaKT * kTileP / 4 / 256;   // 16-byte pieces of the A tile per thread
+    const int vrow = gt >> 3, vc4 = (gt & 7) * kVEls;
+    double nrm = 0.0;
+    __syncthreads();
+    const bool a_vec = ((P & 3) == 0);
+
+    // addresses as one uniform base and 32-bit offsets (a pointer per row and piece held across the loop does not fit G = 4's registers)
+    const TIn* const qb = q + q0 * d;
+    const int voff = static_cast<int>(min(static_cast<int64_t>(vrow), nq - 1 - q0)) * d;      // (the row clamped into the batch)
+    const bool vrow_in = q0 + vrow < nq;
+    const int pcol = min(p0 + (gt & 31) * 4, P - 4);
+    constexpr int kSets = (G == 4) ? 2 : 3;
+    TIn vreg[kSets][kVEls];
+    fsp_f4 areg[kSets][kAVecs];
+    auto fetch = [&](auto set_c, const int t) {          // trip t of this group: k tile t G + g
+        constexpr int st = decltype(set_c)::value;
+        const int k0 = (t * G + g) * kMfmaKT;
+#pragma unroll
+        for (int u = 0; u < kVEls; u++) vreg[st][u] = qb[voff + min(k0 + vc4 + u, d - 1)];
+#pragma unroll
+        for (int i = 0; i < kAVecs; i++) {
+            const int kk = (gt >> 5) + 8 * i, pc = (gt & 31) * 4;      // piece gt + 256 i of the tile: row kk, columns [pc, pc + 4)
+            if (a_vec) {                           // uniform: P % 4 == 0, so a 16-byte piece lies wholly inside or wholly outside P
+                areg[st][i] = *reinterpret_cast<const fsp_f4*>(alphaT32 + static_cast<int64_t>(min(k0 + kk, d - 1)) * P + pcol);
+            } else {
+                fsp_f4 a = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (k0 + kk < d) {
+                    const float* src = alphaT32 + static_cast<int64_t>(k0 + kk) * P + p0 + pc;
+#pragma unroll
+                    for (int u = 0; u < 4; u++) if (p0 + pc + u < P) a[u] = src[u];
+                }
+                areg[st][i] = a;
+            }
+        }
+    };
+    auto tile_from = [&](auto set_c, const int t) {
+        constexpr int st = decltype(set_c)::value;
+        const int k0 = (t * G + g) * kMfmaKT;
+        bool nonfinite = false;
+#pragma unroll
+        for (int u = 0; u < kVEls; u++) {
+            const double v = (vrow_in && k0 + vc4 + u < d) ? static_cast<double>(vreg[st][u]) : 0.0;
+            nonfinite |= !(fabs(v) <= 1.79769313486231570815e+308);
+            Vs[vrow * kVsLd + vc4 + u] = static_cast<float>(v);
+            nrm += v * v;
+        }
+        if (nonfinite) myflag[vrow] = 1;
+#pragma unroll
+        for (int i = 0; i < kAVecs; i++) {
+            const int kk = (gt >> 5) + 8 * i, pc = (gt & 31) * 4;
+            const fsp_f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+            *reinterpret_cast<fsp_f4*>(&As[kk * kTileP + pc]) = (!a_vec || (k0 + kk < d && p0 + pc < P)) ? areg[st][i] : zero;
+        }
+        lds_barrier();
+        if (t + kSets < trips) fetch(set_c, t + kSets);                // uniform: the set just emptied takes the trip kSets ahead
+#pragma unroll
+        for (int kk = 0; kk < kMfmaKT; kk += 2) {
+            const float av = Vs[(lane & 31) * kVsLd + kk + (lane >> 5)];
+            const float bv = As[(kk + (lane >> 5)) * kTileP + w * 32 + (lane & 31)];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+        }
+        lds_barrier();
+    };
+    using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, 1>; using S2 = std::integral_constant<int, 2>;
+    fetch(S0{}, 0);
+    if (1 < trips) fetch(S1{}, 1);
+    if constexpr (kSets == 3) { if (2 < trips) fetch(S2{}, 2); }
+    for (int t = 0; t < trips; t += kSets) {                           // workgroup-uniform trips, two barriers each
+        tile_from(S0{}, t);
+        if (t + 1 < trips) tile_from(S1{}, t + 1);
+        if constexpr (kSets == 3) { if (t + 2 < trips) tile_from(S2{}, t + 2); }
+    }
+    // the group's part of the row norms: reduce the eight lanes that share a row, one writer per row
+    for (int off = 4; off > 0; off >>= 1) nrm += __shfl_xor(nrm, off);
+    if ((gt & 7) == 0) pnorm[g * kTileQ + vrow] = nrm;
+    // the group's accumulators over the As stages (every wave is behind the loop's last barrier: nobody reads a stage any more)
+    {
+        float* part = As_all + g * kSplitAccWords + w * 64 + lane;
+#pragma unroll
+        for (int reg = 0; reg < 16; reg++) part[reg * 256] = acc[reg];
+    }
+    __syncthreads();
+
+    // join: wave (g, w) takes registers [g R, (g + 1) R) of column block w, every group's partial in the order 0 .. G - 1
+    constexpr int R = 16 / G;
+    float y32[R];
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        const float* src = As_all + (g * R + j) * 256 + w * 64 + lane;
+        float v[G];
+#pragma unroll
+        for (int zz = 0; zz < G; zz++) v[zz] = src[zz * kSplitAccWords];
+        y32[j] = v[0];
+#pragma unroll
+        for (int zz = 1; zz < G; zz++) y32[j] = add_f32_single(y32[j], v[zz]);
+    }
+    if (tid < kTileQ) {
+        double s = 0.0;
+        int flag = 0;
+#pragma unroll
+        for (int zz = 0; zz < G; zz++) {
+            s = s + pnorm[zz * kTileQ + tid];
+            flag |= pflag[zz * kTileQ + tid];
+        }
+        badrow[tid] = flag;
+        band[tid] = mfma_row_band(d, alpha_norm_max, s);               // per-row guard band (y units) of the WHOLE row's norm
+        if (bad && blockIdx.y == 0 && q0 + tid < nq) bad[q0 + tid] = flag;
+    }
+    __syncthreads();
+
+    // epilogue of encode_mfma_kernel (RT = CT = 1) on this wave's R registers: quantise, interval test, bit-pack into the pre-zeroed
+    // code words, fix list
+    const int half = lane >> 5, c32 = lane & 31;
+    const int pb = p0 + w * 32;                             // first projection of this wave's 32 columns (wave-uniform)
+    const int p = pb + c32;
+    const double rr = (p < P) ? r[p] : 0.0, ww = (p < P) ? omega[p] : 1.0;
+    const double iw = 1.0 / ww;
+    // the (t,d) tables whose projections fall into this tile: lane (half, seg) packs the bits of table td_first + seg for row-half `half`
+    const int td_first = pb / m;
+    const int td_last = min(P - 1, pb + 31) / m;
+    const int nseg = (pb < P) ? td_last - td_first + 1 : 0;
+    const int my_td = td_first + c32;
+    const bool seg_on = c32 < nseg;
+    const int c_lo = seg_on ? max(0, my_td * m - pb) : 0;
+    const int c_hi = seg_on ? min(min(31, P - 1 - pb), my_td * m + m - 1 - pb) : -1;
+    const int flen = c_hi - c_lo + 1;
+    const int j_lo = pb + c_lo - my_td * m;
+    const unsigned fmask = (flen >= 32) ? 0xFFFFFFFFu : ((1u << max(flen, 0)) - 1u);
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+        const int reg = g * R + j;                          // (wave-uniform)
+        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        const int64_t qi = q0 + row;
+        const bool live = (qi < nq) && (p < P);
+        const double y = static_cast<double>(y32[j]);
+        double fl;
+        const bool inside = mfma_pair_safe(y, band[row], rr, ww, iw, &fl);
+        const bool safe = live && inside && !badrow[row];
+        const int32_t h = java_d2i(fl);
+        if (live && hashes) hashes[qi * P + p] = h;
+        if (live && !safe) {
+            const unsigned long long pos = atomicAdd(fix_count, 1ull);
+            if (pos < static_cast<unsigned long long>(fix_cap)) fix_list[pos] = qi * P + p;
+        }
+        // Coding.C: bit pos = (lambda-1-i)*m + j  <-  bit i of (h_j ^ 0x80000000); one ballot per plane, low half = the
+        // 32 columns of row `row` (half 0), high half = those of row + 4 (half 1)
+        const uint32_t hj = static_cast<uint32_t>(h) ^ 0x80000000u;
+        unsigned long long w0 = 0, w1 = 0, w2 = 0;
+        for (int i = 0; i < lambda; i++) {                            // uniform trip count: every lane takes part in the ballot
+            const unsigned long long bm = __ballot(safe && ((hj >> (i & 31)) & 1u));
+            if (flen > 0) {
+                const unsigned long long field = (bm >> (half * 32 + c_lo)) & fmask;
+                const int bp = (lambda - 1 - i) * m + j_lo;
+                const int wd = bp >> 6, off = bp & 63;
+                const unsigned long long lo = field << off;
+                const unsigned long long hi = (off + flen > 64) ? (field >> (64 - off)) : 0ull;
+                if (wd == 0) { w0 |= lo; w1 |= hi; } else if (wd == 1) { w1 |= lo; w2 |= hi; } else { w2 |= lo; }
+            }
+        }
+        if (flen > 0 && qi < nq) {
+            unsigned long long* cw = codes + (qi * TD + my_td) * W;
+            if (w0) atomicOr(cw, w0);
+            if (W > 1 && w1) atomicOr(cw + 1, w1);
+            if (W > 2 && w2) atomicOr(cw + 2, w2);
+        }
+    }
+}
+
+// =====================================================================================
 // The MFMA encode as ONE workgroup role (front_kernel's encode role, tick.hip.h): kFrontEncQ query rows x ALL P projections.
 // Owning whole tables it writes whole code words — no clearing launch, no atomicOr, no fix list, no fix launch — and it
 // re-checks its own undecided pairs.  Inside the front launch the role's latency hides behind the Route workgroups beside it;

@@ -264,6 +264,8 @@ struct fspann_ctx {
     int encode_mode = 0;                       // 0 auto, 1 exact fp64, 2 MFMA fp32 + exact re-check, 3 = 2 with the dimension split over workgroups
     unsigned long long fix_cap_last = 0;       // capacity of the re-check list of the last MFMA-path call
     bool mfma_last = false;                    // the last encode took the MFMA path
+    int encode_kwaves = 0;                     // fspann_set_encode_kwaves: k-groups of the k-wave MFMA encode (0 off, 2, 4); initial value: FSPANN_ENCODE_KWAVES
+    int kwaves_last = 0;                       // k-groups the last encode ran with (0: another kernel)
     fspann::DevBuf ws_fix;                     // fix list + counter + int32 hashes of the MFMA path
     fspann::DevBuf ws_splitk;                  // arrival counters + [tile][slice] partials of the split-k MFMA encode
     int route_mode = 0;              // 0 auto, 1 always route_select_kernel, 2 bounded select whenever its preconditions hold

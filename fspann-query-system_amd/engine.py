@@ -403,6 +403,19 @@ class FspannContext:
     def last_encode_rechecked(self) -> int:
         return int(self.L.fspann_last_encode_rechecked(self._h))
 
+    def set_encode_kwaves(self, groups: int):
+        """k-groups of the k-wave MFMA encode (include/fspann_encode_kwaves.h): 0 off, 2 or 4 groups of four waves share one
+        32 x 128 tile and join in LDS.  It applies to query batches that encode mode 2 or 3 sends down the MFMA path (all
+        bit-identical)."""
+        N.check(self.L.fspann_set_encode_kwaves(self._h, int(groups)))
+
+    def last_encode_kwaves(self) -> int:
+        """the k-groups the last encode call ran with (0: it ran another kernel)"""
+        rc = int(self.L.fspann_last_encode_kwaves(self._h))
+        if rc < 0:
+            N.check(rc)
+        return rc
+
     # -- Route ---------------------------------------------------------------------
     def effective_probes(self, probe_override=-1):
         return self.L.fspann_effective_probes(self._h, probe_override)

@@ -1,7 +1,7 @@
 """ctypes binding of libfspann_hip.so (include/fspann.h, include/fspann_groundtruth_rows.h, include/fspann_eval.h,
 include/fspann_gt_validate.h, include/fspann_route_plan.h, include/fspann_sweep.h, include/fspann_narrow.h,
 include/fspann_route_recall.h, include/fspann_route_coverage.h, include/fspann_groundtruth_mfma.h,
-include/fspann_encode_kwaves.h).
+include/fspann_encode_kwaves.h, include/fspann_groundtruth_mfma16.h).
 
 Product code.  There is no CPU fallback: if the HIP library is missing, import
 fails; if no GPU is present, creating a context raises FspannDeviceError.
@@ -89,7 +89,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h", "fspann_route_coverage.h", "fspann_groundtruth_mfma.h", "fspann_encode_kwaves.h")]
+    inc = [os.path.join(_HERE, "..", "include", h) for h in ("fspann.h", "fspann_groundtruth_rows.h", "fspann_eval.h", "fspann_gt_validate.h", "fspann_route_plan.h", "fspann_sweep.h", "fspann_narrow.h", "fspann_route_recall.h", "fspann_route_coverage.h", "fspann_groundtruth_mfma.h", "fspann_encode_kwaves.h", "fspann_groundtruth_mfma16.h")]
     return any(os.path.getmtime(p) > t for p in sources() + inc)
 
 
@@ -300,6 +300,13 @@ _SIGS_KWAVES = {
     "fspann_last_encode_kwaves": (_i, [_vp]),
 }
 
+# include/fspann_groundtruth_mfma16.h: the ground truth with the pre-filter on the 16-bit matrix cores, for narrow rows (a table of
+# its own: those above stay as they are)
+_SIGS_GT_MFMA16 = {
+    "fspann_groundtruth_mfma16_dev": _SIGS_GT_MFMA["fspann_groundtruth_mfma_dev"],
+    "fspann_groundtruth_mfma16_store_dev": _SIGS_GT_MFMA["fspann_groundtruth_mfma_store_dev"],
+}
+
 
 def lib() -> C.CDLL:
     """Load libfspann_hip.so; raises if it has not been built (no fallback)."""
@@ -310,7 +317,7 @@ def lib() -> C.CDLL:
                 f"{_SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  fspann has no CPU fallback.")
         L = C.CDLL(_SO)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()) + list(_SIGS_COVERAGE.items()) + list(_SIGS_GT_MFMA.items()) + list(_SIGS_KWAVES.items()):
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_ROWS.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_VALIDATE.items()) + list(_SIGS_PLAN.items()) + list(_SIGS_SWEEP.items()) + list(_SIGS_NARROW.items()) + list(_SIGS_ROUTE_RECALL.items()) + list(_SIGS_COVERAGE.items()) + list(_SIGS_GT_MFMA.items()) + list(_SIGS_KWAVES.items()) + list(_SIGS_GT_MFMA16.items()):
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart
             fn.restype = res
             fn.argtypes = args
@@ -377,3 +384,8 @@ def gt_mfma_symbols():
 def kwaves_symbols():
     """the entry points of include/fspann_encode_kwaves.h"""
     return sorted(_SIGS_KWAVES)
+
+
+def gt_mfma16_symbols():
+    """the entry points of include/fspann_groundtruth_mfma16.h"""
+    return sorted(_SIGS_GT_MFMA16)

@@ -11,7 +11,10 @@ namespace {
 // of all nq queries (what the call reads back), |x|^2 [n], then per chunk |q|^2, the thresholds, the survivor lists [chunk x kGtmCap]
 // and the [chunk x ld] estimates, every part 256-byte aligned.  The chunk follows gt8_run's rule over the same budget, with the lists
 // counted in.  Every kernel of every chunk is launched before anything is known on the host — a flagged call's kernels return at
-// once, an overflowed query's finish returns — and ONE synchronisation reads the flag and the counts.
+// once, an overflowed query's finish returns — and ONE synchronisation reads the flag and the counts (gtm_read_back).
+template <typename TB>
+int gtm_read_back(fspann_ctx* c, const char* w, int64_t n, const TB* base, int64_t nq, const float* q, int dim, int k, int32_t* out_ids, double* out_d2,
+                  fspann_gt_mfma_stats* stats);
 template <typename TB>
 int gtm_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const float* q, int dim, int k, int32_t* out_ids, double* out_d2, fspann_gt_mfma_stats* stats) {
     if (dim > kGtmMaxDim) {
@@ -59,6 +62,14 @@ int gtm_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const float* q
                            qs, dim, k, lists, counts + s, st, out_ids + s * k, out_d2 ? out_d2 + s * k : nullptr);
         FSP_HIP(hipGetLastError());
     }
+    return gtm_read_back(c, w, n, base, nq, q, dim, k, out_ids, out_d2, stats);
+}
+
+// The end of a pre-filtered call (this one's and gtm16_run's), behind the launches of all its chunks: the ONE synchronisation, which
+// reads the head of ws_gt `w` — GtmState and the nq survivor counts —, and the two ways out to gt_rows_run.
+template <typename TB>
+int gtm_read_back(fspann_ctx* c, const char* w, int64_t n, const TB* base, int64_t nq, const float* q, int dim, int k, int32_t* out_ids, double* out_d2,
+                  fspann_gt_mfma_stats* stats) {
     std::vector<int32_t> host(sizeof(GtmState) / 4 + static_cast<size_t>(nq));
     FSP_HIP(hipMemcpyAsync(host.data(), w, host.size() * 4, hipMemcpyDeviceToHost, c->stream));
     FSP_HIP(hipStreamSynchronize(c->stream));
@@ -91,7 +102,7 @@ int gtm_run(fspann_ctx* c, int64_t n, const TB* base, int64_t nq, const float* q
     FSP_HIP(hipMemcpyAsync(idx.get(), over.data(), static_cast<size_t>(m) * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(gtm_gather_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, c->stream, q, idx.get(), dim, tq.get());
     FSP_HIP(hipGetLastError());
-    rc = gt_rows_run(c, n, base, m, tq.get(), dim, k, tids.get(), td2.get());
+    int rc = gt_rows_run(c, n, base, m, tq.get(), dim, k, tids.get(), td2.get());
     if (rc == FSPANN_OK) {
         hipLaunchKernelGGL(gtm_scatter_kernel, dim3(static_cast<unsigned>(m)), dim3(256), 0, c->stream, idx.get(), k, tids.get(), td2.get(), out_ids, out_d2);
         rc = hipGetLastError() == hipSuccess ? FSPANN_OK : fail(FSPANN_E_DEVICE, "gtm_scatter_kernel failed to launch");

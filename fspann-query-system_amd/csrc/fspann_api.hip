@@ -18,6 +18,7 @@
 #include "eval_sweep.hip.h"
 #include "groundtruth_u8.hip.h"
 #include "groundtruth_mfma.hip.h"
+#include "groundtruth_mfma16.hip.h"
 #include "gt_validate.hip.h"
 #include "hostpipe.hip.h"
 #include "narrow.hip.h"
@@ -45,6 +46,7 @@
 #include "api_hostpipe.hip.h"
 #include "api_groundtruth.hip.h"
 #include "api_groundtruth_mfma.hip.h"
+#include "api_groundtruth_mfma16.hip.h"
 #include "api_misc.hip.h"
 #include "api_build.hip.h"
 #include "api_ext.hip.h"

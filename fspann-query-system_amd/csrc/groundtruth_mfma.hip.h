@@ -193,8 +193,10 @@ __global__ __launch_bounds__(256) void gtm_dist_kernel(const TB* __restrict__ ba
 // helper gt8_hist_add is called as it is).  Then the query's threshold, thr = a_k + 2 eps_q rounded UP in fp32, as bits:
 //     eps_q = 1.01 [ 2 (d + 4) 2^-24 |q| X + 2^-21 (|q| + X)^2 ] + d 2^-120          X = the largest |x| of the base
 // from the fp32 |q|^2 inflated by its own rounding and the fp64 X^2, in fp64.
-__global__ __launch_bounds__(kGtmSelThreads) void gtm_kth_kernel(const unsigned* __restrict__ dist, int64_t ld, int64_t n, int k, int d,
-                                                                 const float* __restrict__ qn, const GtmState* __restrict__ st, unsigned* __restrict__ thr) {
+// (gtm_kth_body: the kernel but for eps_q, which eps(qi) gives; gtm16_kth_kernel of groundtruth_mfma16.hip.h is the other caller)
+template <class Eps>
+__device__ __forceinline__ void gtm_kth_body(const unsigned* __restrict__ dist, int64_t ld, int64_t n, int k, const GtmState* __restrict__ st,
+                                             unsigned* __restrict__ thr, Eps eps_of) {
     __shared__ unsigned hist[256];
     __shared__ unsigned s_pk, s_need;
     if (st->flag) return;
@@ -233,14 +235,20 @@ __global__ __launch_bounds__(kGtmSelThreads) void gtm_kth_kernel(const unsigned*
     }
     if (tid == 0) {
         const double ak = static_cast<double>(__uint_as_float(s_pk));
-        const double nq1 = sqrt(static_cast<double>(qn[qi]) * (1.0 + 0x1p-23));
-        const double X = sqrt(__longlong_as_double(static_cast<long long>(st->xmax_bits)));
-        const double eps = 1.01 * (2.0 * static_cast<double>(d + 4) * 0x1p-24 * nq1 * X + 0x1p-21 * (nq1 + X) * (nq1 + X)) + static_cast<double>(d) * 0x1p-120;
+        const double eps = eps_of(qi);
         const double t64 = ak + 2.0 * eps;
         float t = static_cast<float>(t64);
         if (static_cast<double>(t) < t64) t = __uint_as_float(__float_as_uint(t) + 1u);      // (t >= 0 and far below FLT_MAX: the next float up)
         thr[qi] = __float_as_uint(t);
     }
+}
+__global__ __launch_bounds__(kGtmSelThreads) void gtm_kth_kernel(const unsigned* __restrict__ dist, int64_t ld, int64_t n, int k, int d,
+                                                                 const float* __restrict__ qn, const GtmState* __restrict__ st, unsigned* __restrict__ thr) {
+    gtm_kth_body(dist, ld, n, k, st, thr, [&](int64_t qi) {
+        const double nq1 = sqrt(static_cast<double>(qn[qi]) * (1.0 + 0x1p-23));
+        const double X = sqrt(__longlong_as_double(static_cast<long long>(st->xmax_bits)));
+        return 1.01 * (2.0 * static_cast<double>(d + 4) * 0x1p-24 * nq1 * X + 0x1p-21 * (nq1 + X) * (nq1 + X)) + static_cast<double>(d) * 0x1p-120;
+    });
 }
 
 // The ids of a query's survivors, key <= thr, appended to its list [kGtmCap] in any order: a wave's hits take their places with one

@@ -11,6 +11,8 @@
 //   wide(slot, e)      element e of a slot widened EXACTLY to fp64 (e is a constant after unrolling)
 //   piece_f32(p, e)    element e of a 16-byte piece held as four dwords (fsp_u32x4: what the ground-truth kernels load), widened
 //                      EXACTLY to fp32; every type but double has it, every value of those types is a float, so nothing rounds
+//   piece_f16x8(p, u)  elements [8 u, 8 u + 8) of such a piece as eight halves, EXACTLY (the types whose every value is a half: the
+//                      bytes, fp8 and the half itself): one operand of v_mfma_f32_32x32x16_f16 (groundtruth_mfma16.hip.h)
 //   quad_f32(in)         four consecutive elements (4-byte aligned for the byte types, 8-byte for the 16-bit ones) widened exactly to
 //                      fp32: Setup's input of a row-only type
 //   finite(x)          one raw element is finite
@@ -69,8 +71,24 @@ template <> struct RowCodec<double> : NativeRowCodec<double, fsp_f64x2> {
     static __device__ __forceinline__ double wide(slot v, int e) { return v[e]; }
 };
 
+typedef _Float16 fsp_f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 fsp_f16x8 __attribute__((ext_vector_type(8)));
+// Bytes 8 u .. 8 u + 7 of a piece, each b in 0..255, as the halves b - bias: 0x6400 | b is the half 1024 + b (one ulp there is 1),
+// and a packed subtraction, exact, takes 1024 + bias off again — no conversion instruction.
+__device__ __forceinline__ fsp_f16x8 fsp_bytes_f16x8(fsp_u32x4 p, int u, _Float16 bias) {
+    fsp_u32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t w = p[2 * u + (j >> 1)] >> (16 * (j & 1));
+        const fsp_f16x2 h = __builtin_bit_cast(fsp_f16x2, (w & 0xffu) | ((w & 0xff00u) << 8) | 0x64006400u) - static_cast<_Float16>(static_cast<_Float16>(1024.0f) + bias);
+        r[j] = __builtin_bit_cast(uint32_t, h);
+    }
+    return __builtin_bit_cast(fsp_f16x8, r);
+}
+
 // FSPANN_U8: a row element is the integer 0..255; the slot is held as four unsigned dwords.
 template <> struct RowCodec<uint8_t> : ByteRowCodec<uint8_t, fsp_u32x4> {
+    static __device__ __forceinline__ fsp_f16x8 piece_f16x8(fsp_u32x4 p, int u) { return fsp_bytes_f16x8(p, u, static_cast<_Float16>(0.0f)); }
     // A bit-field extract and v_cvt_f64_u32.  Measured against v_cvt_f32_ubyte0..3 + v_cvt_f64_f32, against building 2^52 + byte in
     // the mantissa and subtracting 2^52 (no conversion at all), and against keeping the query's tile as fp64 in LDS instead of
     // converting it per element: within 5 % of each other — every vector instruction of the scan's loop issues at
@@ -110,6 +128,8 @@ template <> struct RowCodec<int8_t> : ByteRowCodec<int8_t, fsp_u64x2> {
                            static_cast<float>(static_cast<int32_t>(w << 8) >> 24), static_cast<float>(static_cast<int32_t>(w) >> 24));
     }
     static constexpr unsigned kToSigned = 0u;      // already signed; ^ 0 compiles to nothing
+    // b ^ 0x80 is the unsigned byte b + 128
+    static __device__ __forceinline__ fsp_f16x8 piece_f16x8(fsp_u32x4 p, int u) { return fsp_bytes_f16x8(p ^ 0x80808080u, u, static_cast<_Float16>(128.0f)); }
     // an integer in -128..127 (the test of FSPANN_U8 over another range)
     static __device__ __forceinline__ bool fits(float x) { return x >= -128.0f && x <= 127.0f && static_cast<float>(static_cast<int32_t>(x)) == x; }
     static __device__ __forceinline__ int8_t narrow(float x) { return static_cast<int8_t>(static_cast<int32_t>(x)); }
@@ -120,8 +140,8 @@ template <> struct RowCodec<int8_t> : ByteRowCodec<int8_t, fsp_u64x2> {
 // FSPANN_F16: a 16-byte slot is 8 IEEE binary16 elements (four dwords, two halves each, low element in the low 16 bits).  An
 // element is the half widened exactly (half -> float -> double: every finite half, subnormals included, is a double), and unlike a
 // byte it can be +-inf or NaN.
-typedef _Float16 fsp_f16x8 __attribute__((ext_vector_type(8)));
 template <> struct RowCodec<_Float16> : NativeRowCodec<_Float16, fsp_f16x8> {
+    static __device__ __forceinline__ fsp_f16x8 piece_f16x8(fsp_u32x4 p, int) { return __builtin_bit_cast(fsp_f16x8, p); }
     // v_cvt_f32_f16 (the high half of a dword through SDWA src0_sel:WORD_1, no shift), then v_cvt_f64_f32
     static __device__ __forceinline__ double wide(slot v, int e) { return static_cast<double>(static_cast<float>(v[e])); }
     // the same v_cvt_f32_f16 (WORD_1 for the high half)
@@ -188,6 +208,13 @@ template <> struct RowCodec<fsp_f8e4m3> : RowCodecOf<fsp_f8e4m3, fsp_u64x2> {
     static __device__ __forceinline__ float piece_f32(fsp_u32x4 p, int e) {
         const int w = static_cast<int>(p[e >> 2]);
         return (e & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true)[e & 1] : __builtin_amdgcn_cvt_pk_f32_fp8(w, false)[e & 1];
+    }
+    // |x| <= 448 with four significant bits down to 2^-9: every e4m3 value is a normal half, so float -> half rounds nothing
+    static __device__ __forceinline__ fsp_f16x8 piece_f16x8(fsp_u32x4 p, int u) {
+        fsp_f16x8 r;
+#pragma unroll
+        for (int e = 0; e < 8; e++) r[e] = static_cast<_Float16>(piece_f32(p, 8 * u + e));
+        return r;
     }
     static __device__ __forceinline__ float slot_f32(slot v, int e) {
 #if FSPANN_F8_WIDEN == 0

@@ -165,10 +165,11 @@ def _row_dt(a):
 
 
 def _gt_method(method):
-    """method= of the numpy-level ground-truth calls: True for "mfma", False for "exact", anything else refused"""
-    if method not in ("exact", "mfma"):
-        raise N.FspannArgumentError(f"method must be 'exact' or 'mfma': {method!r}")
-    return method == "mfma"
+    """method= of the numpy-level ground-truth calls: "" for "exact", else the infix of the pre-filtered calls' names ("mfma",
+    "mfma16"); anything else refused"""
+    if method not in ("exact", "mfma", "mfma16"):
+        raise N.FspannArgumentError(f"method must be 'exact' or 'mfma' (or 'mfma16' for narrow rows): {method!r}")
+    return "" if method == "exact" else method
 
 
 def _typed_rows(vectors, dtype, what):
@@ -823,10 +824,25 @@ class FspannContext:
         N.check(self.L.fspann_groundtruth_mfma_store_dev(self._h, nq, q_ptr, k, out_ids_ptr, out_d2_ptr or None, C.byref(st)))
         self._gt_stats(st)
 
+    def groundtruth_mfma16_dev(self, n, base_ptr, base_dtype, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr=0):
+        """groundtruth_mfma_dev for narrow rows (N.U8, N.I8, N.F16, N.BF16, N.F8E4M3) with the pre-filter on the 16-bit matrix cores
+        (fspann_groundtruth_mfma16_dev): the same arguments, results and last_gt_stats; N.F32 rows are refused."""
+        st = N.GtMfmaStats()
+        N.check(self.L.fspann_groundtruth_mfma16_dev(self._h, n, base_ptr, base_dtype, nq, q_ptr, dim, k, out_ids_ptr, out_d2_ptr or None, C.byref(st)))
+        self._gt_stats(st)
+
+    def groundtruth_mfma16_store_dev(self, nq, q_ptr, k, out_ids_ptr, out_d2_ptr=0):
+        """groundtruth_mfma16_dev with the resident store as the base."""
+        st = N.GtMfmaStats()
+        N.check(self.L.fspann_groundtruth_mfma16_store_dev(self._h, nq, q_ptr, k, out_ids_ptr, out_d2_ptr or None, C.byref(st)))
+        self._gt_stats(st)
+
     def groundtruth_store(self, q, k, method="exact"):
         """Exact k-NN of host fp32 queries q [nq][dim] over the resident store: ids [nq][k] int32, squared distances [nq][k] float64.
-        method="mfma": the fp32 matrix-core pre-filter with an exact finish, the same arrays (last_gt_stats says what it did)."""
-        run = self.groundtruth_mfma_store_dev if _gt_method(method) else self.groundtruth_store_dev
+        method="mfma": the fp32 matrix-core pre-filter with an exact finish, the same arrays (last_gt_stats says what it did);
+        method="mfma16": the same on the 16-bit matrix cores, for a store of narrow rows."""
+        m = _gt_method(method)
+        run = getattr(self, f"groundtruth_{m}_store_dev") if m else self.groundtruth_store_dev
         qq = _c(q, np.float32)
         if qq.ndim != 2 or qq.shape[1] != self.cfg.dim:
             raise N.FspannArgumentError("q must be [nq][dim] of the context's dim")
@@ -855,8 +871,10 @@ class FspannContext:
         as fp32.  float64 rows are refused (the reference's ground truth reads floats: pass dtype=np.float32 to have them cast).
         Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n), what groundtruth() returns
         for the same values held as float32.  method="mfma": the fp32 matrix-core pre-filter with an exact finish
-        (groundtruth_mfma_dev), the same arrays; last_gt_stats says what it did."""
-        run = self.groundtruth_mfma_dev if _gt_method(method) else self.groundtruth_rows_dev
+        (groundtruth_mfma_dev), the same arrays; last_gt_stats says what it did.  method="mfma16": the same on the 16-bit matrix
+        cores (groundtruth_mfma16_dev), for every row type but float32."""
+        m = _gt_method(method)
+        run = getattr(self, f"groundtruth_{m}_dev") if m else self.groundtruth_rows_dev
         if dtype is None and getattr(base, "dtype", None) in (np.uint8, np.int8, np.float16):
             dtype = base.dtype
         b, code, _ = _typed_rows(base, dtype, "groundtruth_rows")
@@ -1417,7 +1435,8 @@ class FspannContext:
         """Exact k-NN of host arrays: uint8 arrays stay bytes on the device, int8 arrays signed bytes, anything else goes as fp32
         (base and q alike; bytes with anything but bytes of the same signedness do not match).
         Returns ids [nq][k] int32 (-1 beyond n) and squared distances [nq][k] float64 (+inf beyond n).  method="mfma": fp32 pairs
-        go through groundtruth_mfma_dev, the same arrays; a byte pair is refused (it runs on the int8 matrix cores as it is)."""
+        go through groundtruth_mfma_dev, the same arrays; a byte pair is refused (it runs on the int8 matrix cores as it is).
+        method="mfma16" is refused as fspann_groundtruth_mfma16_dev refuses fp32 rows: groundtruth_rows is the call for narrow rows."""
         mfma = _gt_method(method)
         base, q = np.asarray(base), np.asarray(q)
         if (base.dtype == np.uint8) != (q.dtype == np.uint8) or (base.dtype == np.int8) != (q.dtype == np.int8):
@@ -1426,8 +1445,9 @@ class FspannContext:
         b, qq = _c(base, dt), _c(q, dt)
         if mfma:
             if dt != np.float32:
-                raise N.FspannArgumentError("method='mfma' takes fp32 pairs: a byte pair is exact on the int8 matrix cores already (method='exact')")
-            return self._groundtruth_host(b, qq, k, lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_mfma_dev(n, bd, N.F32, nq, qd, dim, k, idd, d2d))
+                raise N.FspannArgumentError(f"method={method!r} takes fp32 pairs: a byte pair is exact on the int8 matrix cores already (method='exact')")
+            run = getattr(self, f"groundtruth_{mfma}_dev")
+            return self._groundtruth_host(b, qq, k, lambda n, bd, nq, qd, dim, idd, d2d: run(n, bd, N.F32, nq, qd, dim, k, idd, d2d))
         return self._groundtruth_host(b, qq, k, lambda n, bd, nq, qd, dim, idd, d2d: self.groundtruth_typed_dev(n, bd, _row_dt(b), nq, qd, _row_dt(qq), dim, k,
                                                                                                         idd, d2d))
 

@@ -1,13 +1,15 @@
-"""Dev tool: fspann_groundtruth_mfma_dev beside fspann_groundtruth_rows_dev over the same base, per row type.
+"""Dev tool: fspann_groundtruth_mfma_dev and fspann_groundtruth_mfma16_dev beside fspann_groundtruth_rows_dev over the same base, per
+row type.
 
-  python tools/gt_mfma_bench.py [--n 1000000] [--d 128] [--nq 1024] [--k 100] [--rows f32,f16,u8] [--rounds 3] [--exact-lib PATH] [--tag NAME]
+  python tools/gt_mfma_bench.py [--n 1000000] [--d 128] [--nq 1024] [--k 100] [--rows f32,f16,u8] [--methods exact,mfma,mfma16] [--rounds 3]
+                                [--exact-lib PATH] [--tag NAME]
 
 The method of tools/gt_rows_bench.py.  Per reading: device events around every whole call on its context's stream, WARM warm-up +
-TIMED timed calls, the median; the two calls and the row types alternate in one process, --rounds rounds each, and the spread of a
+TIMED timed calls, the median; the methods and the row types alternate in one process (mfma16 is left out for f32 rows), --rounds rounds each, and the spread of a
 figure is the range of its round medians.  --exact-lib: another build of libfspann_hip.so (the parent commit's) whose
 fspann_groundtruth_rows_dev is the exact reading, on a context of its own; without it this build's call is.  Rows are Gaussian
-(integers 128 + 32 g for u8, 32 g for i8), queries fp32 from the same distribution.  Before anything is timed both calls run at the
-timed size and must return the same arrays; the new call's stats are printed.
+(integers 128 + 32 g for u8, 32 g for i8), queries fp32 from the same distribution.  Before anything is timed every method runs at the
+timed size and must return the exact call's arrays; the pre-filtered calls' stats are printed.
 --once: that comparison only, one call each (what a kernel trace is taken of)."""
 import argparse
 import ctypes as C
@@ -72,12 +74,16 @@ if __name__ == "__main__":
     ap.add_argument("--nq", type=int, default=1024)
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--rows", default="f32,f16,u8")
+    ap.add_argument("--methods", default="exact,mfma")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--exact-lib", default=None)
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--tag", default="branch")
     a = ap.parse_args()
     n, d, nq, k, rows_list = a.n, a.d, a.nq, a.k, a.rows.split(",")
+    fast = [m for m in a.methods.split(",") if m != "exact"]
+    assert set(fast) <= {"mfma", "mfma16"}, a.methods
+    methods = lambda r: ["exact"] + [m for m in fast if not (m == "mfma16" and r == "f32")]
     print(f"# {a.tag}: lib {os.path.relpath(N._SO)}  exact call of {a.exact_lib or 'the same library'}  n={n} d={d} nq={nq} k={k}  rows {rows_list}  "
           f"{WARM} warm-up + {TIMED} timed calls per reading, {a.rounds} rounds", flush=True)
     gen = torch.Generator(device=DEV).manual_seed(1)
@@ -94,33 +100,36 @@ if __name__ == "__main__":
     cfg = pkg.PaperRuntimeConfig(tables=1, divisions=1, m=8, lambda_=2, dim=d)
     ctx = pkg.FspannContext(cfg, 0)
     ex = ExactLib(a.exact_lib, cfg) if a.exact_lib else ctx
-    out = {m: (torch.zeros((nq, k), dtype=torch.int32, device=DEV), torch.zeros((nq, k), dtype=torch.float64, device=DEV)) for m in ("exact", "mfma")}
+    out = {m: (torch.zeros((nq, k), dtype=torch.int32, device=DEV), torch.zeros((nq, k), dtype=torch.float64, device=DEV)) for m in ("exact", "mfma", "mfma16")}
     torch.cuda.synchronize()
 
     def call(m, r):
         oi, od = out[m]
-        f = ctx.groundtruth_mfma_dev if m == "mfma" else ex.groundtruth_rows_dev
+        f = ex.groundtruth_rows_dev if m == "exact" else getattr(ctx, f"groundtruth_{m}_dev")
         f(n, bases[r].data_ptr(), CDT[r], nq, qs[r].data_ptr(), d, k, oi.data_ptr(), od.data_ptr())
 
     for r in rows_list:
         call("exact", r)
-        call("mfma", r)
         ex.sync()
-        ctx.sync()
-        same = torch.equal(out["exact"][0], out["mfma"][0]) and torch.equal(out["exact"][1], out["mfma"][1])
-        print(f"{a.tag} rows={r}: ids and distances of the two calls equal at n={n} nq={nq}: {same}  stats {ctx.last_gt_stats}", flush=True)
-        assert same, r
-    meds = {(m, r): [] for m in ("exact", "mfma") for r in rows_list}
+        for m in methods(r)[1:]:
+            call(m, r)
+            ctx.sync()
+            same = torch.equal(out["exact"][0], out[m][0]) and torch.equal(out["exact"][1], out[m][1])
+            print(f"{a.tag} rows={r}: ids and distances of exact and {m} equal at n={n} nq={nq}: {same}  stats {ctx.last_gt_stats}", flush=True)
+            assert same, (r, m)
+    meds = {(m, r): [] for r in rows_list for m in methods(r)}
     for rnd in range(0 if a.once else a.rounds):
         for r in rows_list:
-            for m in ("exact", "mfma"):
+            for m in methods(r):
                 ts = timed(ex if m == "exact" else ctx, lambda: call(m, r))
                 meds[m, r].append(float(np.median(ts)))
                 print(f"{a.tag} groundtruth {m} rows={r} round={rnd}: median {meds[m, r][-1]:.2f} ms  min {ts.min():.2f}  max {ts.max():.2f}", flush=True)
     for r in rows_list if not a.once else []:
-        e, f = meds["exact", r], meds["mfma", r]
-        print(f"{a.tag} summary {r}: exact round medians {min(e):.2f}..{max(e):.2f} ms, mfma {min(f):.2f}..{max(f):.2f} ms, "
-              f"exact / mfma = {np.median(e) / np.median(f):.1f}", flush=True)
+        e = meds["exact", r]
+        for m in methods(r)[1:]:
+            f = meds[m, r]
+            print(f"{a.tag} summary {r}: exact round medians {min(e):.2f}..{max(e):.2f} ms, {m} {min(f):.2f}..{max(f):.2f} ms, "
+                  f"exact / {m} = {np.median(e) / np.median(f):.1f}", flush=True)
     if ex is not ctx:
         ex.close()
     ctx.close()

@@ -5,6 +5,12 @@
 
 namespace {
 
+// Grid of an MFMA tile kernel whose blocks take 32 RT rows x 128 CT projections (z: the slices of the split-k kernel)
+inline dim3 mfma_tile_grid(int64_t nq, int P, int RT, int CT, int z = 1) {
+    return dim3(static_cast<unsigned>((nq + mfma_tile_q(RT) - 1) / mfma_tile_q(RT)), static_cast<unsigned>((P + mfma_tile_p(CT) - 1) / mfma_tile_p(CT)),
+                static_cast<unsigned>(z));
+}
+
 // Slices of the split-k MFMA encode for a batch of nq rows (1: the unsplit 32 x 128 tile).  FSPANN_ENCODE_SPLITK forces a count; the
 // rule otherwise, settled by measurement (tools/encode_bench.py with SPLITK=..., profiles/notes/encode_splitk.txt): split only while
 // the slices together stay at or below one block per two CUs, at most four ways, and no slice shorter than four k tiles.  A slice's
@@ -17,7 +23,8 @@ inline int encode_splitk_slices(const fspann_ctx* c, int64_t nq) {
     const int KT = (c->cfg.dim + kMfmaKT - 1) / kMfmaKT;
     int S = c->knob_encode_splitk;
     if (S <= 0) {
-        const int64_t blocks = ((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)) * ((c->P_total + mfma_tile_p(1) - 1) / mfma_tile_p(1));
+        const dim3 tiles = mfma_tile_grid(nq, c->P_total, 1, 1);
+        const int64_t blocks = static_cast<int64_t>(tiles.x) * tiles.y;
         S = static_cast<int>(std::min<int64_t>(4, static_cast<int64_t>(c->num_cus) / (2 * blocks)));
         S = std::min(S, KT / 4);
     }
@@ -28,37 +35,29 @@ inline int encode_splitk_slices(const fspann_ctx* c, int64_t nq) {
 
 // The split-k kernel in place of the small tile (S >= 2 slices).  Work area: one arrival counter per 32 x 128 tile (cleared on the
 // stream, like the code words), then [tiles][S] slots of one block's partial (16 KB of accumulators + 32 norms + 32 flags).
-template <typename TIn>
-int launch_encode_mfma_splitk(fspann_ctx* c, int64_t nq, const TIn* q_dev, int32_t* hashes_dev, unsigned long long* cw, int32_t* bad_dev,
-                              int64_t* list, int64_t cap, unsigned long long* cnt, int S) {
-    const int P = c->P_total, d = c->cfg.dim;
-    const int KT = (d + kMfmaKT - 1) / kMfmaKT, per = (KT + S - 1) / S;
-    const dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)), static_cast<unsigned>((P + mfma_tile_p(1) - 1) / mfma_tile_p(1)),
-                    static_cast<unsigned>(S));
+// launch_tile, here and below: launch_encode_mfma's launcher (kernel, grid, block, LDS bytes, then what follows the 18 common arguments)
+template <typename TIn, typename LaunchTile>
+int launch_encode_mfma_splitk(fspann_ctx* c, int64_t nq, int S, LaunchTile launch_tile) {
+    const int KT = (c->cfg.dim + kMfmaKT - 1) / kMfmaKT, per = (KT + S - 1) / S;
+    const dim3 grid = mfma_tile_grid(nq, c->P_total, 1, 1, S);
     const size_t tiles = static_cast<size_t>(grid.x) * grid.y;
     const size_t ctr_bytes = (tiles * 4 + 255) / 256 * 256;
     int rc = ensure(c, c->ws_splitk, ctr_bytes + tiles * S * kSplitSlotBytes);
     if (rc) return rc;
     unsigned* arrive = static_cast<unsigned*>(c->ws_splitk.p);
     FSP_HIP(hipMemsetAsync(arrive, 0, tiles * 4, c->stream));
-    hipLaunchKernelGGL((encode_mfma_splitk_kernel<TIn>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P,
-                       c->cfg.m, c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max, per,
-                       static_cast<unsigned char*>(c->ws_splitk.p) + ctr_bytes, arrive);
+    launch_tile(encode_mfma_splitk_kernel<TIn>, grid, dim3(256), 0, per, static_cast<unsigned char*>(c->ws_splitk.p) + ctr_bytes, arrive);
     return FSPANN_OK;
 }
 
 // The k-wave kernel in place of the small tile: one workgroup of 4 G waves per 32 x 128 tile, the k tiles dealt to its G groups, the
 // join in LDS (no work area, nothing to clear).  G = 4 needs 84 352 B of dynamic LDS: the kernel's ceiling is raised once per context.
-template <typename TIn, int G>
-int launch_encode_mfma_kwave(fspann_ctx* c, int64_t nq, const TIn* q_dev, int32_t* hashes_dev, unsigned long long* cw, int32_t* bad_dev,
-                             int64_t* list, int64_t cap, unsigned long long* cnt) {
-    const int P = c->P_total;
+template <typename TIn, int G, typename LaunchTile>
+int launch_encode_mfma_kwave(fspann_ctx* c, int64_t nq, LaunchTile launch_tile) {
     constexpr size_t lds = encode_kwave_lds(G);
     if (lds > 64 * 1024)
         if (int rc = raise_lds_ceiling(c, encode_mfma_kwave_kernel<TIn, G>, lds)) return rc;
-    const dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)), static_cast<unsigned>((P + mfma_tile_p(1) - 1) / mfma_tile_p(1)));
-    hipLaunchKernelGGL((encode_mfma_kwave_kernel<TIn, G>), grid, dim3(256 * G), lds, c->stream, q_dev, nq, c->cfg.dim, c->fam->d_alphaT32.get(), c->fam->d_r.get(),
-                       c->fam->d_omega.get(), P, c->cfg.m, c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max);
+    launch_tile(encode_mfma_kwave_kernel<TIn, G>, mfma_tile_grid(nq, c->P_total, 1, 1), dim3(256 * G), lds);
     return FSPANN_OK;
 }
 
@@ -76,23 +75,23 @@ int launch_encode_mfma(fspann_ctx* c, int64_t nq, const TIn* q_dev, uint64_t* co
     // the code words start clear: the MFMA epilogue ORs in the bits of the pairs it can decide, encode_fix_kernel those of the rest
     FSP_HIP(hipMemsetAsync(codes_dev, 0, static_cast<size_t>(nq) * c->TD * c->W * 8, c->stream));
     unsigned long long* cw = reinterpret_cast<unsigned long long*>(codes_dev);
+    // an MFMA tile kernel: the 18 arguments they all begin with, then the kernel's own
+    auto launch_tile = [&](auto kernel, dim3 grid, dim3 block, size_t lds, auto... extra) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P, c->cfg.m,
+                           c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max, extra...);
+    };
     // block tile: 64 x 256 for bulk coding (Setup: hundreds of thousands of rows per call); 32 x 128 with tiles in flight for batches
     // of up to a few thousand blocks of the large tile (8 192 x 1 024 x 768: 273 against 327 us; equal at 262 144 rows)
     const int64_t big_blocks = ((nq + 63) / 64) * ((P + 255) / 256);
     if (kwaves == 2 || kwaves == 4) {
-        rc = (kwaves == 2) ? launch_encode_mfma_kwave<TIn, 2>(c, nq, q_dev, hashes_dev, cw, bad_dev, list, cap, cnt)
-                           : launch_encode_mfma_kwave<TIn, 4>(c, nq, q_dev, hashes_dev, cw, bad_dev, list, cap, cnt);
+        rc = (kwaves == 2) ? launch_encode_mfma_kwave<TIn, 2>(c, nq, launch_tile) : launch_encode_mfma_kwave<TIn, 4>(c, nq, launch_tile);
         if (rc) return rc;
     } else if (splitk > 1) {
-        if ((rc = launch_encode_mfma_splitk<TIn>(c, nq, q_dev, hashes_dev, cw, bad_dev, list, cap, cnt, splitk))) return rc;
+        if ((rc = launch_encode_mfma_splitk<TIn>(c, nq, splitk, launch_tile))) return rc;
     } else if (big_blocks >= 16 * static_cast<int64_t>(c->num_cus) && c->knob_mfma_tile != 1) {
-        dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(2) - 1) / mfma_tile_q(2)), static_cast<unsigned>((P + mfma_tile_p(2) - 1) / mfma_tile_p(2)));
-        hipLaunchKernelGGL((encode_mfma_kernel<TIn, 2, 2>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P, c->cfg.m,
-                           c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max);
+        launch_tile(encode_mfma_kernel<TIn, 2, 2>, mfma_tile_grid(nq, P, 2, 2), dim3(256), 0);
     } else {
-        dim3 grid(static_cast<unsigned>((nq + mfma_tile_q(1) - 1) / mfma_tile_q(1)), static_cast<unsigned>((P + mfma_tile_p(1) - 1) / mfma_tile_p(1)));
-        hipLaunchKernelGGL((encode_mfma_kernel<TIn, 1, 1>), grid, dim3(256), 0, c->stream, q_dev, nq, d, c->fam->d_alphaT32.get(), c->fam->d_r.get(), c->fam->d_omega.get(), P, c->cfg.m,
-                           c->cfg.lambda, c->W, c->TD, hashes_dev, cw, bad_dev, list, cap, cnt, c->fam->alpha_norm_max);
+        launch_tile(encode_mfma_kernel<TIn, 1, 1>, mfma_tile_grid(nq, P, 1, 1), dim3(256), 0);
     }
     FSP_HIP(hipGetLastError());
     // (a wave per kFixG pairs: as many blocks as the list can need, at most four per CU — the waves stride over the tasks)

@@ -37,6 +37,30 @@ def test_mfma_equals_exact(pkg, oracle, T, D, m, lam, d, nq):
             assert n_fix < 0.01 * h2.size + 8, n_fix            # the guard band is narrow on ordinary data
 
 
+def test_mfma_bulk_tile_equals_exact(pkg, oracle):
+    """The 64 x 256 tile (RT = CT = 2 epilogue) at the smallest batch that takes it.  Nothing reports which tile ran: the size follows
+    the rule in launch_encode_mfma, ceil(nq / 64) * ceil(P / 256) >= 16 x CUs.  P = 300: a second, partial column block, tables
+    that straddle 32-column blocks, two code words, d % 32 != 0; nq ends in a partial row block."""
+    import torch
+    T, D, m, lam, d = 3, 1, 100, 1, 40
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nq = 64 * ((16 * cus + 1) // 2) + 5                      # two column blocks: ceil(16 cus / 2) full row blocks, and five rows
+    rng, o, ctx, _ = _setup(pkg, oracle, T, D, m, lam, d, seed=41)
+    with ctx:
+        Q = (rng.standard_normal((nq, d)) * 2).astype(np.float32)
+        ends = np.r_[0:200, nq - 200:nq]
+        Qe = Q[ends].astype(np.float64)
+        ref_h, ref_c = o.hashes(Qe), o.encode(Qe)
+        ctx.set_encode_mode(1)
+        c1, h1 = ctx.encode(Q, want_hashes=True)
+        ctx.set_encode_mode(2)
+        c2, h2 = ctx.encode(Q, want_hashes=True)
+        assert ctx.last_encode_rechecked() > 0
+        assert np.array_equal(h2, h1) and np.array_equal(c2, c1)
+        assert np.array_equal(h1[ends], ref_h) and np.array_equal(c1[ends], ref_c)
+        assert np.array_equal(h2[ends], ref_h) and np.array_equal(c2[ends], ref_c)
+
+
 def test_mfma_boundary_cases_are_rechecked(pkg, oracle):
     """Vectors scaled so that (alpha.v + r)/omega lands within 1e-12..1e-6 of an integer."""
     T, D, m, lam, d = 4, 1, 16, 2, 64
